@@ -271,9 +271,12 @@ class OO_pqc_batch:
             wsz = self.lib.oovqe_orbital_hessian_work_size(self.nao, self._n_occ, self.ncas)
             self._plans[key] = (torch.empty(G * wsz, dtype=F64, device=self.device), 0)
         Hkk = torch.empty((G, nk, nk), dtype=F64, device=self.device)
+        # the copies stay referenced until the call is enqueued: a temporary freed inside the argument list goes back
+        # to the caching allocator at once, and the next copy can land in it before the kernel has read it
+        gamma0, Gamma0 = gamma[:, 0].contiguous(), Gamma[:, 0].contiguous()
         check(self.lib.oovqe_orbital_hessian_batch(
-            dptr(self.int2e_ao), dptr(self.int1e_ao), dptr(self.mo_coeff), dptr(gamma[:, 0].contiguous()),
-            dptr(Gamma[:, 0].contiguous()), dptr(fock), self.nao, self._n_occ, self.ncas,
+            dptr(self.int2e_ao), dptr(self.int1e_ao), dptr(self.mo_coeff), dptr(gamma0),
+            dptr(Gamma0), dptr(fock), self.nao, self._n_occ, self.ncas,
             dptr(self._kap_row, torch.int32), dptr(self._kap_col, torch.int32), nk, G, dptr(self._plans[key][0]),
             dptr(Hkk), int(self.eri_flags), stream_ptr()), "oovqe_orbital_hessian_batch")
         H[:, nt:, nt:] = Hkk

@@ -505,8 +505,9 @@ def circuit_hessian(theta, gates_dev, n_gates, n_qubits, ncas, init_index, c1, c
                            device=dev)
         _CHESS_WORK[key] = work
     H = torch.empty((n_theta, n_theta), dtype=F64, device=dev)
+    c1, c2 = c1.contiguous(), c2.contiguous()     # (referenced until the call is enqueued)
     check(lib.oovqe_circuit_hessian(dptr(th2), n_theta, dptr(gates_dev, torch.uint8), n_gates, n_qubits, ncas,
-                                    ctypes.c_uint32(init_index), dptr(c1.contiguous()), dptr(c2.contiguous()),
+                                    ctypes.c_uint32(init_index), dptr(c1), dptr(c2),
                                     dptr(pairs_dev, torch.int32), n_pairs, dptr(work), dptr(H), stream_ptr()),
           "oovqe_circuit_hessian")
     return H

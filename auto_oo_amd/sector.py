@@ -173,8 +173,9 @@ class SectorEngine:
         n = vecs.shape[0]
         out = torch.empty((n, self.Dc), dtype=F64, device=self.device)
         self.pair_lists()
-        check(self.lib.oovqe_sector_lambda(dptr(vecs), self.ncas, *self._tabs(), n, dptr(c1.contiguous()),
-                                           dptr(c2.contiguous()), self._tables_ptr, dptr(self.work(n)), dptr(out),
+        c1, c2 = c1.contiguous(), c2.contiguous()     # (referenced until the call is enqueued)
+        check(self.lib.oovqe_sector_lambda(dptr(vecs), self.ncas, *self._tabs(), n, dptr(c1),
+                                           dptr(c2), self._tables_ptr, dptr(self.work(n)), dptr(out),
                                            stream_ptr()),
               "oovqe_sector_lambda")
         return out
@@ -330,10 +331,11 @@ class SectorEngine:
         batch = theta.shape[0]
         dth = torch.empty((batch, self.n_theta), dtype=F64, device=self.device)
         pairs, max_pairs = self.pair_lists()
+        c1, c2 = c1.contiguous(), c2.contiguous()     # (referenced until the call is enqueued)
         check(self.lib.oovqe_sector_adjoint_pl(dptr(theta), self.n_theta,
                                                dptr(self.gates_dev, torch.uint8), self.n_gates,
                                                self.ncas, *self._tabs(), batch, dptr(psi_c),
-                                               dptr(c1.contiguous()), dptr(c2.contiguous()),
+                                               dptr(c1), dptr(c2),
                                                dptr(pairs, torch.int32), max_pairs, self._tables_ptr,
                                                dptr(self.work(batch)), dptr(dth), stream_ptr()),
               "oovqe_sector_adjoint_pl")

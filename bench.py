@@ -21,13 +21,17 @@ per-geometry energies/gradients at the end of the timed region.
 torch.distributed.run child process, started before anything touches the GPU); under torchrun the
 ranks read RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
-The JSON line also carries
+A plain run does only what the headline needs: set-up, priming and warm-up, the K timed steps, the
+outputs of the last step if `--dump-outputs DIR` is given (DIR/energy.npy, DIR/gradient.npy; the
+inputs are seeded, so two builds can be compared output for output), and the JSON line with
+`value` and `ms_per_step` (milliseconds per timed step).  With `--full` the JSON line also carries
   roofline      -- dominant kernel (the N^4 half-transform sweep) against the HBM roofline,
                    timed with HIP events on the launch stream inside the timed region;
   cpu_baseline  -- the CPU oracle (plain-torch restatement of the reference algorithm, "port")
                    timed on this box's host cores on a bounded sample (rank 0, N=1 only);
   transform     -- the second half of the headline metric: full (pq|rs)->(ij|kl) transform at
-                   N=200 (BASELINE.json configs[2]) in fp64 TFLOP/s against the 78.6 TF peak.
+                   N=200 (BASELINE.json configs[2]) in fp64 TFLOP/s against the 78.6 TF peak;
+and the pipelining, ingest, single-evaluation, Berry-phase-loop and kUpCCD figures.
 """
 import argparse
 import json
@@ -85,6 +89,15 @@ def parse():
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend: nccl (= RCCL, default) or gloo (rehearsal of the "
                          "N>1 path on a one-GPU box: all ranks share cuda:0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (HIP events around the timed launches), "
+                         "pipelining and ingest figures, single-evaluation latency, the Berry-phase-loop, "
+                         "CPU-baseline + parity, transform and kUpCCD extras (each --no-* flag still skips its "
+                         "part); off by default: a plain run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned to its caller as DIR/<name>.npy "
+                         "(float64): energy [geometries] and gradient [geometries, n_theta + n_kappa] of every "
+                         "geometry of the job")
     return ap.parse_args()
 
 
@@ -738,6 +751,25 @@ def oo_evaluation_large(N, g, C):
                     "stages are inside the time)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, gathered):
+    """What the timed path returned in its last step, for comparison between builds: the gathered rows
+    [E, dE/dtheta, dE/dkappa] of every geometry of the job as DIR/energy.npy [geometries] and
+    DIR/gradient.npy [geometries, n_theta + n_kappa], float64.  A job too large for 64 MB is cut to a fixed
+    sample of geometries (seed 0), whose indices go to DIR/geometry_index.npy."""
+    rows = gathered.detach().to("cpu", torch.float64).numpy()
+    keep = max(1, DUMP_LIMIT_BYTES // rows[0].nbytes)
+    os.makedirs(out_dir, exist_ok=True)
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(out_dir, "geometry_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "energy.npy"), np.ascontiguousarray(rows[:, 0]))
+    np.save(os.path.join(out_dir, "gradient.npy"), np.ascontiguousarray(rows[:, 1:]))
+
+
 def launch_command(n_ranks, port, argv):
     """The driver's own multi-GPU command line (one rank per GPU, rendezvous on 127.0.0.1)."""
     import socket
@@ -842,10 +874,11 @@ def main():
     # set-up (not part of W or K): every code path of the timed region runs once, so that lazily
     # loaded code objects (ours and torch's index_put/copy kernels used by the final exchange: ~30 ms
     # the first time a fresh box reads them from disk) are resident, and the GPU clocks have ramped.
-    # (the library's pool of HIP events is made on the first profile_begin: 16 384 hipEventCreate calls, ~20 ms of host
-    # time during which the GPU idles and its clocks fall -- made here, not in front of the timed region)
-    ops.profile_begin()
-    ops.profile_end()
+    # (--full: the library's pool of HIP events is made on the first profile_begin: 16 384 hipEventCreate calls, ~20 ms
+    # of host time during which the GPU idles and its clocks fall -- made here, not in front of the timed region)
+    if args.full:
+        ops.profile_begin()
+        ops.profile_end()
     # The exchange runs once BEFORE the priming: its first call reads torch's index_put kernel from disk (tens of
     # milliseconds with an idle GPU).  Rounds 1-4 made that call between the priming and the warm-up steps, the clocks
     # fell during it and needed ~25 steps (12 ms) to come back: with the driver's --warmup 5 the 20 timed steps ran
@@ -862,7 +895,8 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.profile_begin()   # HIP events around every half-transform launch, on its stream
+    if args.full:
+        ops.profile_begin()   # HIP events around every half-transform launch, on its stream
     if os.environ.get("OOVQE_BENCH_STEP_TIMES"):
         step_marks = [torch.cuda.Event(enable_timing=True)]
         step_marks[0].record()
@@ -882,155 +916,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    kern_total_ms, kern_count, _ = ops.profile_end()
+    if args.full:
+        kern_total_ms, kern_count, _ = ops.profile_end()
     if step_marks is not None:
         print("step intervals (us):", [round(a_.elapsed_time(b_) * 1e3, 1) for a_, b_ in zip(step_marks, step_marks[1:])],
               file=sys.stderr, flush=True)
         step_marks = None
 
-    # extras (untimed for `value`; SHORT BURSTS of 40 calls after other work, not the sustained regime of the headline:
-    # the chip runs this workload against its power limit and a burst finds higher clocks): the same steps as in-order
-    # calls on the current stream and as deferred calls over the two side streams, and deferred calls of 224 of the
-    # 256 geometries (the sweep then leaves 32 CUs to the tails of the previous call)
-    pipelining = None
-    if world == 1 and not args.general_eri:
-        def timed_calls(n, count, defer):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            pend = [batch.evaluate_deferred(thetas, count=count) if defer else batch.evaluate(thetas, count=count)
-                    for _ in range(n)]
-            if defer:
-                for p_ in pend:
-                    p_.result()
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t) / n
-        pipelining = {"headline_calls": "deferred" if deferred else "in order"}
-        for label, count, defer in (("in_order_256", G, False), ("deferred_256", G, True),
-                                    ("deferred_224", G - 32, True)):
-            if count < 1:
-                continue
-            timed_calls(6, count, defer)
-            t_c = min(timed_calls(40, count, defer) for _ in range(2))
-            pipelining[label] = {"geometries_per_call": count, "us_per_call": t_c * 1e6,
-                                 "evaluations_per_s": count / t_c}
-        pipelining["note"] = ("independent calls in bursts of 40; deferred = OO_pqc_batch.evaluate_deferred (two side streams / "
-                              "workspace slots in turn, N^4 sweeps of the two streams ordered one after the other, all calls "
-                              "joined at the end); bit-identical to the in-order calls "
-                              "(tests/test_full_size_gpu.py::test_deferred_evaluations_equal_the_in_order_calls_bit_for_bit).  "
-                              "In the SUSTAINED regime of the headline (0.5 s of priming in front of the timed steps) both forms "
-                              "give the same evaluations/s to within the run-to-run spread (bench.py --deferred): the sweep "
-                              "slows by what the overlapped tails take (its HIP-event duration 370 -> 410 us) -- the chip is "
-                              "power-limited on this workload (DESIGN.md section 5), so hiding latency does not buy throughput")
-    # ingest (untimed for `value`; SURVEY.md section 8(d) fixes g_ao): what it costs to make a geometry's integrals
-    # usable once they are in HBM -- the bitwise symmetry tests and the packed resident copy, ONE pass over the stack
-    # (oovqe_eri_ingest) -- and the host -> device copy of one geometry's tensors from pinned memory, separately
-    ingest = None
-    if world == 1 and not args.general_eri:
-        torch.cuda.synchronize()
-        t_i = []
-        for _ in range(3):
-            t = time.perf_counter()
-            batch.reverify_integrals()
-            torch.cuda.synchronize()
-            t_i.append(time.perf_counter() - t)
-        t_ing = min(t_i)
-        tensor_bytes = 8.0 * NAO ** 4
-        packed_bytes = 8.0 * batch._eri_packed.shape[1] if batch._eri_packed is not None else 0.0
-        host = torch.empty((NAO,) * 4, dtype=torch.float64).pin_memory()
-        host.copy_(batch.int2e_ao[0])
-        dst = torch.empty_like(batch.int2e_ao[0])
-        dst.copy_(host, non_blocking=True)
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(8):
-            dst.copy_(host, non_blocking=True)
-        torch.cuda.synchronize()
-        t_h2d = (time.perf_counter() - t) / 8
-        del host, dst
-        ingest = {"setup_us_per_geometry": t_ing / G * 1e6, "geometries": G, "ms_per_stack": t_ing * 1e3,
-                  "bytes_per_geometry": tensor_bytes + packed_bytes,
-                  "effective_GBs": (tensor_bytes + packed_bytes) * G / t_ing / 1e9,
-                  "frac_of_hbm_peak": (tensor_bytes + packed_bytes) * G / t_ing / 1e9 / HBM_PEAK_GBS,
-                  "h2d_us_per_geometry_pinned": t_h2d * 1e6, "h2d_GBs": tensor_bytes / t_h2d / 1e9,
-                  "evaluation_calls_equivalent": None,
-                  "note": "OO_pqc_batch.reverify_integrals() = oovqe_eri_ingest over the stack (every slab of g_ao read "
-                          "once: bitwise p<->q / r<->s tests, packed copy written; rounds 1-4: a check pass + a pack "
-                          "pass, 3.24 ms per 256 geometries) + mo_coeff refresh, one host readback of the flags included; "
-                          "the host->device copy of a geometry's 27 MB (pinned) is NOT in it and NOT in any figure of "
-                          "this line (SURVEY.md section 8(d): inputs resident in HBM)"}
-    # per-launch breakdown of one evaluation call, from a separate untimed pass (bracketing every
-    # launch costs dispatch gaps, so it is kept out of the timed region)
-    ops.profile_begin(detail=True)
-    run(16)
-    torch.cuda.synchronize()
-    kern_by = ops.profile_end()[2]
-    kern_s = kern_total_ms * 1e-3 / kern_count if kern_count else float("nan")
-    M = batch._n_occ + NCAS
-    # which stage-1 kernel the library picks (cas.hip: fused_plan): the persistent T3 kernel once a
-    # launch covers >= 48 slabs per CU, the one-slab-per-wave T2 kernel below that
-    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
-    t3_path = G * NAO ** 2 >= 48 * n_cu
-    # p<->q symmetric integrals (verified bit for bit when the batch was built, as PySCF's int2e
-    # is): the library reads only the N(N+1)/2 slabs p <= q -- the algorithmic bytes of the sweep
-    # are then 8 N^2 * N(N+1)/2 (half of SURVEY.md section 8(d)'s 8 N^4) + the packed J written
-    pq_sym = bool(batch.eri_flags & ops.ERI_PQ_SYMMETRIC)
-    rs_sym = bool(batch.eri_flags & ops.ERI_RS_SYMMETRIC)
-    # the stage-1 kernel the library actually dispatched for the timed calls (name + template arguments)
-    from auto_oo_amd import _lib as _aoo_lib
-    dispatched = _aoo_lib.load().oovqe_last_stage1_kernel().decode()
-    tri = NAO * (NAO + 1) // 2
-    if pq_sym and t3_path:
-        bytes_per_eval = 8.0 * NAO ** 2 * tri + 8.0 * tri * M ** 2
-        if rs_sym:
-            # each slab is symmetric too: the packed copy holds its upper triangle only, and only
-            # the columns y <= z of its result are written
-            slab_elems = sum(NAO - (r & ~1) for r in range(NAO))   # upper triangle, even row starts
-            bytes_per_eval = 8.0 * slab_elems * tri + 8.0 * tri * (M * (M + 1) // 2)
-        kernel_name = (dispatched
-                       + " (J[p<=q,y,z] = sum_rs C[r,y] g[p,q,r,s] C[s,z] over the "
-                       "upper triangle of slabs"
-                       + (", streaming the packed copy (upper triangle of each slab)"
-                          if rs_sym else "")
-                       + "; integrals verified p<->q" + (" and r<->s" if rs_sym else "") + " symmetric)")
-    elif pq_sym:
-        bytes_per_eval = 8.0 * NAO ** 2 * tri + 8.0 * NAO ** 2 * M ** 2
-        kernel_name = (dispatched + ", slabs p <= q mirrored into T2[p,q] and T2[q,p] "
-                       "(integrals verified p<->q symmetric)")
-    elif t3_path:
-        # g_ao read once + T3 (8 N M^3) written
-        bytes_per_eval = 8.0 * NAO ** 4 + 8.0 * NAO * M ** 3
-        kernel_name = (dispatched + " (T3[p,x,y,z] = sum_q C[q,x] "
-                       "sum_rs C[r,y] g[p,q,r,s] C[s,z])")
-    else:
-        bytes_per_eval = 8.0 * NAO ** 4 + 8.0 * NAO ** 2 * M ** 2
-        kernel_name = dispatched + " (T2[p,q,y,z] = sum_rs C[r,y] g[p,q,r,s] C[s,z])"
-    # evaluations per launch from the calls made (the event pool brackets at most 8192 launches of
-    # a long run: the average duration is then over those, the bytes are still per launch)
-    evals_per_launch = float(G)
-    if kern_count < min(args.steps, 8192):
-        raise SystemExit(f"roofline: only {kern_count} of {args.steps} stage-1 launches were bracketed")
-    alg_bytes = bytes_per_eval * evals_per_launch                   # per launch (batched)
-    achieved = alg_bytes / kern_s / 1e9
-    # HBM traffic of that kernel from the rocprofv3 PMC passes (FETCH_SIZE x2 [gfx950 correction] +
-    # WRITE_SIZE, separate passes; profiles/pmc_half_transform.json), scaled to this launch size
-    traffic, traffic_note = None, None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_half_transform.json")
-    if os.path.exists(pmc_path) and t3_path:        # (the PMC passes were taken on the batched kernel)
-        try:
-            import hashlib
-            with open(pmc_path) as fh:
-                pmc = json.load(fh)
-            with open(os.path.join(ROOT, "auto_oo_amd", "csrc", "cas.hip"), "rb") as fh:
-                sha = hashlib.sha256(fh.read()).hexdigest()
-            # the counters belong to ONE build of the stage-1 source and to ONE kernel: anything else gets no figure
-            if pmc.get("cas_hip_sha256") != sha:
-                traffic_note = "profiles/pmc_half_transform.json was measured on another version of cas.hip"
-            elif not pmc.get("kernel", "").startswith(dispatched):
-                traffic_note = f"profiles/pmc_half_transform.json is about {pmc.get('kernel')!r}, not {dispatched!r}"
-            elif pmc.get("pq_symmetric", False) == pq_sym:
-                traffic = pmc["hbm_bytes_per_launch"] / pmc.get("geometries_per_launch", 64) * evals_per_launch
-        except Exception as exc:
-            traffic, traffic_note = None, f"pmc file unreadable: {exc}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered)
 
     out = {
         "metric": METRIC,
@@ -1060,15 +954,164 @@ def main():
             "timed_region_us": {"enqueue_and_join": t_submit * 1e6, "exchange_enqueued_at": t_gather * 1e6,
                                 "elapsed": elapsed * 1e6},
             "parallelism": f"geometry-sharded x{world}, one all_gather at the end",
-            "pipelining": pipelining,
-            "ingest": ingest,
             # what torch.distributed itself reports (a SCALE line proves RCCL saw N ranks)
             "dist_backend": dist.get_backend() if dist is not None else None,
             "dist_world_size": dist.get_world_size() if dist is not None else 1,
             "devices_visible": torch.cuda.device_count(),
             "device_of_rank0": torch.cuda.current_device(),
         },
-        "roofline": {
+    }
+    if n_geom_total <= 64:
+        # small jobs (tests): the gathered energies bit for bit, geometry by geometry
+        out["gathered_energies_hex"] = [float(e).hex() for e in gathered[:, 0].tolist()]
+    if args.full:
+        # extras (untimed for `value`; SHORT BURSTS of 40 calls after other work, not the sustained regime of the headline:
+        # the chip runs this workload against its power limit and a burst finds higher clocks): the same steps as in-order
+        # calls on the current stream and as deferred calls over the two side streams, and deferred calls of 224 of the
+        # 256 geometries (the sweep then leaves 32 CUs to the tails of the previous call)
+        pipelining = None
+        if world == 1 and not args.general_eri:
+            def timed_calls(n, count, defer):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                pend = [batch.evaluate_deferred(thetas, count=count) if defer else batch.evaluate(thetas, count=count)
+                        for _ in range(n)]
+                if defer:
+                    for p_ in pend:
+                        p_.result()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t) / n
+            pipelining = {"headline_calls": "deferred" if deferred else "in order"}
+            for label, count, defer in (("in_order_256", G, False), ("deferred_256", G, True),
+                                        ("deferred_224", G - 32, True)):
+                if count < 1:
+                    continue
+                timed_calls(6, count, defer)
+                t_c = min(timed_calls(40, count, defer) for _ in range(2))
+                pipelining[label] = {"geometries_per_call": count, "us_per_call": t_c * 1e6,
+                                     "evaluations_per_s": count / t_c}
+            pipelining["note"] = ("independent calls in bursts of 40; deferred = OO_pqc_batch.evaluate_deferred (two side streams / "
+                                  "workspace slots in turn, N^4 sweeps of the two streams ordered one after the other, all calls "
+                                  "joined at the end); bit-identical to the in-order calls "
+                                  "(tests/test_full_size_gpu.py::test_deferred_evaluations_equal_the_in_order_calls_bit_for_bit).  "
+                                  "In the SUSTAINED regime of the headline (0.5 s of priming in front of the timed steps) both forms "
+                                  "give the same evaluations/s to within the run-to-run spread (bench.py --deferred): the sweep "
+                                  "slows by what the overlapped tails take (its HIP-event duration 370 -> 410 us) -- the chip is "
+                                  "power-limited on this workload (DESIGN.md section 5), so hiding latency does not buy throughput")
+        # ingest (untimed for `value`; SURVEY.md section 8(d) fixes g_ao): what it costs to make a geometry's integrals
+        # usable once they are in HBM -- the bitwise symmetry tests and the packed resident copy, ONE pass over the stack
+        # (oovqe_eri_ingest) -- and the host -> device copy of one geometry's tensors from pinned memory, separately
+        ingest = None
+        if world == 1 and not args.general_eri:
+            torch.cuda.synchronize()
+            t_i = []
+            for _ in range(3):
+                t = time.perf_counter()
+                batch.reverify_integrals()
+                torch.cuda.synchronize()
+                t_i.append(time.perf_counter() - t)
+            t_ing = min(t_i)
+            tensor_bytes = 8.0 * NAO ** 4
+            packed_bytes = 8.0 * batch._eri_packed.shape[1] if batch._eri_packed is not None else 0.0
+            host = torch.empty((NAO,) * 4, dtype=torch.float64).pin_memory()
+            host.copy_(batch.int2e_ao[0])
+            dst = torch.empty_like(batch.int2e_ao[0])
+            dst.copy_(host, non_blocking=True)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(8):
+                dst.copy_(host, non_blocking=True)
+            torch.cuda.synchronize()
+            t_h2d = (time.perf_counter() - t) / 8
+            del host, dst
+            ingest = {"setup_us_per_geometry": t_ing / G * 1e6, "geometries": G, "ms_per_stack": t_ing * 1e3,
+                      "bytes_per_geometry": tensor_bytes + packed_bytes,
+                      "effective_GBs": (tensor_bytes + packed_bytes) * G / t_ing / 1e9,
+                      "frac_of_hbm_peak": (tensor_bytes + packed_bytes) * G / t_ing / 1e9 / HBM_PEAK_GBS,
+                      "h2d_us_per_geometry_pinned": t_h2d * 1e6, "h2d_GBs": tensor_bytes / t_h2d / 1e9,
+                      "evaluation_calls_equivalent": None,
+                      "note": "OO_pqc_batch.reverify_integrals() = oovqe_eri_ingest over the stack (every slab of g_ao read "
+                              "once: bitwise p<->q / r<->s tests, packed copy written; rounds 1-4: a check pass + a pack "
+                              "pass, 3.24 ms per 256 geometries) + mo_coeff refresh, one host readback of the flags included; "
+                              "the host->device copy of a geometry's 27 MB (pinned) is NOT in it and NOT in any figure of "
+                              "this line (SURVEY.md section 8(d): inputs resident in HBM)"}
+        # per-launch breakdown of one evaluation call, from a separate untimed pass (bracketing every
+        # launch costs dispatch gaps, so it is kept out of the timed region)
+        ops.profile_begin(detail=True)
+        run(16)
+        torch.cuda.synchronize()
+        kern_by = ops.profile_end()[2]
+        kern_s = kern_total_ms * 1e-3 / kern_count if kern_count else float("nan")
+        M = batch._n_occ + NCAS
+        # which stage-1 kernel the library picks (cas.hip: fused_plan): the persistent T3 kernel once a
+        # launch covers >= 48 slabs per CU, the one-slab-per-wave T2 kernel below that
+        n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+        t3_path = G * NAO ** 2 >= 48 * n_cu
+        # p<->q symmetric integrals (verified bit for bit when the batch was built, as PySCF's int2e
+        # is): the library reads only the N(N+1)/2 slabs p <= q -- the algorithmic bytes of the sweep
+        # are then 8 N^2 * N(N+1)/2 (half of SURVEY.md section 8(d)'s 8 N^4) + the packed J written
+        pq_sym = bool(batch.eri_flags & ops.ERI_PQ_SYMMETRIC)
+        rs_sym = bool(batch.eri_flags & ops.ERI_RS_SYMMETRIC)
+        # the stage-1 kernel the library actually dispatched for the timed calls (name + template arguments)
+        from auto_oo_amd import _lib as _aoo_lib
+        dispatched = _aoo_lib.load().oovqe_last_stage1_kernel().decode()
+        tri = NAO * (NAO + 1) // 2
+        if pq_sym and t3_path:
+            bytes_per_eval = 8.0 * NAO ** 2 * tri + 8.0 * tri * M ** 2
+            if rs_sym:
+                # each slab is symmetric too: the packed copy holds its upper triangle only, and only
+                # the columns y <= z of its result are written
+                slab_elems = sum(NAO - (r & ~1) for r in range(NAO))   # upper triangle, even row starts
+                bytes_per_eval = 8.0 * slab_elems * tri + 8.0 * tri * (M * (M + 1) // 2)
+            kernel_name = (dispatched
+                           + " (J[p<=q,y,z] = sum_rs C[r,y] g[p,q,r,s] C[s,z] over the "
+                           "upper triangle of slabs"
+                           + (", streaming the packed copy (upper triangle of each slab)"
+                              if rs_sym else "")
+                           + "; integrals verified p<->q" + (" and r<->s" if rs_sym else "") + " symmetric)")
+        elif pq_sym:
+            bytes_per_eval = 8.0 * NAO ** 2 * tri + 8.0 * NAO ** 2 * M ** 2
+            kernel_name = (dispatched + ", slabs p <= q mirrored into T2[p,q] and T2[q,p] "
+                           "(integrals verified p<->q symmetric)")
+        elif t3_path:
+            # g_ao read once + T3 (8 N M^3) written
+            bytes_per_eval = 8.0 * NAO ** 4 + 8.0 * NAO * M ** 3
+            kernel_name = (dispatched + " (T3[p,x,y,z] = sum_q C[q,x] "
+                           "sum_rs C[r,y] g[p,q,r,s] C[s,z])")
+        else:
+            bytes_per_eval = 8.0 * NAO ** 4 + 8.0 * NAO ** 2 * M ** 2
+            kernel_name = dispatched + " (T2[p,q,y,z] = sum_rs C[r,y] g[p,q,r,s] C[s,z])"
+        # evaluations per launch from the calls made (the event pool brackets at most 8192 launches of
+        # a long run: the average duration is then over those, the bytes are still per launch)
+        evals_per_launch = float(G)
+        if kern_count < min(args.steps, 8192):
+            raise SystemExit(f"roofline: only {kern_count} of {args.steps} stage-1 launches were bracketed")
+        alg_bytes = bytes_per_eval * evals_per_launch                   # per launch (batched)
+        achieved = alg_bytes / kern_s / 1e9
+        # HBM traffic of that kernel from the rocprofv3 PMC passes (FETCH_SIZE x2 [gfx950 correction] +
+        # WRITE_SIZE, separate passes; profiles/pmc_half_transform.json), scaled to this launch size
+        traffic, traffic_note = None, None
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_half_transform.json")
+        if os.path.exists(pmc_path) and t3_path:        # (the PMC passes were taken on the batched kernel)
+            try:
+                import hashlib
+                with open(pmc_path) as fh:
+                    pmc = json.load(fh)
+                with open(os.path.join(ROOT, "auto_oo_amd", "csrc", "cas.hip"), "rb") as fh:
+                    sha = hashlib.sha256(fh.read()).hexdigest()
+                # the counters belong to ONE build of the stage-1 source and to ONE kernel: anything else gets no figure
+                if pmc.get("cas_hip_sha256") != sha:
+                    traffic_note = "profiles/pmc_half_transform.json was measured on another version of cas.hip"
+                elif not pmc.get("kernel", "").startswith(dispatched):
+                    traffic_note = f"profiles/pmc_half_transform.json is about {pmc.get('kernel')!r}, not {dispatched!r}"
+                elif pmc.get("pq_symmetric", False) == pq_sym:
+                    traffic = pmc["hbm_bytes_per_launch"] / pmc.get("geometries_per_launch", 64) * evals_per_launch
+            except Exception as exc:
+                traffic, traffic_note = None, f"pmc file unreadable: {exc}"
+
+        out["config"]["pipelining"] = pipelining
+        out["config"]["ingest"] = ingest
+        out["roofline"] = {
             "kernel": kernel_name,
             "eri_pq_symmetric": pq_sym,
             "bound": "hbm",
@@ -1088,75 +1131,72 @@ def main():
             "avg_launch_us": kern_s * 1e6,
             "all_launches_avg_us": {k: (v[0] / v[1] * 1e3 if v[1] else None) for k, v in kern_by.items()},
             "launches_timed": kern_count,
-        },
-    }
-    if ingest is not None:
-        ingest["evaluation_calls_equivalent"] = ingest["ms_per_stack"] / out["ms_per_step"]
-    if pq_sym and rs_sym and t3_path and NAO == 43 and M == 9:
-        # The same launch against the fp64 matrix pipe (informational; DESIGN.md "What bounds stage 1": the
-        # kernel is bound by MFMA issue at a power-limited clock, not by HBM).  34 v_mfma_f64_16x16x4 per
-        # slab (11 + 4 + 8 first products, 3 + 4 + 4 second), 2 048 flop each, padding included.
-        mfma_flops = 34 * 2048.0 * tri * evals_per_launch
-        out["roofline"]["mfma_view"] = {
-            "mfma_instructions_per_slab": 34,
-            "achieved_TFLOPs_incl_tile_padding": mfma_flops / kern_s / 1e12,
-            "peak_TFLOPs": 78.6,
-            "frac_of_peak_at_2.4GHz": mfma_flops / kern_s / 1e12 / 78.6,
-            # 34 x 64 pipe cycles per slab, 946 slabs per geometry, 1 024 SIMDs: the launch cannot be shorter
-            "pipe_floor_us_at_2.4GHz": 34 * 64.0 * tri * evals_per_launch / 1024 / 2.4e3,
-            "pipe_floor_us_at_1.75GHz": 34 * 64.0 * tri * evals_per_launch / 1024 / 1.75e3,
-            "frac_of_pipe_floor_at_1.75GHz": (34 * 64.0 * tri * evals_per_launch / 1024 / 1.75e3) / (kern_s * 1e6),
-            "useful_flop_share_of_issued": (2.0 * 967 * 9 + 2.0 * 43 * 81) / (34 * 2048.0),
-            "note": "the core clock under this kernel is ~1.75 GHz (power-limited with the HBM stream: tools/tri_spread.hip, "
-                    "profiles/r02_t_stage1_cycles.txt); against the matrix pipe at that clock the launch stands at "
-                    "frac_of_pipe_floor -- the HBM fraction understates how close the kernel is to ITS bound",
         }
-    if n_geom_total <= 64:
-        # small jobs (tests): the gathered energies bit for bit, geometry by geometry
-        out["gathered_energies_hex"] = [float(e).hex() for e in gathered[:, 0].tolist()]
-    if rank == 0 and world == 1:
-        # latency of ONE un-batched evaluation through the drop-in API (not the headline)
-        th0 = thetas[0].contiguous()
-        t_w = time.perf_counter()
-        while time.perf_counter() - t_w < 0.2:          # clocks up after the host-side work above
-            for _ in range(50):
+        if ingest is not None:
+            ingest["evaluation_calls_equivalent"] = ingest["ms_per_stack"] / out["ms_per_step"]
+        if pq_sym and rs_sym and t3_path and NAO == 43 and M == 9:
+            # The same launch against the fp64 matrix pipe (informational; DESIGN.md "What bounds stage 1": the
+            # kernel is bound by MFMA issue at a power-limited clock, not by HBM).  34 v_mfma_f64_16x16x4 per
+            # slab (11 + 4 + 8 first products, 3 + 4 + 4 second), 2 048 flop each, padding included.
+            mfma_flops = 34 * 2048.0 * tri * evals_per_launch
+            out["roofline"]["mfma_view"] = {
+                "mfma_instructions_per_slab": 34,
+                "achieved_TFLOPs_incl_tile_padding": mfma_flops / kern_s / 1e12,
+                "peak_TFLOPs": 78.6,
+                "frac_of_peak_at_2.4GHz": mfma_flops / kern_s / 1e12 / 78.6,
+                # 34 x 64 pipe cycles per slab, 946 slabs per geometry, 1 024 SIMDs: the launch cannot be shorter
+                "pipe_floor_us_at_2.4GHz": 34 * 64.0 * tri * evals_per_launch / 1024 / 2.4e3,
+                "pipe_floor_us_at_1.75GHz": 34 * 64.0 * tri * evals_per_launch / 1024 / 1.75e3,
+                "frac_of_pipe_floor_at_1.75GHz": (34 * 64.0 * tri * evals_per_launch / 1024 / 1.75e3) / (kern_s * 1e6),
+                "useful_flop_share_of_issued": (2.0 * 967 * 9 + 2.0 * 43 * 81) / (34 * 2048.0),
+                "note": "the core clock under this kernel is ~1.75 GHz (power-limited with the HBM stream: tools/tri_spread.hip, "
+                        "profiles/r02_t_stage1_cycles.txt); against the matrix pipe at that clock the launch stands at "
+                        "frac_of_pipe_floor -- the HBM fraction understates how close the kernel is to ITS bound",
+            }
+        if rank == 0 and world == 1:
+            # latency of ONE un-batched evaluation through the drop-in API (not the headline)
+            th0 = thetas[0].contiguous()
+            t_w = time.perf_counter()
+            while time.perf_counter() - t_w < 0.2:          # clocks up after the host-side work above
+                for _ in range(50):
+                    single.energy_and_gradient(th0)
+                torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(500):
                 single.energy_and_gradient(th0)
             torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(500):
-            single.energy_and_gradient(th0)
-        torch.cuda.synchronize()
-        out["single_eval_us"] = (time.perf_counter() - t1) / 500 * 1e6
-    if not args.no_berry:
-        # configs[3]: the 64-geometry Berry-phase-loop workload.  "strong": --berry-geoms geometries in
-        # the whole job, split over the GPUs (the north star's >= 6x at 8 GPUs is about this one);
-        # "weak": --berry-geoms geometries per GPU (the same run when n_gpus = 1).
-        nb = max(args.berry_geoms, world)
-        strong_geoms = shard_geometries(nb, rank, world)
-        strong = berry_loop_extra(strong_geoms, nb, dist, world, args.backend, "strong")
-        if world > 1:
-            weak_geoms = shard_geometries(nb * world, rank, world)
-            weak = berry_loop_extra(weak_geoms, nb * world, dist, world, args.backend, "weak")
-        else:
-            weak = dict(strong, scaling=f"weak ({nb} geometries per GPU; identical to the strong run at 1 GPU)")
-        # the same workload in the regime the reference's loop runs in (one step per loop point from the
-        # previous point's solution: positive definite Hessians), strong figure only
-        tracking = berry_loop_extra(strong_geoms, nb, dist, world, args.backend, "strong", regime="tracking")
+            out["single_eval_us"] = (time.perf_counter() - t1) / 500 * 1e6
+        if not args.no_berry:
+            # configs[3]: the 64-geometry Berry-phase-loop workload.  "strong": --berry-geoms geometries in
+            # the whole job, split over the GPUs (the north star's >= 6x at 8 GPUs is about this one);
+            # "weak": --berry-geoms geometries per GPU (the same run when n_gpus = 1).
+            nb = max(args.berry_geoms, world)
+            strong_geoms = shard_geometries(nb, rank, world)
+            strong = berry_loop_extra(strong_geoms, nb, dist, world, args.backend, "strong")
+            if world > 1:
+                weak_geoms = shard_geometries(nb * world, rank, world)
+                weak = berry_loop_extra(weak_geoms, nb * world, dist, world, args.backend, "weak")
+            else:
+                weak = dict(strong, scaling=f"weak ({nb} geometries per GPU; identical to the strong run at 1 GPU)")
+            # the same workload in the regime the reference's loop runs in (one step per loop point from the
+            # previous point's solution: positive definite Hessians), strong figure only
+            tracking = berry_loop_extra(strong_geoms, nb, dist, world, args.backend, "strong", regime="tracking")
+            if rank == 0:
+                out["berry_loop"] = {"strong": strong, "weak": weak, "tracking_strong": tracking}
         if rank == 0:
-            out["berry_loop"] = {"strong": strong, "weak": weak, "tracking_strong": tracking}
+            if world == 1 and not args.no_cpu_baseline:
+                cb, e_ref, g_ref = cpu_baseline()
+                out["cpu_baseline"] = cb
+                # parity of what was just benchmarked (geometry 0) against the oracle
+                e_gpu = float(gathered[0, 0].item())
+                out["parity"] = {"dE_vs_oracle": abs(e_gpu - e_ref),
+                                 "max_dgrad_vs_oracle":
+                                     float((gathered[0, 1:].cpu() - g_ref).abs().max())}
+            if world == 1 and not args.no_transform:
+                out["transform"] = transform_microbench(args.transform_n)
+            if world == 1 and not args.no_kupccd:
+                out["kupccd_cas88"] = kupccd_extra()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            cb, e_ref, g_ref = cpu_baseline()
-            out["cpu_baseline"] = cb
-            # parity of what was just benchmarked (geometry 0) against the oracle
-            e_gpu = float(gathered[0, 0].item())
-            out["parity"] = {"dE_vs_oracle": abs(e_gpu - e_ref),
-                             "max_dgrad_vs_oracle":
-                                 float((gathered[0, 1:].cpu() - g_ref).abs().max())}
-        if world == 1 and not args.no_transform:
-            out["transform"] = transform_microbench(args.transform_n)
-        if world == 1 and not args.no_kupccd:
-            out["kupccd_cas88"] = kupccd_extra()
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

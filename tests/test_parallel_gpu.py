@@ -96,7 +96,7 @@ def test_two_gpu_rccl_job_matches_one_process():
     same shards, and the strong leg of the Berry-phase loop ran on both ranks."""
     import bench
     geoms_per_rank = 4
-    cmd = bench.launch_command(2, 0, ["--gpus", "2", "--backend", "nccl", "--steps", "2", "--warmup", "1",
+    cmd = bench.launch_command(2, 0, ["--gpus", "2", "--backend", "nccl", "--steps", "2", "--warmup", "1", "--full",
                                       "--geoms", str(geoms_per_rank), "--no-cpu-baseline", "--no-transform",
                                       "--no-kupccd", "--berry-geoms", "4", "--prime-seconds", "0.05"])
     res = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=1200, cwd=ROOT)
