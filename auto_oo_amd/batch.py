@@ -350,6 +350,26 @@ class OO_pqc_batch:
             return self.evaluate(thetas, derivatives=False)[:, 1]
         return self.evaluate(thetas, derivatives=False, mo_coeff=self.rotated_mo_coeff(kappas))[:, 1]
 
+    # ---- exact reference of the stack ------------------------------------------------------------------
+    def casci(self, nroots=1, fix_singlet=True, tol=1e-9, max_iter=200):
+        """CASCI of every geometry at its current orbitals: the CAS coefficients of the whole stack from ONE
+        ``oovqe_cas_eval_batch`` call, then ONE Davidson launch (``oovqe_ci_davidson_batch``) reading c0 | c1 | c2
+        where that call leaves them.  -> (energies [G, nroots], ci [G, nroots, Dc]) on the device; the CI vectors
+        are in the sector layout of the circuit engine.  Raises when a geometry's solve does not converge."""
+        from . import ci
+        ci.check_scope(self.ncas, self.nelecas, nroots)
+        a = self.ncas
+        zero1 = torch.zeros((self.G, 1, a, a), dtype=F64, device=self.device)
+        zero2 = torch.zeros((self.G, 1) + (a,) * 4, dtype=F64, device=self.device)
+        cas, _, _ = self._cas_batch(zero1, zero2, self.G)
+        e, vecs, _, rn, info = ci.casci_packed(cas, 3 + self.n_kappa, a, self.nelecas, nroots, fix_singlet, tol,
+                                               max_iter)
+        bad = torch.nonzero(info != 0).flatten().tolist()
+        if bad:
+            raise RuntimeError(f"OO_pqc_batch.casci: geometries {bad} did not converge "
+                               f"(residuals {rn[bad].tolist()})")
+        return e, vecs
+
     # ---- orbital rotations of the whole stack -------------------------------------------------------
     def _rotate(self, C, kappas, out):
         kappas = ops.as_device(kappas, self.device).reshape(self.G, self.n_kappa)

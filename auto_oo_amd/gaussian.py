@@ -37,6 +37,8 @@ _STO3G = {
     "C": {"Z": 6, "1s": (71.6168370, 13.0450960, 3.5305122), "2sp": (2.9412494, 0.6834831, 0.2222899)},
     "N": {"Z": 7, "1s": (99.1061690, 18.0523120, 4.8856602), "2sp": (3.7804559, 0.8784966, 0.2857144)},
     "O": {"Z": 8, "1s": (130.7093200, 23.8088610, 6.4436083), "2sp": (5.0331513, 1.1695961, 0.3803890)},
+    # the shared STO-3G expansions scaled by Pople's standard exponents zeta(1s) = 8.65, zeta(2sp) = 2.55
+    "F": {"Z": 9, "1s": (166.6791340, 30.36081233, 8.216820672), "2sp": (6.464803249, 1.502281245, 0.4885884864)},
 }
 
 
@@ -54,14 +56,18 @@ def _rotation(axis, angle):
 def zmatrix_to_cartesian(zmat):
     """Z-matrix text (one atom per line: ``sym [ref dist [ref angle [ref dihedral]]]``, 1-based
     references, Angstrom / degrees) -> (symbols, coordinates [natm, 3] in Angstrom), laid out as
-    PySCF does: first atom at the origin, second on +x, third rotated about z x (bond vector)."""
+    PySCF does: first atom at the origin, second on +x, third rotated about z x (bond vector).
+    A line of four tokens ``sym x y z`` (never a valid Z-matrix line) is a Cartesian position in
+    Angstrom, as PySCF reads ``'H 0 0 0; F 0 0 1.1'``."""
     symbols, coord = [], []
     for line in zmat.replace(";", "\n").replace(",", " ").splitlines():
         tok = line.split()
         if not tok or tok[0].startswith("#"):
             continue
         symbols.append(tok[0])
-        if len(tok) < 3:
+        if len(tok) == 4:
+            coord.append(np.array([float(t) for t in tok[1:]]))
+        elif len(tok) < 3:
             coord.append(np.zeros(3))
         elif len(tok) == 3:
             coord.append(np.array([float(tok[2]), 0.0, 0.0]))
@@ -316,9 +322,10 @@ def rhf(int1e, int2e, overlap, n_occ, conv_tol=1e-12, max_cycle=200):
 
 class Moldata_sto3g(Moldata):
     """Stand-in for ``Moldata_pyscf(geometry, 'sto-3g')`` (src/auto_oo/moldata_pyscf.py:19-61) for
-    molecules of H, C, N, O: same attributes (``int1e_ao, int2e_ao, overlap, oao_coeff, nuc, nao``),
+    molecules of H, C, N, O, F: same attributes (``int1e_ao, int2e_ao, overlap, oao_coeff, nuc, nao``),
     ``run_rhf()`` -> ``hf.mo_coeff`` / ``hf.e_tot``.  ``geometry`` is a Z-matrix string (as
-    ``get_formal_geo`` returns) or a list of ``(symbol, (x, y, z))`` in Angstrom."""
+    ``get_formal_geo`` returns), a Cartesian string ``'H 0 0 0; F 0 0 1.1'`` or a list of
+    ``(symbol, (x, y, z))`` in Angstrom."""
 
     def __init__(self, geometry, basis="sto-3g", charge=0):
         if str(basis).lower().replace("-", "") != "sto3g":

@@ -63,6 +63,34 @@ class Moldata:
                     "to OO_energy / OO_pqc")
             self.hf = SimpleNamespace(mo_coeff=self._mo_coeff0)
 
+    # ---- exact active-space solutions (moldata_pyscf.py:63-105; device CI, auto_oo_amd/ci.py) ----------------
+    # Result objects carry e_tot, mo_coeff (AO->MO), ci ([na, nb] in the sector layout of the circuit engine,
+    # NOT PySCF's string order), s2 and converged; SA-CASSCF also e_states.
+    def run_fci(self, n_roots=1, fix_singlet=1, verbose=0):
+        """moldata_pyscf.py:63-72: CASCI over all orbitals at the RHF orbitals."""
+        from . import ci
+        ci.check_scope(self.nao, self.nelectron, n_roots)
+        self.fci = ci.run_casci(self, self.nao, self.nelectron, n_roots, None, fix_singlet, verbose)
+        return self.fci
+
+    def run_casci(self, ncas, nelecas, n_roots=1, mo=None, fix_singlet=1, verbose=0):
+        """moldata_pyscf.py:74-84; ``mo``: AO->MO coefficients (default: the RHF orbitals)."""
+        from . import ci
+        self.casci = ci.run_casci(self, ncas, nelecas, n_roots, mo, fix_singlet, verbose)
+        return self.casci
+
+    def run_casscf(self, ncas, nelecas, fix_singlet=1, verbose=0):
+        """moldata_pyscf.py:86-94: two-step CASSCF from the RHF orbitals."""
+        from . import ci
+        self.casscf = ci.run_casscf(self, ncas, nelecas, fix_singlet, verbose)
+        return self.casscf
+
+    def run_sa_casscf(self, ncas, nelecas, fix_singlet=1, verbose=0):
+        """moldata_pyscf.py:96-105: state-averaged CASSCF, weights [0.5, 0.5] on the two lowest singlets."""
+        from . import ci
+        self.sa_casscf = ci.run_sa_casscf(self, ncas, nelecas, fix_singlet, verbose)
+        return self.sa_casscf
+
     # ---- real-molecule inputs (SURVEY.md section 8(f) rank 3) -----------------------------------
     NPZ_KEYS = ("int1e_ao", "int2e_ao", "overlap", "nuc", "nelectron")
 

@@ -611,6 +611,23 @@ int oovqe_oo_newton_step_batch(const oovqe_newton_step_t* step, oovqe_stream_t s
 /* sizeof(oovqe_newton_step_t) in the library as built (a binding compares its mirror of the block with it) */
 int oovqe_newton_step_size(void);
 
+/* ---- determinant CI (ci.hip): batched block Davidson for the lowest roots of the active-space Hamiltonian
+ * H = c0 + c1 . E + c2 . (E E - E), c2 = g / 2 (the convention of oovqe_cas_eval*: E = c0 + c1.gamma + c2.Gamma),
+ * one workgroup per problem, every iteration inside ONE launch.  Problem b reads c0[b * c_stride],
+ * c1 + b * c_stride [a][a] and c2 + b * c_stride [a][a][a][a] (so c1 | c2 can be read where oovqe_cas_eval_batch
+ * leaves them).  Scope: ncas <= 8, nelecas even (N_alpha = N_beta), Dc = C(ncas, nelecas / 2)^2 <= 4900,
+ * 1 <= nroots <= min(4, Dc); anything else returns a negative code (oovqe_last_error gives the text).
+ * Outputs per problem: energies [nroots] (<H>), ci [nroots][Dc] in the sector layout c = ia * nb + ib with the
+ * strings and signs of the sector engine (orthonormal; the largest |component| positive), s2 [nroots] (<S^2>),
+ * rnorm [nroots] (residual norms), info = 0 converged, > 0 iterations done when stopped unconverged.
+ * fix_singlet: the sigma is that of H + S^2 (roots are singlets); the energy reported is <H>.
+ * work: oovqe_ci_work_size(ncas, nelecas, nroots, batch) doubles. */
+int64_t oovqe_ci_work_size(int ncas, int nelecas, int nroots, int batch);
+int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int batch, const double* c0, const double* c1,
+                            const double* c2, int64_t c_stride, int fix_singlet, double tol, int max_iter,
+                            double* energies, double* ci, double* s2, double* rnorm, int* info, double* work,
+                            oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
