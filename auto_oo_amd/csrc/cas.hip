@@ -3238,6 +3238,363 @@ void cas_final_kernel(const double* __restrict__ Fcol, const double* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The whole tail of a batched call in ONE workgroup per geometry ("tail" kernel; packed-triangle
+// path with p <-> q and r <-> s symmetric integrals, W = C^T h_ao left by the circuit launch):
+//   q -> x, p -> n   sym_gm_kernel's two MFMA steps, one 16-wide tile of (y <= z) at a time, the
+//                    result kept in LDS instead of written to memory -- and of g_mo[n, x, y, z] only
+//                    the entries stage 3 reads (tail_needed: 210 of 405 per n at M = 9, no = 6)
+//   stage 3          cas_panel_kernel's arithmetic for every n of the geometry, Fock columns in LDS
+//   assembly         cas_final_kernel's
+// Every sum runs in the order of those kernels: the results are those of the three launches, bit
+// for bit.  It replaces sym_gm_kernel + cas_panel_kernel + cas_final_kernel (g_mo: 2 x 64 MB of
+// memory traffic at 256 geometries, three grids of short latency-bound workgroups) by one launch;
+// measured at N = 43, M = 9, 256 geometries: see DESIGN.md section 5.
+// ------------------------------------------------------------------------------------------
+constexpr int TAIL_THREADS = 512;
+
+// the entries (x, {y, z}) of g_mo[n] that stage 3 reads (g_mo[n] is symmetric in y, z): (x, i, i) and
+// (i, i, x) of FI (i core), (m, V, W) and (W, V, m) of the core rows of a Fock column, the active block
+__host__ __device__ inline bool tail_needed(int x, int y, int z, int no)
+{
+    const int lo = y < z ? y : z, hi = y < z ? z : y;
+    if (lo >= no) return true;                               // both active
+    if (hi < no) return lo == hi || x == lo || x == hi;      // both core
+    return x >= no || x == lo;                               // lo core, hi active
+}
+
+template <int KS>
+__global__ __launch_bounds__(TAIL_THREADS, 2)
+void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C, const double* __restrict__ Wpre,
+                     const double* __restrict__ gamma, const double* __restrict__ Gamma, int nrdm, int N, int no,
+                     int na, int NC, double nuc, const double* __restrict__ nuc_arr,
+                     const int32_t* __restrict__ kap_row, const int32_t* __restrict__ kap_col, int n_kappa,
+                     double* __restrict__ c0, double* __restrict__ E, double* __restrict__ gvec,
+                     double* __restrict__ dE, double* __restrict__ c1, double* __restrict__ c2, size_t out_stride)
+{
+    extern __shared__ double lds[];
+    constexpr int NW = TAIL_THREADS / 64;
+    constexpr int PW = (4 * KS + NW - 1) / NW;       // rows p per wave in q -> x
+    constexpr int PB = PW * KS > 48 ? (PW + 1) / 2 : PW;   // of them with their loads in flight together
+    const int M = no + na, M2 = M * M, M3 = M2 * M;
+    const int na2 = na * na, na3 = na2 * na, na4 = na2 * na2;
+    const int ncol = M * (M + 1) / 2, nty = (ncol + 15) / 16;
+    const long tri = (long)N * (N + 1) / 2;
+    const int by = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lq = lane >> 4, lr = lane & 15;
+    {   // by = geometry of a batch
+        const size_t gi = by;
+        J += gi * nty * tri * 16;
+        C += gi * (size_t)N * N;
+        Wpre += gi * (size_t)N * N;
+        gamma += gi * (size_t)nrdm * na2;
+        Gamma += gi * (size_t)nrdm * na4;
+        c0 += gi * out_stride;
+        E += gi * out_stride;
+        gvec += gi * out_stride;
+        if (dE) dE += gi * out_stride;
+        c1 += gi * out_stride;
+        c2 += gi * out_stride;
+        if (nuc_arr) nuc = nuc_arr[gi];
+    }
+    double* Gc = lds;                                // [N][NC]   the kept entries of g_mo[n]
+    double* Cl = Gc + (size_t)N * NC;                // [N][M]    C[:, :M]
+    double* hn = Cl + (size_t)N * M;                 // [N][M]    h_mo
+    double* FIn = hn + (size_t)N * M;                // [N][M]
+    double* gml = FIn + (size_t)N * M;               // [nrdm][na2]
+    double* Gml = gml + (size_t)nrdm * na2;          // [nrdm][na4]
+    double* Cp = Gml + (size_t)nrdm * na4;           // [N]       Cpart
+    int* tab = reinterpret_cast<int*>(Cp + N);       // [M3]      position in Gc[n] of (x, y, z); -1: not kept
+    int* wcnt = tab + M3;                            // [NW]
+    int* krow = wcnt + NW;                           // [n_kappa]  kap_row
+    int* kcol = krow + n_kappa;                      // [n_kappa]  kap_col
+    double* scr = Cp + N + (M3 + NW + 2 * n_kappa + 1) / 2;   // W [N][N], then T3s [4 KS][LDP], then Fcol, Epart, Ga, Dc
+    const int LDP = M * 16 + 8;
+
+    // ---- q -> x, p -> n per tile of (y <= z) (sym_gm_kernel's arithmetic) ------------------------------
+    // J comes in (at most) two halves of the wave's rows per tile, each half's loads all in flight together;
+    // the first tile's first half is in flight under the staging of the inputs below (the workgroup barriers
+    // wait for LDS only)
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const __amdgpu_buffer_rsrc_t csrd = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double*>(C), 0, (int)((size_t)N * N * sizeof(double)), 0x00020000);
+    double af[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int q = 4 * ks + lq;
+        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
+            csrd, (q < N && lr < M) ? (unsigned)((q * N + lr) * (int)sizeof(double)) : 0x7fffffffu, 0, 0);
+        af[ks] = __builtin_bit_cast(double, v);
+    }
+    // rows h0 .. h0 + PB - 1 of the wave, tile ty
+    auto load_half = [&](double (&bf)[PB][KS], int ty, int h0) {
+        const __amdgpu_buffer_rsrc_t jsrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(J + (size_t)ty * tri * 16), 0, (int)(tri * 16 * sizeof(double)), 0x00020000);
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            const int p = wave + NW * (h0 + i);
+            const int pc = p < N ? p : N - 1;                           // wave-uniform
+            const int basep = pc * (2 * N - pc + 1) / 2 - pc;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                // triangle row of the pair (p, q): base(min) + max, base(a) = a (2N - a + 1) / 2 - a
+                const int q = 4 * ks + lq < N ? 4 * ks + lq : N - 1;
+                const int t = q < pc ? q * (2 * N - q + 1) / 2 - q + pc : basep + q;
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
+                    jsrd, (unsigned)((t * 16 + lr) * (int)sizeof(double)), 0, 0);
+                bf[i][ks] = __builtin_bit_cast(double, v);
+            }
+        }
+    };
+    double* T3s = scr;                               // [4 KS][LDP], rows p >= N are zero
+    auto mfma_half = [&](const double (&bf)[PB][KS], int h0) {
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            if (h0 + i >= PW) continue;
+            const int p = wave + NW * (h0 + i);
+            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(af[ks], bf[i][ks], acc);
+            double* row = T3s + (size_t)(p < 4 * KS ? p : 0) * LDP + lr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = lq + 4 * j;
+                if (x < M && p < 4 * KS) row[x * 16] = p < N ? acc[j] : 0.0;
+            }
+        }
+    };
+    static_assert(2 * PB >= PW, "two halves cover the rows of a wave");
+    double bf[PB][KS];
+    load_half(bf, 0, 0);
+
+    // ---- inputs; the position table by a ballot prefix over (x, y <= z) in order ------------------
+    for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
+        const int q = idx / M, x = idx - q * M;
+        Cl[idx] = C[(size_t)q * N + x];
+    }
+    for (int idx = tid; idx < N * N; idx += TAIL_THREADS) scr[idx] = Wpre[idx];
+    for (int idx = tid; idx < nrdm * na2; idx += TAIL_THREADS) gml[idx] = gamma[idx];
+    for (int idx = tid; idx < nrdm * na4; idx += TAIL_THREADS) Gml[idx] = Gamma[idx];
+    for (int idx = tid; idx < n_kappa; idx += TAIL_THREADS) {
+        krow[idx] = kap_row[idx];
+        kcol[idx] = kap_col[idx];
+    }
+    {
+        const int total = M * ncol;
+        int base = 0;
+        for (int i0 = 0; i0 < total; i0 += TAIL_THREADS) {
+            const int i = i0 + tid;
+            int x = 0, y = 0, z = 0;
+            bool need = false;
+            if (i < total) {
+                x = i / ncol;
+                tri_decode(i - x * ncol, M, y, z);
+                need = tail_needed(x, y, z, no);
+            }
+            const unsigned long long mask = __ballot(need);
+            const int below = __popcll(mask & ((1ull << lane) - 1ull));
+            if (lane == 0) wcnt[wave] = __popcll(mask);
+            __syncthreads();
+            int pre = base, all = 0;
+            for (int w = 0; w < NW; ++w) {
+                const int c = wcnt[w];
+                if (w < wave) pre += c;
+                all += c;
+            }
+            if (i < total) {
+                const int v = need ? pre + below : -1;
+                tab[(x * M + y) * M + z] = v;
+                tab[(x * M + z) * M + y] = v;
+            }
+            __syncthreads();
+            base += all;
+        }
+    }
+    // h_mo[n, x] = sum_q W[n, q] C[q, x]
+    for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
+        const int n = idx / M, x = idx - n * M;
+        double acc = 0.0;
+        for (int q = 0; q < N; ++q) acc += scr[(size_t)n * N + q] * Cl[q * M + x];
+        hn[idx] = acc;
+    }
+    __syncthreads();
+
+    {
+        const int ntn = (N + 15) / 16;
+        for (int ty = 0; ty < nty; ++ty) {
+            mfma_half(bf, 0);
+            if (PB < PW) {
+                load_half(bf, ty, PB);
+                mfma_half(bf, PB);
+            }
+            __syncthreads();
+            const int yz = 16 * ty + lr;
+            int off = 0;
+            if (yz < ncol) {
+                int y, z;
+                tri_decode(yz, M, y, z);
+                off = y * M + z;
+            }
+            int cur_nt = -1;
+            double cf[KS];
+            for (int tile = wave; tile < ntn * M; tile += NW) {
+                const int nt = tile / M, x = tile - nt * M;
+                if (nt != cur_nt) {
+                    const int n = 16 * nt + lr;
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        const int pp = 4 * ks + lq;
+                        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
+                            csrd, (pp < N && n < N) ? (unsigned)((pp * N + n) * (int)sizeof(double)) : 0x7fffffffu,
+                            0, 0);
+                        cf[ks] = __builtin_bit_cast(double, v);
+                    }
+                    cur_nt = nt;
+                }
+                double tf[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) tf[ks] = T3s[(size_t)(4 * ks + lq) * LDP + x * 16 + lr];
+                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(cf[ks], tf[ks], acc);
+                const int ci = yz < ncol ? tab[x * M2 + off] : -1;
+                if (ci >= 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int n = 16 * nt + lq + 4 * j;
+                        if (n < N) Gc[(size_t)n * NC + ci] = acc[j];
+                    }
+                }
+            }
+            if (ty + 1 < nty) load_half(bf, ty + 1, 0);
+            __syncthreads();
+        }
+    }
+
+    // ---- stage 3 (cas_panel_kernel with one panel of all N general indices) -----------------------
+#define TAIL_G(n, a, b, c) Gc[(size_t)(n) * NC + tab[((a) * M + (b)) * M + (c)]]
+    for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
+        const int n = idx / M, x = idx - n * M;
+        double fi = hn[idx];
+        for (int i = 0; i < no; ++i) fi += 2.0 * TAIL_G(n, x, i, i) - TAIL_G(n, i, i, x);
+        FIn[idx] = fi;
+    }
+    double* Fl = scr;                                // [nrdm][M][N]  Fock columns
+    double* El = Fl + (size_t)nrdm * M * N;          // [nrdm][N]     Epart
+    double* Ga = El + (size_t)nrdm * N;              // [N][na3]      g_mo[n, no + w, no + x, no + y]
+    double* Dc = Ga + (size_t)N * na3;               // [N][no][na2]  g_mo[n, m, V, W] - 0.5 g_mo[n, W, V, m]
+    // the operands of the Fock columns and energy parts gathered once (dense, no table lookup in their sums)
+    for (int idx = tid; idx < N * na3; idx += TAIL_THREADS) {
+        const int n = idx / na3, r = idx - n * na3;
+        const int w = r / na2, x = (r / na) % na, y = r % na;
+        Ga[idx] = TAIL_G(n, no + w, no + x, no + y);
+    }
+    for (int idx = tid; idx < N * no * na2; idx += TAIL_THREADS) {
+        const int n = idx / (no * na2), r = idx - n * (no * na2);
+        const int m = r / na2, v = (r / na) % na, w = r % na;
+        const int V = no + v, W = no + w;
+        Dc[idx] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
+    }
+    __syncthreads();
+    for (int n = tid; n < N; n += TAIL_THREADS) Cp[n] = n < no ? hn[n * M + n] + FIn[n * M + n] : 0.0;
+    for (int idx = tid; idx < na * (na + na3); idx += TAIL_THREADS) {
+        const int pl = idx / (na + na3), r0 = idx - pl * (na + na3);
+        const int n = no + pl;
+        if (r0 < na) {
+            c1[pl * na + r0] = FIn[n * M + no + r0];
+        } else {
+            int t = r0 - na;
+            const int i3 = t;
+            const int s = t % na; t /= na;
+            const int r = t % na; t /= na;
+            const int q = t;
+            c2[(size_t)pl * na3 + i3] = 0.5 * TAIL_G(n, no + q, no + r, no + s);
+        }
+    }
+    // Fock columns: one thread per (n, set k, row m), the core rows first (waves without divergent rows)
+    const int ncore = N * nrdm * no;
+    for (int idx = tid; idx < N * nrdm * M; idx += TAIL_THREADS) {
+        int n, k, m;
+        if (idx < ncore) {
+            n = idx / (nrdm * no);
+            const int r0 = idx - n * (nrdm * no);
+            k = r0 / no;
+            m = r0 - k * no;
+        } else {
+            const int j = idx - ncore;
+            n = j / (nrdm * na);
+            const int r0 = j - n * (nrdm * na);
+            k = r0 / na;
+            m = no + r0 - k * na;
+        }
+        const double* FIv = FIn + (size_t)n * M;
+        const double* gam = gml + (size_t)k * na2;
+        double val;
+        if (m < no) {
+            const double* Dm = Dc + ((size_t)n * no + m) * na2;
+            double fa = 0.0;
+            for (int v = 0; v < na; ++v)
+                for (int w = 0; w < na; ++w) fa += gam[v * na + w] * Dm[v * na + w];
+            val = 2.0 * ((k == 0 ? FIv[m] : 0.0) + fa);
+        } else {
+            const int v = m - no;
+            const double* Gv = Gml + (size_t)k * na4 + (size_t)v * na3;
+            double acc = 0.0;
+            for (int w = 0; w < na; ++w) acc += FIv[no + w] * gam[v * na + w];
+            for (int w = 0; w < na; ++w)
+                for (int x = 0; x < na; ++x)
+                    for (int y = 0; y < na; ++y)
+                        acc += Gv[(w * na + x) * na + y] * Ga[(size_t)n * na3 + (w * na + x) * na + y];
+            val = acc;
+        }
+        Fl[((size_t)k * M + m) * N + n] = val;
+    }
+    // E_k contribution of row p = n - no (active n only), serial per (n, set)
+    for (int idx = tid; idx < N * nrdm; idx += TAIL_THREADS) {
+        const int n = idx / nrdm, k = idx - n * nrdm;
+        double acc = 0.0;
+        if (n >= no && n < M) {
+            const int p = n - no;
+            const double* FIv = FIn + (size_t)n * M;
+            const double* gam = gml + (size_t)k * na2 + (size_t)p * na;
+            const double* Gpq = Gml + (size_t)k * na4 + (size_t)p * na3;
+            for (int q = 0; q < na; ++q) acc += FIv[no + q] * gam[q];
+            for (int q = 0; q < na; ++q)
+                for (int r = 0; r < na; ++r)
+                    for (int s2 = 0; s2 < na; ++s2)
+                        acc += 0.5 * Ga[(size_t)n * na3 + (q * na + r) * na + s2] * Gpq[(q * na + r) * na + s2];
+        }
+        El[(size_t)k * N + n] = acc;
+    }
+#undef TAIL_G
+    __syncthreads();
+
+    // ---- assembly (cas_final_kernel) ----------------------------------------------------------------
+    for (int idx = tid; idx < nrdm * n_kappa; idx += TAIL_THREADS) {
+        const int k = idx / n_kappa, t = idx - k * n_kappa;
+        const int r = krow[t], c = kcol[t];
+        const double* F = Fl + (size_t)k * M * N;
+        const double frc = F[(size_t)(r < M ? r : 0) * N + c] * (r < M ? 1.0 : 0.0);
+        const double fcr = F[(size_t)(c < M ? c : 0) * N + r] * (c < M ? 1.0 : 0.0);
+        gvec[idx] = 2.0 * (frc - fcr);
+    }
+    if (tid < nrdm) {
+        const int k = tid;
+        double acc = 0.0;
+        for (int n = 0; n < M; ++n) acc += El[(size_t)k * N + n];
+        if (k == 0) {
+            double core = nuc;
+            for (int n = 0; n < M; ++n) core += Cp[n];
+            c0[0] = core;
+            E[0] = core + acc;
+        } else if (dE) {
+            dE[k - 1] = acc;
+        }
+    }
+}
+
 }  // namespace
 
 static int half_transform_batched(const double* g_ao, const double* C, int N, int M, double* T2,
@@ -3547,6 +3904,64 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
 #undef OOVQE_LAUNCH_GM
 #undef OOVQE_LAUNCH_GM2
     OOVQE_CHECK_LAUNCH("cas_eval/sym_gm");
+    return 0;
+}
+
+// cas_tail_kernel: kept entries of g_mo[n] (NC) and LDS bytes for one workgroup per geometry (0: it does not fit)
+static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* NC)
+{
+    const int M = no + na, M3 = M * M * M;
+    if (N > 48 || M > 16) return 0;
+    int nc = 0;
+    for (int x = 0; x < M; ++x)
+        for (int y = 0; y < M; ++y)
+            for (int z = y; z < M; ++z) nc += tail_needed(x, y, z, no) ? 1 : 0;
+    *NC = nc;
+    const int ksteps = (N + 3) / 4, KSr = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : 12;
+    const size_t na2 = (size_t)na * na, na4 = na2 * na2;
+    size_t scr = (size_t)N * N;                                           // W
+    const size_t t3 = (size_t)4 * KSr * (M * 16 + 8);                     // T3s
+    const size_t fe = (size_t)nrdm * M * N + (size_t)nrdm * N +           // Fcol + Epart + Ga + Dc
+                      (size_t)N * na * na * na + (size_t)N * no * na2;
+    if (t3 > scr) scr = t3;
+    if (fe > scr) scr = fe;
+    const size_t doubles = (size_t)N * nc + 3 * (size_t)N * M + (size_t)nrdm * (na2 + na4) + N +
+                           ((size_t)M3 + TAIL_THREADS / 64 + 2 * (size_t)n_kappa + 1) / 2 + scr;
+    const size_t bytes = doubles * sizeof(double);
+    return bytes <= 160 * 1024 ? bytes : 0;
+}
+
+// the tail of the packed-triangle path in one launch, one workgroup per geometry (cas_tail_kernel)
+static int cas_tail_batched(const double* J, const double* C, const double* Wpre, const double* gamma,
+                            const double* Gamma, int nrdm, double nuc, const double* nuc_arr, int N, int n_occ,
+                            int ncas, const int32_t* kap_row, const int32_t* kap_col, int n_kappa, double* c0,
+                            double* c1, double* c2, double* E, double* gvec, double* dE, int batch,
+                            size_t out_stride, hipStream_t st)
+{
+    int NC = 0;
+    const size_t lds_bytes = tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &NC);
+    OOVQE_REQUIRE(lds_bytes > 0, "cas_eval/tail: N=%d M=%d nrdm=%d does not fit", N, n_occ + ncas, nrdm);
+    const int ksteps = (N + 3) / 4;
+#define OOVQE_LAUNCH_TAIL(KS_)                                                                    \
+    do {                                                                                          \
+        static size_t attr_bytes = 0;                                                             \
+        if (lds_bytes > attr_bytes) {                                                             \
+            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)cas_tail_kernel<KS_>,                \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                                                (int)lds_bytes), "cas_eval/tail");                \
+            attr_bytes = lds_bytes;                                                               \
+        }                                                                                         \
+        hipLaunchKernelGGL((cas_tail_kernel<KS_>), dim3(batch), dim3(TAIL_THREADS), lds_bytes, st, J, C, Wpre, \
+                           gamma, Gamma, nrdm, N, n_occ, ncas, NC, nuc, nuc_arr, kap_row, kap_col, n_kappa, c0, \
+                           E, gvec, dE, c1, c2, out_stride);                                      \
+    } while (0)
+    oovqe_profile_mark_start_l(st, 2);
+    if (ksteps <= 4) OOVQE_LAUNCH_TAIL(4);
+    else if (ksteps <= 8) OOVQE_LAUNCH_TAIL(8);
+    else OOVQE_LAUNCH_TAIL(12);
+    oovqe_profile_mark_stop(st);
+#undef OOVQE_LAUNCH_TAIL
+    OOVQE_CHECK_LAUNCH("cas_eval/tail");
     return 0;
 }
 
@@ -4091,6 +4506,23 @@ static int cas_eval_batched(const double* g_ao, const double* h_ao, const double
             } else if ((rc = half_tri_batched(use_pk ? g_packed : g_ao, C, N, M, Jp, batch, st,
                                               two_step ? 0 : rs_sym ? 2 : 1, use_pk)))
                 return rc;
+        }
+        // the whole tail in one launch of one workgroup per geometry (cas_tail_kernel) when the batch fills at
+        // least half the chip with it, the circuit has run in its own launch (RDMs and W = C^T h in memory) and
+        // nothing beyond the packed outputs is asked for; otherwise sym_gm, panel and final launches
+        int tail_nc = 0;
+        const bool tail = !two_step && rs_sym && g_packed != nullptr && !T2_ready && !cj && w_ready && !fock && !gmat && !Gm && !hmo &&
+                          2L * batch > (long)device_cu_count() && tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &tail_nc) > 0 &&
+                          oovqe_opt(OOVQE_OPT_TAIL_SPLIT) == 0;
+        if (tail) {
+            double* wchk = nullptr;
+            OOVQE_REQUIRE(cas_w_block(N, M, batch, eri_flags, work, &wchk) && wchk == T3,
+                          "cas_eval: W = C^T h was promised for another path");
+            if ((rc = cas_tail_batched(Jp, C, T3, gamma, Gamma, nrdm, nuc, nuc_arr, N, n_occ, ncas, kap_row, kap_col,
+                                       n_kappa, c0, c1, c2, E, gvec, dE, batch, out_stride, st)))
+                return rc;
+            if (rdm_event) OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");
+            return 0;
         }
         if (!two_step) {
             if ((rc = sym_gm_batched(Jp, C, Gmw, N, M, batch, st, cj, rs_sym))) return rc;

@@ -55,6 +55,7 @@ enum oovqe_option_t {
     OOVQE_OPT_PANEL_NO_W,            // cas_panel_kernel always stages h_ao and forms its rows of C^T h itself (no W from the circuit launch)
     OOVQE_OPT_STAGE1_FREE_RUN,       // 1: N^4 sweeps enqueued on different streams are not ordered one after the other
     OOVQE_OPT_ONE_STREAM,            // 1: every launch of a call on the caller's stream (no chain of a call on the library's internal streams)
+    OOVQE_OPT_TAIL_SPLIT,            // 1: packed-triangle path: the three-launch tail (sym_gm, panel, final) instead of cas_tail_kernel
     OOVQE_OPT_COUNT
 };
 int oovqe_opt(int id);
