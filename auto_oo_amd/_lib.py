@@ -210,6 +210,13 @@ SIGNATURES = {
                                 + [ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int]
                                 + [c_double_p] * 4 + [c_int32_p, c_double_p, c_stream]),
     "oovqe_circuit_rdms_is_small": (ctypes.c_int, [ctypes.c_int] * 4),
+    "oovqe_gto_work_size": (ctypes.c_int64, [ctypes.c_int] * 3),
+    "oovqe_gto_integrals_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                                 ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int]
+                                  + [c_double_p] * 5 + [c_stream]),
+    "oovqe_sym_invsqrt_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_int32_p,
+                                               c_stream]),
+    "oovqe_boys": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_int64, c_double_p, c_stream]),
     "oovqe_spin_rdms": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                        c_double_p, c_stream]),
     "oovqe_debug_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),

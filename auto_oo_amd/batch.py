@@ -16,12 +16,15 @@ geometry by geometry.
 """
 import ctypes
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _lib, excitations as X, ops
+from . import _lib, excitations as X, gto as GTO, ops
 from ._lib import check, dptr, stream_ptr
+from .gaussian import rhf
+from .moldata import Moldata
 from .oo_energy import mo_ao_to_mo_oao, non_redundant_indices
 
 F64 = torch.float64
@@ -37,34 +40,12 @@ class OO_pqc_batch:
             oao_mo_coeffs: sequence of [N,N] OAO->MO coefficients (default: from mol.hf.mo_coeff)
             freeze_active: freeze active-active rotations (oo_energy.py:139-140)
         """
-        self.lib = _lib.load()
-        self.device = _lib.require_device()
-        self.pqc = pqc
-        self.G = len(mols)
-        if self.G < 1:
+        if len(mols) < 1:
             raise ValueError("need at least one geometry")
-        self.nao = mols[0].nao
-        self.ncas, self.nelecas = ncas, nelecas
         for m in mols:
-            if m.nao != self.nao or m.nelectron != mols[0].nelectron:
+            if m.nao != mols[0].nao or m.nelectron != mols[0].nelectron:
                 raise ValueError("all geometries of a batch must share nao and the electron count")
-        self.occ_idx, self.act_idx, self.virt_idx = mols[0].get_active_space_idx(ncas, nelecas)
-        self._n_occ = len(self.occ_idx)
-        self.params_idx = non_redundant_indices(self.occ_idx, self.act_idx, self.virt_idx,
-                                                freeze_active)
-        self.n_kappa = len(self.params_idx)
-        rows, cols = X.tril_tables(self.nao, self.params_idx)
-        self._kap_row = torch.as_tensor(rows).to(self.device)
-        self._kap_col = torch.as_tensor(cols).to(self.device)
-        self.n_theta = int(np.prod(pqc.theta_shape))
-
-        N = self.nao
-        self.int2e_ao = torch.empty((self.G, N, N, N, N), dtype=F64, device=self.device)
-        self.int1e_ao = torch.empty((self.G, N, N), dtype=F64, device=self.device)
-        self.oao_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
-        self.oao_mo_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
-        self.mo_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
-        self.nuc = torch.empty(self.G, dtype=F64, device=self.device)
+        self._allocate(pqc, len(mols), mols[0].nao, mols[0].nelectron, ncas, nelecas, freeze_active)
         nuc_host = np.empty(self.G)
         for g, m in enumerate(mols):
             self.int2e_ao[g].copy_(ops.as_device(m.int2e_ao, self.device))
@@ -82,14 +63,120 @@ class OO_pqc_batch:
         # bit for bit per geometry, and the packed resident copy the batched N^4 pass streams: ONE pass over the
         # stack (oovqe_eri_ingest).  The batch runs on the flags ALL its geometries share.  int2e_ao must
         # not be modified in place afterwards (set_molecule / reverify_integrals are the ways in).
-        self._eri_packed = None
         self._ingest()
+
+    def _allocate(self, pqc, G, nao, nelectron, ncas, nelecas, freeze_active):
+        """Tables and (uninitialised) per-geometry tensors of a batch of G geometries."""
+        self.lib = _lib.load()
+        self.device = _lib.require_device()
+        self.pqc = pqc
+        self.G = int(G)
+        if self.G < 1:
+            raise ValueError("need at least one geometry")
+        self.nao = int(nao)
+        self.ncas, self.nelecas = ncas, nelecas
+        self.occ_idx, self.act_idx, self.virt_idx = Moldata.get_active_space_idx(
+            SimpleNamespace(nelectron=int(nelectron), nao=self.nao), ncas, nelecas)
+        self._n_occ = len(self.occ_idx)
+        self.params_idx = non_redundant_indices(self.occ_idx, self.act_idx, self.virt_idx,
+                                                freeze_active)
+        self.n_kappa = len(self.params_idx)
+        rows, cols = X.tril_tables(self.nao, self.params_idx)
+        self._kap_row = torch.as_tensor(rows).to(self.device)
+        self._kap_col = torch.as_tensor(cols).to(self.device)
+        self.n_theta = int(np.prod(pqc.theta_shape))
+
+        N = self.nao
+        self.int2e_ao = torch.empty((self.G, N, N, N, N), dtype=F64, device=self.device)
+        self.int1e_ao = torch.empty((self.G, N, N), dtype=F64, device=self.device)
+        self.oao_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
+        self.oao_mo_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
+        self.mo_coeff = torch.empty((self.G, N, N), dtype=F64, device=self.device)
+        self.nuc = torch.empty(self.G, dtype=F64, device=self.device)
+        self._eri_packed = None
         self._plans = {}
         self._flat0 = None
         self._trial_orbitals = None
         self._step_args = None
         self._all_pd_last_step = False
         self.step_by_calls = False
+        self.basis = None
+
+    # ---- integrals made on the device (auto_oo_amd/gto.py) ----------------------------------------------------------
+    @classmethod
+    def from_geometries(cls, pqc, basis, coords, ncas, nelecas, oao_mo_coeffs=None, freeze_active=False):
+        """A batch whose AO integrals are computed on the device (``gto.integrals_batch``) instead of being copied
+        from host-built molecules.
+
+        Args:
+            pqc: Parameterized_circuit shared by all geometries
+            basis: gto.GTOBasis of the molecule
+            coords: [G, natm, 3] in Angstrom, or a list of geometries as ``Moldata_sto3g`` takes them
+            ncas, nelecas: active space
+            oao_mo_coeffs: [G][N, N] OAO->MO coefficients.  Default: RHF orbitals of every geometry from the host
+                ``gaussian.rhf`` on the (small) integrals copied back once -- the only host copy on this path
+        """
+        self = cls.__new__(cls)
+        xyz = GTO.coords_to_device(basis, coords)
+        self._allocate(pqc, int(xyz.shape[0]), basis.nao, basis.nelectron, ncas, nelecas, freeze_active)
+        self.basis = basis
+        self._write_integrals(xyz, None)
+        if oao_mo_coeffs is None:
+            S, h, g = self.overlap.cpu().numpy(), self.int1e_ao.cpu().numpy(), self.int2e_ao.cpu().numpy()
+            oao_mo_coeffs = [mo_ao_to_mo_oao(rhf(h[k], g[k], S[k], basis.nelectron // 2)[0], S[k])
+                             for k in range(self.G)]
+        for g_, c in enumerate(oao_mo_coeffs):
+            self.oao_mo_coeff[g_].copy_(ops.as_device(c, self.device))
+        self._ingest()
+        self.refresh_mo_coeff()
+        return self
+
+    def _write_integrals(self, xyz_bohr, index):
+        """Integrals, S^-1/2 and nuclear repulsion of the geometries ``xyz_bohr`` (device, Bohr) into the rows ``index``
+        of the stack (None: all rows), written in place by the integral kernels: runs of consecutive rows take one
+        call each."""
+        if getattr(self, "overlap", None) is None:
+            self.overlap = torch.empty((self.G, self.nao, self.nao), dtype=F64, device=self.device)
+        rows = list(range(self.G)) if index is None else [int(i) for i in index]
+        if len(rows) != int(xyz_bohr.shape[0]):
+            raise ValueError(f"{int(xyz_bohr.shape[0])} geometries for {len(rows)} rows")
+        if any(not 0 <= r < self.G for r in rows) or len(set(rows)) != len(rows):
+            raise ValueError(f"index must hold distinct rows in 0..{self.G - 1}")
+        infos = []
+        k = 0
+        while k < len(rows):
+            e = k + 1
+            while e < len(rows) and rows[e] == rows[e - 1] + 1:
+                e += 1
+            a, b = rows[k], rows[e - 1] + 1
+            GTO.integrals_into(self.basis, xyz_bohr[k:e], self.overlap[a:b], self.int1e_ao[a:b], self.int2e_ao[a:b],
+                               self.nuc[a:b])
+            infos.append(GTO.sym_invsqrt_batch(self.overlap[a:b], out=self.oao_coeff[a:b])[1])
+            k = e
+        GTO.raise_if_dependent(torch.cat(infos), rows)
+
+    def set_geometries(self, coords, index=None, oao_mo_coeffs=None):
+        """Move the batch (or its rows ``index``) to new geometries: ``int2e_ao``, ``int1e_ao``, ``oao_coeff`` and
+        ``nuc`` are computed in place on the device, then the symmetry flags / packed copy are re-made (``_ingest``)
+        and ``mo_coeff = S^-1/2 C_oao`` refreshed.  ``oao_mo_coeffs=None`` keeps the current orbitals (the tracking
+        regime of a Berry-phase loop); otherwise one [N, N] matrix per new geometry.  No integral tensor passes through
+        the host."""
+        if self.basis is None:
+            raise RuntimeError("set_geometries needs a batch made by OO_pqc_batch.from_geometries")
+        xyz = GTO.coords_to_device(self.basis, coords, self.device)
+        rows = None if index is None else [int(i) for i in np.atleast_1d(index)]
+        self._write_integrals(xyz, rows)
+        if oao_mo_coeffs is not None:
+            targets = range(self.G) if rows is None else rows
+            if len(oao_mo_coeffs) != len(targets):
+                raise ValueError("one orbital matrix per new geometry")
+            for g_, c in zip(targets, oao_mo_coeffs):
+                self.oao_mo_coeff[g_].copy_(ops.as_device(c, self.device))
+        if rows is not None and len(rows) == 1:
+            self._ingest(rows[0])
+        else:
+            self._ingest()
+        self.refresh_mo_coeff()
 
     def set_oao_mo_coeff(self, g, oao_mo_coeff):
         """Replace the orbitals of geometry g and refresh mo_coeff[g] = S^-1/2 C_oao

@@ -1,0 +1,871 @@
+// Batched Gaussian integrals over a stack of geometries (gfx950): contracted Cartesian s and p shells,
+// McMurchie-Davidson.  One basis description (shell table, exponents, normalised contraction coefficients,
+// charges) is shared by all geometries; the geometry index is a grid dimension of every kernel.
+//
+//   gto_setup_kernel   AO offset of every shell and the shell pairs i >= j sorted into classes (la >= lb: ss, ps, pp)
+//   gto_pair_kernel    per geometry and primitive pair: p, P, c_a c_b exp(-mu |AB|^2), 1/(2p), a/p, b/p
+//                      (8 doubles, in the work buffer) and the nuclear repulsion of the geometry.  The Hermite
+//                      coefficients E_t^{ij} per dimension are polynomials in (P - A, P - B, 1/2p) times the
+//                      exponential kept here: the consumers rebuild them in registers from these 8 doubles
+//                      (a table of all E_t^{ij} would be 29 doubles per primitive pair read 81 times per quartet).
+//   gto_one_kernel     <la, lb>: S, T, V of one shell pair per group of GTO_SPLIT lanes, all components together
+//   gto_eri_kernel     <la, lb, lc, ld>: one unique shell quartet per group of GTO_SPLIT lanes (the primitive pairs of
+//                      the bra dealt out over the lanes), all components together: Boys values and R_tuv once per
+//                      primitive quartet; every unique value goes to its (up to 8) places from one register
+//   sym_invsqrt_kernel S^-1/2 by cyclic Jacobi (round-robin ordering), one wave per matrix, matrix and vectors in LDS
+//
+// l is a template parameter everywhere; GTO_LMAX = 1 limits what is instantiated (and the component tables
+// gto_ncomp / gto_pow are written for l <= 1).  Every per-thread array is indexed by compile-time constants
+// (static_for / fully unrolled loops of constant trip count), so none of them lives in scratch.
+#include "common.h"
+#include <math.h>
+#include <utility>
+#include <vector>
+
+#define GTO_LMAX 1
+#define GTO_NCLS ((GTO_LMAX + 1) * (GTO_LMAX + 2) / 2)
+#define GTO_PW 8                 // doubles per primitive pair
+#define GTO_NT 64                // threads per workgroup of the integral kernels (one wave)
+#define GTO_SPLIT 8              // lanes that share one shell pair / quartet: each takes every 8th primitive pair of the
+                                 // bra, the partial sums are added by a butterfly (fixed order: the same bits whatever
+                                 // the batch).  A thread's chain of 81 primitive quartets is what a call waits for.
+#define GTO_BOYS_SWITCH 5.0      // T below: series for F_L and downward recursion; above: erf and upward recursion
+#define GTO_BOYS_TERMS 36        // terms of the series (last term below 1e-17 of the sum for T < 5, n >= 0)
+#define GTO_PI 3.14159265358979323846
+#define INVSQRT_NT 64
+
+template <class F, int... I>
+__host__ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __host__ __device__ __forceinline__ void static_for(F&& f)
+{
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// sum over the SPLIT adjacent lanes of a group; every lane of the group receives the same bits
+template <int SPLIT> __host__ __device__ __forceinline__ double gto_group_sum(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int o = 1; o < SPLIT; o <<= 1) x += __shfl_xor(x, o, 64);
+#endif
+    return x;
+}
+
+__host__ __device__ constexpr int gto_ncomp(int l) { return l == 0 ? 1 : 3; }
+// power of coordinate d in Cartesian component c of a shell of angular momentum l (s; px, py, pz)
+__host__ __device__ constexpr int gto_pow(int l, int c, int d) { return (l == 1 && c == d) ? 1 : 0; }
+__host__ __device__ constexpr int gto_cls(int la, int lb) { return la * (la + 1) / 2 + lb; }
+
+// ---- Boys function -------------------------------------------------------------------------------------------
+// F_n(T) = int_0^1 t^2n exp(-T t^2) dt, n = 0 .. L.
+// T < 5: F_L = exp(-T) sum_k (2T)^k / ((2L+1)(2L+3)...(2L+2k+1)) (all terms positive), then downwards
+// F_{n-1} = (2T F_n + exp(-T)) / (2n - 1) (a sum of positive terms).  T >= 5: F_0 = sqrt(pi/T) erf(sqrt T) / 2, then
+// upwards F_{n+1} = ((2n+1) F_n - exp(-T)) / (2T): for T >= 5 and n <= 4 the subtraction loses less than a bit per
+// step.  Against 40-digit arithmetic this scheme in fp64 is within 6.4e-16 relative for n <= 4 on [0, 2000].
+template <int L> __host__ __device__ __forceinline__ void gto_boys(double T, double (&F)[L + 1])
+{
+    const double et = exp(-T);
+    if (T < GTO_BOYS_SWITCH) {
+        const double T2 = 2.0 * T;
+        double s = 0.0;
+#pragma unroll
+        for (int k = GTO_BOYS_TERMS; k > 0; --k) s = (s + 1.0) * T2 * (1.0 / (double)(2 * L + 2 * k + 1));
+        F[L] = et * (s + 1.0) * (1.0 / (double)(2 * L + 1));
+#pragma unroll
+        for (int n = L; n > 0; --n) F[n - 1] = (T2 * F[n] + et) * (1.0 / (double)(2 * n - 1));
+    } else {
+        const double st = sqrt(T);
+        F[0] = 0.88622692545275801365 / st * erf(st);        // sqrt(pi) / 2
+        const double o2t = 0.5 / T;
+#pragma unroll
+        for (int n = 0; n < L; ++n) F[n + 1] = ((double)(2 * n + 1) * F[n] - et) * o2t;
+    }
+}
+
+// ---- Hermite expansion coefficients of one dimension, without the exponential factor --------------------------
+// E[i][j][t] = E_t^{ij} / E_0^{00}, i <= LA, j <= LB: E^{i+1,j}_t = E^{ij}_{t-1} / 2p + XPA E^{ij}_t + (t+1) E^{ij}_{t+1}
+template <int LA, int LB>
+__host__ __device__ __forceinline__ void gto_herm(double (&E)[LA + 1][LB + 1][LA + LB + 1], double xpa, double xpb, double oo2p)
+{
+#pragma unroll
+    for (int i = 0; i <= LA; ++i) {
+#pragma unroll
+        for (int j = 0; j <= LB; ++j) {
+#pragma unroll
+            for (int t = 0; t <= LA + LB; ++t) {
+                double v = 0.0;
+                if (i == 0 && j == 0) {
+                    v = (t == 0) ? 1.0 : 0.0;
+                } else if (t <= i + j) {
+                    const int top = i + j - 1;             // highest t of the parent
+                    if (j == 0) {
+                        if (t >= 1) v += oo2p * E[i > 0 ? i - 1 : 0][0][t > 0 ? t - 1 : 0];
+                        if (t <= top) v += xpa * E[i > 0 ? i - 1 : 0][0][t];
+                        if (t + 1 <= top) v += (double)(t + 1) * E[i > 0 ? i - 1 : 0][0][t + 1 <= LA + LB ? t + 1 : 0];
+                    } else {
+                        if (t >= 1) v += oo2p * E[i][j > 0 ? j - 1 : 0][t > 0 ? t - 1 : 0];
+                        if (t <= top) v += xpb * E[i][j > 0 ? j - 1 : 0][t];
+                        if (t + 1 <= top) v += (double)(t + 1) * E[i][j > 0 ? j - 1 : 0][t + 1 <= LA + LB ? t + 1 : 0];
+                    }
+                }
+                E[i][j][t] = v;
+            }
+        }
+    }
+}
+
+// ---- Hermite Coulomb integrals R^n_tuv from Fs[n] = (-2 alpha)^n F_n(T) (times any common factor) -----------
+template <int T, int U, int V, int N, int NF>
+__host__ __device__ __forceinline__ double gto_R(const double (&Fs)[NF], double X, double Y, double Z)
+{
+    if constexpr (T < 0 || U < 0 || V < 0) {
+        return 0.0;
+    } else if constexpr (T == 0 && U == 0 && V == 0) {
+        return Fs[N];
+    } else if constexpr (T == 0 && U == 0) {
+        double v = Z * gto_R<0, 0, V - 1, N + 1>(Fs, X, Y, Z);
+        if constexpr (V > 1) v += (double)(V - 1) * gto_R<0, 0, V - 2, N + 1>(Fs, X, Y, Z);
+        return v;
+    } else if constexpr (T == 0) {
+        double v = Y * gto_R<0, U - 1, V, N + 1>(Fs, X, Y, Z);
+        if constexpr (U > 1) v += (double)(U - 1) * gto_R<0, U - 2, V, N + 1>(Fs, X, Y, Z);
+        return v;
+    } else {
+        double v = X * gto_R<T - 1, U, V, N + 1>(Fs, X, Y, Z);
+        if constexpr (T > 1) v += (double)(T - 1) * gto_R<T - 2, U, V, N + 1>(Fs, X, Y, Z);
+        return v;
+    }
+}
+
+template <int L>
+__host__ __device__ __forceinline__ void gto_R_fill(double (&R)[L + 1][L + 1][L + 1], const double (&Fs)[L + 1], double X,
+                                           double Y, double Z)
+{
+    static_for<L + 1>([&](auto tc) {
+        static_for<L + 1>([&](auto uc) {
+            static_for<L + 1>([&](auto vc) {
+                constexpr int t = decltype(tc)::value, u = decltype(uc)::value, v = decltype(vc)::value;
+                if constexpr (t + u + v <= L) R[t][u][v] = gto_R<t, u, v, 0>(Fs, X, Y, Z);
+            });
+        });
+    });
+}
+
+// ---- work buffer ------------------------------------------------------------------------------------------------
+// int32 part: ao_off[nshell] | lists[GTO_NCLS][npair][2] (shell of higher l, shell of lower l), padded to 16 bytes;
+// then pair data [batch][npair][kp][GTO_PW], pair index i (i + 1) / 2 + j (i >= j), slot ka * nprim_j + kb.
+__host__ __device__ inline long gto_int_doubles(int nshell)
+{
+    const long npair = (long)nshell * (nshell + 1) / 2;
+    const long ints = nshell + (long)GTO_NCLS * npair * 2;
+    return ((ints + 1) / 2 + 1) & ~1L;
+}
+
+__host__ __device__ inline void gto_setup_body(const int* __restrict__ shells, int nshell, int* __restrict__ iw)
+{
+    const int npair = nshell * (nshell + 1) / 2;
+    int off = 0;
+    for (int s = 0; s < nshell; ++s) {
+        iw[s] = off;
+        off += gto_ncomp(shells[4 * s + 1]);
+    }
+    int cnt[GTO_NCLS];
+#pragma unroll
+    for (int c = 0; c < GTO_NCLS; ++c) cnt[c] = 0;
+    int* lists = iw + nshell;
+    for (int i = 0; i < nshell; ++i) {
+        for (int j = 0; j <= i; ++j) {
+            const int li = shells[4 * i + 1], lj = shells[4 * j + 1];
+            const int hi = (li >= lj) ? i : j, lo = (li >= lj) ? j : i;
+            const int cls = gto_cls(li >= lj ? li : lj, li >= lj ? lj : li);
+#pragma unroll
+            for (int c = 0; c < GTO_NCLS; ++c) {          // (static index into cnt)
+                if (c == cls) {
+                    lists[((long)c * npair + cnt[c]) * 2 + 0] = hi;
+                    lists[((long)c * npair + cnt[c]) * 2 + 1] = lo;
+                    cnt[c] += 1;
+                }
+            }
+        }
+    }
+}
+
+__global__ void gto_setup_kernel(const int* __restrict__ shells, int nshell, int* __restrict__ iw)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) gto_setup_body(shells, nshell, iw);
+}
+
+__host__ __device__ __forceinline__ void gto_pair_body(long tid, const int* __restrict__ shells, int nshell,
+                                                       const double* __restrict__ exps,
+                                                       const double* __restrict__ coefs,
+                                                       const double* __restrict__ charges, int natm,
+                                                       const double* __restrict__ coords, int batch, int kp,
+                                                       double* __restrict__ pairs, double* __restrict__ nuc)
+{
+    const long npair = (long)nshell * (nshell + 1) / 2;
+    const long per = npair * kp;
+    if (tid >= per * batch) return;
+    const int g = (int)(tid / per);
+    const long r = tid - (long)g * per;
+    const int pidx = (int)(r / kp), k = (int)(r - (long)pidx * kp);
+    const double* xyz = coords + (size_t)g * natm * 3;
+    if (r == 0 && nuc) {
+        // the order of the host sum (gaussian.Moldata_sto3g): i ascending, j < i ascending
+        double e = 0.0;
+        for (int i = 0; i < natm; ++i) {
+            for (int j = 0; j < i; ++j) {
+                const double dx = xyz[3 * i] - xyz[3 * j], dy = xyz[3 * i + 1] - xyz[3 * j + 1],
+                             dz = xyz[3 * i + 2] - xyz[3 * j + 2];
+                e += charges[i] * charges[j] / sqrt(dx * dx + dy * dy + dz * dz);
+            }
+        }
+        nuc[g] = e;
+    }
+    int i = (int)((sqrt(8.0 * (double)pidx + 1.0) - 1.0) * 0.5);
+    while ((long)(i + 1) * (i + 2) / 2 <= pidx) ++i;
+    while ((long)i * (i + 1) / 2 > pidx) --i;
+    const int j = pidx - i * (i + 1) / 2;
+    const int ni = shells[4 * i + 2], nj = shells[4 * j + 2];
+    if (k >= ni * nj) return;
+    const int ka = k / nj, kb = k - ka * nj;
+    const double a = exps[shells[4 * i + 3] + ka], b = exps[shells[4 * j + 3] + kb];
+    const double ca = coefs[shells[4 * i + 3] + ka], cb = coefs[shells[4 * j + 3] + kb];
+    const double* A = xyz + 3 * shells[4 * i];
+    const double* B = xyz + 3 * shells[4 * j];
+    const double p = a + b, mu = a * b / p;
+    const double qx = A[0] - B[0], qy = A[1] - B[1], qz = A[2] - B[2];
+    double* o = pairs + ((size_t)g * npair + pidx) * kp * GTO_PW + (size_t)k * GTO_PW;
+    d2* o2 = reinterpret_cast<d2*>(o);
+    d2 v;
+    v.x = p; v.y = (a * A[0] + b * B[0]) / p; o2[0] = v;
+    v.x = (a * A[1] + b * B[1]) / p; v.y = (a * A[2] + b * B[2]) / p; o2[1] = v;
+    v.x = ca * cb * exp(-mu * (qx * qx + qy * qy + qz * qz)); v.y = 0.5 / p; o2[2] = v;
+    v.x = a / p; v.y = b / p; o2[3] = v;
+}
+
+__global__ __launch_bounds__(256) void gto_pair_kernel(const int* __restrict__ shells, int nshell,
+                                                       const double* __restrict__ exps,
+                                                       const double* __restrict__ coefs,
+                                                       const double* __restrict__ charges, int natm,
+                                                       const double* __restrict__ coords, int batch, int kp,
+                                                       double* __restrict__ pairs, double* __restrict__ nuc)
+{
+    gto_pair_body((long)blockIdx.x * blockDim.x + threadIdx.x, shells, nshell, exps, coefs, charges, natm, coords,
+                  batch, kp, pairs, nuc);
+}
+
+// what a consumer keeps of one primitive pair, oriented to ITS order of the two shells (first = higher l)
+struct gto_prim_t {
+    double p, P[3], cck, oo2p, fa, fb;     // fa = (exponent of the first shell) / p, fb = (second) / p
+};
+__host__ __device__ __forceinline__ gto_prim_t gto_load_prim(const double* e, bool swapped)
+{
+    const d2* e2 = reinterpret_cast<const d2*>(e);
+    const d2 v0 = e2[0], v1 = e2[1], v2 = e2[2], v3 = e2[3];
+    gto_prim_t q;
+    q.p = v0.x; q.P[0] = v0.y; q.P[1] = v1.x; q.P[2] = v1.y; q.cck = v2.x; q.oo2p = v2.y;
+    q.fa = swapped ? v3.y : v3.x;
+    q.fb = swapped ? v3.x : v3.y;
+    return q;
+}
+
+struct gto_pair_ref_t {
+    int sa, sb;                 // shells (l of sa >= l of sb)
+    int oa, ob;                 // their AO offsets
+    int nprim;                  // primitive pairs
+    bool swapped;               // sa < sb: the stored orientation is (sb, sa)
+    double AB[3];               // A - B
+    const double* data;
+};
+__host__ __device__ __forceinline__ gto_pair_ref_t gto_pair_ref(const int* lists, int cls, int k, long npair, const int* iw,
+                                                       const int* shells, const double* xyz, const double* pairs_g,
+                                                       int kp)
+{
+    gto_pair_ref_t r;
+    r.sa = lists[((long)cls * npair + k) * 2];
+    r.sb = lists[((long)cls * npair + k) * 2 + 1];
+    r.oa = iw[r.sa];
+    r.ob = iw[r.sb];
+    r.nprim = shells[4 * r.sa + 2] * shells[4 * r.sb + 2];
+    r.swapped = r.sa < r.sb;
+    const int hi = r.swapped ? r.sb : r.sa, lo = r.swapped ? r.sa : r.sb;
+    r.data = pairs_g + ((size_t)hi * (hi + 1) / 2 + lo) * kp * GTO_PW;
+    const double* A = xyz + 3 * shells[4 * r.sa];
+    const double* B = xyz + 3 * shells[4 * r.sb];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) r.AB[d] = A[d] - B[d];
+    return r;
+}
+
+// ---- one-electron integrals ---------------------------------------------------------------------------------------
+// (the bodies of the integral kernels are __host__ __device__ functions of the thread index: a CPU build of this file
+// can run them in a loop under a host debugger or sanitizer)
+template <int LA, int LB, int SPLIT>
+__host__ __device__ __forceinline__ void gto_one_body(long tid, const int* __restrict__ iw,
+                                                      const int* __restrict__ shells, int nshell, int count,
+                                                      const double* __restrict__ charges, int natm,
+                                                      const double* __restrict__ coords, int batch,
+                                                      const double* __restrict__ pairs, int kp, int nao,
+                                                      double* __restrict__ overlap, double* __restrict__ h_ao)
+{
+    constexpr int NA = gto_ncomp(LA), NB = gto_ncomp(LB), L = LA + LB;
+    const int sub = (int)(tid % SPLIT);
+    tid /= SPLIT;
+    if (tid >= (long)count * batch) return;
+    const int g = (int)(tid / count), k = (int)(tid - (long)g * count);
+    const long npair = (long)nshell * (nshell + 1) / 2;
+    const double* xyz = coords + (size_t)g * natm * 3;
+    const gto_pair_ref_t ab = gto_pair_ref(iw + nshell, gto_cls(LA, LB), k, npair, iw, shells, xyz,
+                                           pairs + (size_t)g * npair * kp * GTO_PW, kp);
+    double accS[NA * NB], accT[NA * NB], accV[NA * NB];
+#pragma unroll
+    for (int c = 0; c < NA * NB; ++c) { accS[c] = 0.0; accT[c] = 0.0; accV[c] = 0.0; }
+    for (int kab = sub; kab < ab.nprim; kab += SPLIT) {
+        const gto_prim_t pr = gto_load_prim(ab.data + (size_t)kab * GTO_PW, ab.swapped);
+        double E[3][LA + 1][LB + 3][LA + LB + 3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) gto_herm<LA, LB + 2>(E[d], -pr.fb * ab.AB[d], pr.fa * ab.AB[d], pr.oo2p);
+        const double b = pr.fb * pr.p;
+        const double pop = GTO_PI / pr.p;
+        const double fS = pr.cck * pop * sqrt(pop);
+        static_for<NA>([&](auto cac) {
+            static_for<NB>([&](auto cbc) {
+                constexpr int ca = decltype(cac)::value, cb = decltype(cbc)::value;
+                double s1[3], t1[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const int i = gto_pow(LA, ca, d), j = gto_pow(LB, cb, d);
+                    s1[d] = E[d][i][j][0];
+                    double td = -2.0 * b * b * E[d][i][j + 2][0] + b * (double)(2 * j + 1) * s1[d];
+                    if (j >= 2) td -= 0.5 * (double)(j * (j - 1)) * E[d][i][j >= 2 ? j - 2 : 0][0];
+                    t1[d] = td;
+                }
+                accS[ca * NB + cb] += fS * (s1[0] * s1[1] * s1[2]);
+                accT[ca * NB + cb] += fS * (t1[0] * s1[1] * s1[2] + s1[0] * t1[1] * s1[2] + s1[0] * s1[1] * t1[2]);
+            });
+        });
+        if (h_ao) {
+            const double fV = -2.0 * GTO_PI / pr.p * pr.cck;
+            for (int c = 0; c < natm; ++c) {
+                const double X = pr.P[0] - xyz[3 * c], Y = pr.P[1] - xyz[3 * c + 1], Z = pr.P[2] - xyz[3 * c + 2];
+                double F[L + 1], Fs[L + 1], R[L + 1][L + 1][L + 1];
+                gto_boys<L>(pr.p * (X * X + Y * Y + Z * Z), F);
+                double sc = fV * charges[c];
+#pragma unroll
+                for (int n = 0; n <= L; ++n) { Fs[n] = sc * F[n]; sc *= -2.0 * pr.p; }
+                gto_R_fill<L>(R, Fs, X, Y, Z);
+                static_for<NA>([&](auto cac) {
+                    static_for<NB>([&](auto cbc) {
+                        constexpr int ca = decltype(cac)::value, cb = decltype(cbc)::value;
+                        constexpr int ix = gto_pow(LA, ca, 0), jx = gto_pow(LB, cb, 0), iy = gto_pow(LA, ca, 1),
+                                      jy = gto_pow(LB, cb, 1), iz = gto_pow(LA, ca, 2), jz = gto_pow(LB, cb, 2);
+                        double v = 0.0;
+#pragma unroll
+                        for (int t = 0; t <= ix + jx; ++t)
+#pragma unroll
+                            for (int u = 0; u <= iy + jy; ++u)
+#pragma unroll
+                                for (int w = 0; w <= iz + jz; ++w)
+                                    v += E[0][ix][jx][t] * E[1][iy][jy][u] * E[2][iz][jz][w] * R[t][u][w];
+                        accV[ca * NB + cb] += v;
+                    });
+                });
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NA * NB; ++c) {
+        accS[c] = gto_group_sum<SPLIT>(accS[c]);
+        accT[c] = gto_group_sum<SPLIT>(accT[c]);
+        accV[c] = gto_group_sum<SPLIT>(accV[c]);
+    }
+    const bool same = ab.sa == ab.sb;
+    static_for<NA>([&](auto cac) {
+        static_for<NB>([&](auto cbc) {
+            constexpr int ca = decltype(cac)::value, cb = decltype(cbc)::value;
+            const int mu = ab.oa + ca, nu = ab.ob + cb;
+            if ((ca * NB + cb) % SPLIT == sub && (!same || mu >= nu) && mu < nao && nu < nao) {
+                if (overlap) {
+                    const double s = accS[ca * NB + cb];
+                    overlap[((size_t)g * nao + mu) * nao + nu] = s;
+                    overlap[((size_t)g * nao + nu) * nao + mu] = s;
+                }
+                if (h_ao) {
+                    const double h = accT[ca * NB + cb] + accV[ca * NB + cb];
+                    h_ao[((size_t)g * nao + mu) * nao + nu] = h;
+                    h_ao[((size_t)g * nao + nu) * nao + mu] = h;
+                }
+            }
+        });
+    });
+}
+
+template <int LA, int LB>
+__global__ __launch_bounds__(GTO_NT) void gto_one_kernel(const int* __restrict__ iw, const int* __restrict__ shells,
+                                                         int nshell, int count, const double* __restrict__ charges,
+                                                         int natm, const double* __restrict__ coords, int batch,
+                                                         const double* __restrict__ pairs, int kp, int nao,
+                                                         double* __restrict__ overlap, double* __restrict__ h_ao)
+{
+    gto_one_body<LA, LB, GTO_SPLIT>((long)blockIdx.x * GTO_NT + threadIdx.x, iw, shells, nshell, count, charges, natm, coords,
+                         batch, pairs, kp, nao, overlap, h_ao);
+}
+
+// ---- two-electron integrals ---------------------------------------------------------------------------------------
+template <int LA, int LB, int LC, int LD, int SPLIT>
+__host__ __device__ __forceinline__ void gto_eri_body(long tid, const int* __restrict__ iw,
+                                                      const int* __restrict__ shells, int nshell, int nbra, int nket,
+                                                      long nquart, const double* __restrict__ coords, int natm,
+                                                      int batch, const double* __restrict__ pairs, int kp, int nao,
+                                                      double* __restrict__ g_ao)
+{
+    constexpr int NA = gto_ncomp(LA), NB = gto_ncomp(LB), NC = gto_ncomp(LC), ND = gto_ncomp(LD);
+    constexpr int L = LA + LB + LC + LD;
+    constexpr bool same_cls = (LA == LC && LB == LD);
+    const int sub = (int)(tid % SPLIT);
+    tid /= SPLIT;
+    if (tid >= nquart * batch) return;
+    const int g = (int)(tid / nquart);
+    const long r = tid - (long)g * nquart;
+    int k1, k2;
+    if (same_cls) {              // unique pairs of pairs k1 >= k2
+        k1 = (int)((sqrt(8.0 * (double)r + 1.0) - 1.0) * 0.5);
+        while ((long)(k1 + 1) * (k1 + 2) / 2 <= r) ++k1;
+        while ((long)k1 * (k1 + 1) / 2 > r) --k1;
+        k2 = (int)(r - (long)k1 * (k1 + 1) / 2);
+    } else {
+        k1 = (int)(r / nket);
+        k2 = (int)(r - (long)k1 * nket);
+    }
+    if (k1 >= nbra || k2 >= nket) return;
+    const long npair = (long)nshell * (nshell + 1) / 2;
+    const double* xyz = coords + (size_t)g * natm * 3;
+    const double* pairs_g = pairs + (size_t)g * npair * kp * GTO_PW;
+    const gto_pair_ref_t ab = gto_pair_ref(iw + nshell, gto_cls(LA, LB), k1, npair, iw, shells, xyz, pairs_g, kp);
+    const gto_pair_ref_t cd = gto_pair_ref(iw + nshell, gto_cls(LC, LD), k2, npair, iw, shells, xyz, pairs_g, kp);
+
+    double acc[NA * NB * NC * ND];
+#pragma unroll
+    for (int c = 0; c < NA * NB * NC * ND; ++c) acc[c] = 0.0;
+    for (int kab = sub; kab < ab.nprim; kab += SPLIT) {
+        const gto_prim_t pb = gto_load_prim(ab.data + (size_t)kab * GTO_PW, ab.swapped);
+        double Eb[3][LA + 1][LB + 1][LA + LB + 1];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) gto_herm<LA, LB>(Eb[d], -pb.fb * ab.AB[d], pb.fa * ab.AB[d], pb.oo2p);
+        for (int kcd = 0; kcd < cd.nprim; ++kcd) {
+            const gto_prim_t pk = gto_load_prim(cd.data + (size_t)kcd * GTO_PW, cd.swapped);
+            double Ek[3][LC + 1][LD + 1][LC + LD + 1];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) gto_herm<LC, LD>(Ek[d], -pk.fb * cd.AB[d], pk.fa * cd.AB[d], pk.oo2p);
+            const double s = pb.p + pk.p, alpha = pb.p * pk.p / s;
+            const double X = pb.P[0] - pk.P[0], Y = pb.P[1] - pk.P[1], Z = pb.P[2] - pk.P[2];
+            double F[L + 1], Fs[L + 1], R[L + 1][L + 1][L + 1];
+            gto_boys<L>(alpha * (X * X + Y * Y + Z * Z), F);
+            // 2 pi^(5/2) / (p q sqrt(p + q)) and the two pair factors
+            double sc = 34.98683665524972497 / (pb.p * pk.p * sqrt(s)) * (pb.cck * pk.cck);
+#pragma unroll
+            for (int n = 0; n <= L; ++n) { Fs[n] = sc * F[n]; sc *= -2.0 * alpha; }
+            gto_R_fill<L>(R, Fs, X, Y, Z);
+            // ket side first: X_tuv = sum_t'u'v' (-1)^(t'+u'+v') E^cd_t'u'v' R_(t+t', u+u', v+v') of one ket component,
+            // then every bra component takes its few E^ab_tuv X_tuv
+            static_for<NC * ND>([&](auto ccdc) {
+                constexpr int ccd = decltype(ccdc)::value, cc = ccd / ND, cd_ = ccd % ND;
+                constexpr int kx = gto_pow(LC, cc, 0), lx = gto_pow(LD, cd_, 0), ky = gto_pow(LC, cc, 1),
+                              ly = gto_pow(LD, cd_, 1), kz = gto_pow(LC, cc, 2), lz = gto_pow(LD, cd_, 2);
+                constexpr int LAB = LA + LB;
+                double Xh[LAB + 1][LAB + 1][LAB + 1];
+                static_for<(LAB + 1) * (LAB + 1) * (LAB + 1)>([&](auto tuvc) {
+                    constexpr int tuv = decltype(tuvc)::value, t = tuv / ((LAB + 1) * (LAB + 1)),
+                                  u = (tuv / (LAB + 1)) % (LAB + 1), w = tuv % (LAB + 1);
+                    if constexpr (t + u + w <= LAB) {
+                        double x = 0.0;
+#pragma unroll
+                        for (int t2 = 0; t2 <= kx + lx; ++t2)
+#pragma unroll
+                            for (int u2 = 0; u2 <= ky + ly; ++u2)
+#pragma unroll
+                                for (int w2 = 0; w2 <= kz + lz; ++w2) {
+                                    const double ek = Ek[0][kx][lx][t2] * Ek[1][ky][ly][u2] * Ek[2][kz][lz][w2];
+                                    const double sg = ((t2 + u2 + w2) & 1) ? -1.0 : 1.0;
+                                    x += sg * ek * R[t + t2][u + u2][w + w2];
+                                }
+                        Xh[t][u][w] = x;
+                    }
+                });
+                static_for<NA * NB>([&](auto cabc) {
+                    constexpr int cab = decltype(cabc)::value, ca = cab / NB, cb = cab % NB;
+                    constexpr int ix = gto_pow(LA, ca, 0), jx = gto_pow(LB, cb, 0), iy = gto_pow(LA, ca, 1),
+                                  jy = gto_pow(LB, cb, 1), iz = gto_pow(LA, ca, 2), jz = gto_pow(LB, cb, 2);
+                    double v = 0.0;
+#pragma unroll
+                    for (int t = 0; t <= ix + jx; ++t)
+#pragma unroll
+                        for (int u = 0; u <= iy + jy; ++u)
+#pragma unroll
+                            for (int w = 0; w <= iz + jz; ++w)
+                                v += Eb[0][ix][jx][t] * Eb[1][iy][jy][u] * Eb[2][iz][jz][w] * Xh[t][u][w];
+                    acc[cab * (NC * ND) + ccd] += v;
+                });
+            });
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NA * NB * NC * ND; ++c) acc[c] = gto_group_sum<SPLIT>(acc[c]);
+    // (after the butterfly every lane of the group holds every value: lane `sub` stores every SPLIT-th component)
+    // every unique value to its (up to 8) places, from one register; a value two components of this thread both
+    // stand for (same shell twice in a pair, same pair twice in the quartet) is stored by one of them only
+    const bool same_ab = ab.sa == ab.sb, same_cd = cd.sa == cd.sb;
+    const bool same_pair = same_cls && ab.sa == cd.sa && ab.sb == cd.sb;
+    double* out = g_ao + (size_t)g * nao * nao * nao * nao;
+    const size_t n1 = (size_t)nao, n2 = n1 * n1, n3 = n2 * n1;
+    static_for<NA * NB>([&](auto cabc) {
+        constexpr int cab = decltype(cabc)::value, ca = cab / NB, cb = cab % NB;
+        static_for<NC * ND>([&](auto ccdc) {
+            constexpr int ccd = decltype(ccdc)::value, cc = ccd / ND, cd_ = ccd % ND;
+            const size_t mu = ab.oa + ca, nu = ab.ob + cb, la = cd.oa + cc, si = cd.ob + cd_;
+            const size_t m1 = mu > nu ? mu : nu, m0 = mu > nu ? nu : mu, l1 = la > si ? la : si,
+                         l0 = la > si ? si : la;
+            bool keep = m1 < n1 && l1 < n1 && (cab * (NC * ND) + ccd) % SPLIT == sub;
+            if (same_ab && mu < nu) keep = false;
+            if (same_cd && la < si) keep = false;
+            if (same_pair && m1 * (m1 + 1) / 2 + m0 < l1 * (l1 + 1) / 2 + l0) keep = false;
+            if (keep) {
+                const double x = acc[cab * (NC * ND) + ccd];
+                out[mu * n3 + nu * n2 + la * n1 + si] = x;
+                out[nu * n3 + mu * n2 + la * n1 + si] = x;
+                out[mu * n3 + nu * n2 + si * n1 + la] = x;
+                out[nu * n3 + mu * n2 + si * n1 + la] = x;
+                out[la * n3 + si * n2 + mu * n1 + nu] = x;
+                out[si * n3 + la * n2 + mu * n1 + nu] = x;
+                out[la * n3 + si * n2 + nu * n1 + mu] = x;
+                out[si * n3 + la * n2 + nu * n1 + mu] = x;
+            }
+        });
+    });
+}
+
+template <int LA, int LB, int LC, int LD>
+__global__ __launch_bounds__(GTO_NT) void gto_eri_kernel(const int* __restrict__ iw, const int* __restrict__ shells,
+                                                         int nshell, int nbra, int nket, long nquart,
+                                                         const double* __restrict__ coords, int natm, int batch,
+                                                         const double* __restrict__ pairs, int kp, int nao,
+                                                         double* __restrict__ g_ao)
+{
+    gto_eri_body<LA, LB, LC, LD, GTO_SPLIT>((long)blockIdx.x * GTO_NT + threadIdx.x, iw, shells, nshell, nbra, nket, nquart,
+                                 coords, natm, batch, pairs, kp, nao, g_ao);
+}
+
+// ---- Boys function on its own (the accuracy test) ----------------------------------------------------------------
+template <int L>
+__global__ void gto_boys_kernel(const double* __restrict__ T, long count, double* __restrict__ F)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    double f[L + 1];
+    gto_boys<L>(T[i], f);
+#pragma unroll
+    for (int n = 0; n <= L; ++n) F[i * (L + 1) + n] = f[n];
+}
+
+// ---- S^-1/2 -------------------------------------------------------------------------------------------------------
+// One wave per matrix: cyclic Jacobi on A in the parallel (round-robin) ordering -- the rotations of the n / 2 disjoint
+// pairs of a round are computed by n / 2 lanes at once and applied in two passes; with one rotation at a time (the
+// order of ci_jacobi) the chain of divisions and square roots of 78 rotations per sweep took 0.27 ms at n = 13 --
+// then X = U diag(w^-1/2) U^T, each element of the lower triangle once, stored to both places.
+// LDS: A and U, leading dimension n | 1, and the (cos, sin) and index pairs of a round.
+// pair k of round r of the round-robin schedule over n2 (even) indices: index n2 - 1 stays, the others rotate
+__device__ __forceinline__ void invsqrt_pair(int k, int r, int n2, int& p, int& q)
+{
+    const int a = (k == 0) ? r : (r + k) % (n2 - 1), b = (k == 0) ? n2 - 1 : (r - k + n2 - 1) % (n2 - 1);
+    p = a < b ? a : b;
+    q = a < b ? b : a;
+}
+
+__global__ __launch_bounds__(INVSQRT_NT) void sym_invsqrt_kernel(const double* __restrict__ S, int n, double min_eig,
+                                                                 double* __restrict__ Xout, int* __restrict__ info)
+{
+    extern __shared__ double lds[];
+    const int ld = n | 1;
+    double* A = lds;
+    double* U = lds + (size_t)n * ld;
+    double* cs = U + (size_t)n * ld;                // (cos, sin) of the rotations of a round
+    int* pq = reinterpret_cast<int*>(cs + INVSQRT_NT);   // and their index pairs
+    const int n2 = n + (n & 1), m = n2 / 2;
+    const int lane = threadIdx.x, g = blockIdx.x;
+    const double* Sg = S + (size_t)g * n * n;
+    double* Xg = Xout + (size_t)g * n * n;
+    for (int k = lane; k < n * n; k += INVSQRT_NT) {
+        const int r = k / n, c = k - r * n;
+        // (the upper triangle is taken from the lower one: the iteration works on an exactly symmetric matrix)
+        A[r * ld + c] = (r >= c) ? Sg[r * n + c] : Sg[c * n + r];
+        U[r * ld + c] = (r == c) ? 1.0 : 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, dg = 0.0;
+        if (lane < n) {
+            for (int c = 0; c < n; ++c) {
+                const double x = fabs(A[lane * ld + c]);
+                if (c == lane) dg = fmax(dg, x); else off = fmax(off, x);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            off = fmax(off, __shfl_xor(off, o, 64));
+            dg = fmax(dg, __shfl_xor(dg, o, 64));
+        }
+        if (!(off > 1e-15 * fmax(dg, 1e-300))) break;      // (also leaves on NaN)
+        // one sweep = n2 - 1 rounds of the round-robin schedule: the n2 / 2 pairs of a round are disjoint, so their
+        // rotations J commute; A <- J^T A J as a column pass (lane = row) and a row pass (lane = column)
+        for (int r = 0; r < n2 - 1; ++r) {
+            int p = 0, q = n;
+            double c = 1.0, s = 0.0;
+            if (lane < m) {
+                invsqrt_pair(lane, r, n2, p, q);
+                if (q < n) {
+                    const double apq = A[p * ld + q];
+                    if (fabs(apq) > 1e-300) {
+                        const double tau = (A[q * ld + q] - A[p * ld + p]) / (2.0 * apq);
+                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                        c = 1.0 / sqrt(1.0 + t * t);
+                        s = t * c;
+                    }
+                }
+                cs[2 * lane] = c;
+                cs[2 * lane + 1] = (q < n) ? s : 0.0;
+                pq[2 * lane] = p;
+                pq[2 * lane + 1] = (q < n) ? q : p;           // (an idle pair has s = 0 and is skipped)
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            // the pairs of a round are disjoint: four at a time, all loads of a group before its stores (the compiler
+            // cannot know that the stores of one pair leave the loads of the next alone; one pair at a time was a
+            // chain of LDS round trips)
+            if (lane < n) {
+                for (int k0 = 0; k0 < m; k0 += 4) {
+                    double ap[4], aq[4], up[4], uq[4], ck[4], sk[4];
+                    int pk[4], qk[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = (k0 + j < m) ? k0 + j : 0;
+                        pk[j] = pq[2 * k]; qk[j] = pq[2 * k + 1];
+                        ck[j] = cs[2 * k]; sk[j] = (k0 + j < m) ? cs[2 * k + 1] : 0.0;
+                        ap[j] = A[lane * ld + pk[j]]; aq[j] = A[lane * ld + qk[j]];
+                        up[j] = U[lane * ld + pk[j]]; uq[j] = U[lane * ld + qk[j]];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (sk[j] != 0.0) {
+                            A[lane * ld + pk[j]] = ck[j] * ap[j] - sk[j] * aq[j];
+                            A[lane * ld + qk[j]] = sk[j] * ap[j] + ck[j] * aq[j];
+                            U[lane * ld + pk[j]] = ck[j] * up[j] - sk[j] * uq[j];
+                            U[lane * ld + qk[j]] = sk[j] * up[j] + ck[j] * uq[j];
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (lane < n) {
+                for (int k0 = 0; k0 < m; k0 += 4) {
+                    double ap[4], aq[4], ck[4], sk[4];
+                    int pk[4], qk[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = (k0 + j < m) ? k0 + j : 0;
+                        pk[j] = pq[2 * k]; qk[j] = pq[2 * k + 1];
+                        ck[j] = cs[2 * k]; sk[j] = (k0 + j < m) ? cs[2 * k + 1] : 0.0;
+                        ap[j] = A[pk[j] * ld + lane]; aq[j] = A[qk[j] * ld + lane];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (sk[j] != 0.0) {
+                            A[pk[j] * ld + lane] = ck[j] * ap[j] - sk[j] * aq[j];
+                            A[qk[j] * ld + lane] = sk[j] * ap[j] + ck[j] * aq[j];
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (lane < m && q < n && s != 0.0) {
+                A[p * ld + q] = 0.0;               // (annihilated up to rounding: made exact)
+                A[q * ld + p] = 0.0;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        }
+    }
+    double w = INFINITY;
+    bool bad = false;
+    if (lane < n) { w = A[lane * ld + lane]; bad = !(w >= min_eig); }     // (NaN is bad)
+    const bool any_bad = __any(bad);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (lane < n) A[lane * ld + lane] = any_bad ? 0.0 : 1.0 / sqrt(w);     // the diagonal now holds w^-1/2
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (lane == 0) info[g] = any_bad ? -1 : 0;
+    if (lane < n) {
+        for (int c = 0; c <= lane; ++c) {
+            double x = 0.0;
+            for (int k = 0; k < n; ++k) x += U[lane * ld + k] * A[k * ld + k] * U[c * ld + k];
+            if (any_bad) x = __builtin_nan("");
+            Xg[lane * n + c] = x;
+            Xg[c * n + lane] = x;
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+static int gto_check_sizes(const char* who, int nshell, int max_nprim, int batch)
+{
+    OOVQE_REQUIRE(nshell >= 1 && nshell <= OOVQE_GTO_MAX_SHELL, "%s: nshell = %d (1 .. %d)", who, nshell,
+                  OOVQE_GTO_MAX_SHELL);
+    OOVQE_REQUIRE(max_nprim >= 1 && max_nprim <= OOVQE_GTO_MAX_PRIM, "%s: %d primitives per shell (1 .. %d)", who,
+                  max_nprim, OOVQE_GTO_MAX_PRIM);
+    OOVQE_REQUIRE(batch >= 0, "%s: batch = %d", who, batch);
+    return 0;
+}
+
+extern "C" int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch)
+{
+    if (gto_check_sizes("oovqe_gto_work_size", nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
+    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
+    return gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
+}
+
+namespace {
+struct gto_launch_t {
+    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
+    const double* coords; int batch; const double* pairs; int kp; int nao; double* overlap; double* h_ao;
+    double* g_ao; hipStream_t st;
+};
+
+template <int LA, int LB> int gto_launch_one(const gto_launch_t& a)
+{
+    const int count = a.cnt[gto_cls(LA, LB)];
+    if (count == 0) return 0;
+    const long total = (long)count * a.batch * GTO_SPLIT;
+    hipLaunchKernelGGL((gto_one_kernel<LA, LB>), dim3((unsigned)((total + GTO_NT - 1) / GTO_NT)), dim3(GTO_NT), 0,
+                       a.st, a.iw, a.shells, a.nshell, count, a.charges, a.natm, a.coords, a.batch, a.pairs, a.kp,
+                       a.nao, a.overlap, a.h_ao);
+    OOVQE_CHECK_LAUNCH("gto_one_kernel");
+    return 0;
+}
+
+template <int LA, int LB, int LC, int LD> int gto_launch_eri(const gto_launch_t& a)
+{
+    const int nbra = a.cnt[gto_cls(LA, LB)], nket = a.cnt[gto_cls(LC, LD)];
+    const bool same = (LA == LC && LB == LD);
+    const long nq = same ? (long)nbra * (nbra + 1) / 2 : (long)nbra * nket;
+    if (nq == 0) return 0;
+    const long blocks = (nq * a.batch * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
+    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_integrals_batch: %ld workgroups in one launch", blocks);
+    hipLaunchKernelGGL((gto_eri_kernel<LA, LB, LC, LD>), dim3((unsigned)blocks), dim3(GTO_NT), 0, a.st, a.iw,
+                       a.shells, a.nshell, nbra, nket, nq, a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao, a.g_ao);
+    OOVQE_CHECK_LAUNCH("gto_eri_kernel");
+    return 0;
+}
+}  // namespace
+
+extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                         const double* coefs, int natm, const double* charges, int batch,
+                                         const double* coords, int nao, double* overlap, double* h_ao, double* g_ao,
+                                         double* nuc, double* work, oovqe_stream_t stream)
+{
+    const char* who = "oovqe_gto_integrals_batch";
+    OOVQE_REQUIRE(nshell >= 1 && nshell <= OOVQE_GTO_MAX_SHELL, "%s: nshell = %d (1 .. %d)", who, nshell,
+                  OOVQE_GTO_MAX_SHELL);
+    OOVQE_REQUIRE(batch >= 0 && natm >= 1 && nprim_total >= 1, "%s: batch = %d, natm = %d, nprim_total = %d", who,
+                  batch, natm, nprim_total);
+    if (batch == 0) return 0;
+    OOVQE_REQUIRE(shells && exps && coefs && charges && coords && work, "%s: null pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    // the shell table is read back once per call (16 bytes per shell): the limits below are enforced here, with a
+    // return code, and the launches are sized from it
+    std::vector<int32_t> tab((size_t)nshell * 4);
+    OOVQE_CHECK_HIP(hipMemcpyAsync(tab.data(), shells, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st), who);
+    OOVQE_CHECK_HIP(hipStreamSynchronize(st), who);
+    int cnt[GTO_NCLS] = {0}, ao = 0, kp = 0;
+    for (int s = 0; s < nshell; ++s) {
+        const int atom = tab[4 * s], l = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
+        OOVQE_REQUIRE(l >= 0 && l <= OOVQE_GTO_MAX_L, "%s: shell %d has l = %d (s and p shells only, l <= %d)", who,
+                      s, l, OOVQE_GTO_MAX_L);
+        OOVQE_REQUIRE(np >= 1 && np <= OOVQE_GTO_MAX_PRIM, "%s: shell %d has %d primitives (1 .. %d)", who, s, np,
+                      OOVQE_GTO_MAX_PRIM);
+        OOVQE_REQUIRE(atom >= 0 && atom < natm, "%s: shell %d sits on atom %d of %d", who, s, atom, natm);
+        OOVQE_REQUIRE(off >= 0 && off + np <= nprim_total, "%s: shell %d reads primitives %d .. %d of %d", who, s,
+                      off, off + np - 1, nprim_total);
+        ao += gto_ncomp(l);
+        kp = np > kp ? np : kp;
+    }
+    OOVQE_REQUIRE(ao == nao, "%s: the shell table has %d functions, nao = %d", who, ao, nao);
+    for (int i = 0; i < nshell; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const int li = tab[4 * i + 1], lj = tab[4 * j + 1];
+            cnt[gto_cls(li >= lj ? li : lj, li >= lj ? lj : li)] += 1;
+        }
+    kp *= kp;
+    const long npair = (long)nshell * (nshell + 1) / 2;
+    int* iw = reinterpret_cast<int*>(work);
+    double* pairs = work + gto_int_doubles(nshell);
+    hipLaunchKernelGGL(gto_setup_kernel, dim3(1), dim3(64), 0, st, shells, nshell, iw);
+    OOVQE_CHECK_LAUNCH("gto_setup_kernel");
+    const long pt = npair * kp * batch;
+    OOVQE_REQUIRE((pt + 255) / 256 < (1L << 31), "%s: %ld primitive pairs", who, pt);
+    hipLaunchKernelGGL(gto_pair_kernel, dim3((unsigned)((pt + 255) / 256)), dim3(256), 0, st, shells, nshell, exps,
+                       coefs, charges, natm, coords, batch, kp, pairs, nuc);
+    OOVQE_CHECK_LAUNCH("gto_pair_kernel");
+    const gto_launch_t a = {iw, shells, nshell, cnt, charges, natm, coords, batch, pairs, kp, nao, overlap, h_ao,
+                            g_ao, st};
+    int rc = 0;
+    if (overlap || h_ao) {
+        if ((rc = gto_launch_one<0, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_one<1, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_one<1, 1>(a)) != 0) return rc;
+    }
+    if (g_ao) {
+        // bra class >= ket class; the most numerous (and cheapest) classes last, behind the long threads of (pp|pp)
+        if ((rc = gto_launch_eri<1, 1, 1, 1>(a)) != 0) return rc;
+        if ((rc = gto_launch_eri<1, 1, 1, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_eri<1, 1, 0, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_eri<1, 0, 1, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_eri<1, 0, 0, 0>(a)) != 0) return rc;
+        if ((rc = gto_launch_eri<0, 0, 0, 0>(a)) != 0) return rc;
+    }
+    return 0;
+}
+
+extern "C" int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* info,
+                                       oovqe_stream_t stream)
+{
+    const char* who = "oovqe_sym_invsqrt_batch";
+    OOVQE_REQUIRE(n >= 1 && n <= OOVQE_INVSQRT_MAX_N, "%s: n = %d (1 .. %d)", who, n, OOVQE_INVSQRT_MAX_N);
+    OOVQE_REQUIRE(batch >= 0, "%s: batch = %d", who, batch);
+    if (batch == 0) return 0;
+    OOVQE_REQUIRE(s && x && info, "%s: null pointer", who);
+    const size_t lds = (2 * (size_t)n * (n | 1) + 2 * INVSQRT_NT) * sizeof(double);
+    if (oovqe_ensure_dynamic_lds(reinterpret_cast<const void*>(&sym_invsqrt_kernel), lds) != 0) return OOVQE_ERR_HIP;
+    hipLaunchKernelGGL(sym_invsqrt_kernel, dim3(batch), dim3(INVSQRT_NT), lds, (hipStream_t)stream, s, n,
+                       (double)OOVQE_INVSQRT_MIN_EIG, x, info);
+    OOVQE_CHECK_LAUNCH("sym_invsqrt_kernel");
+    return 0;
+}
+
+extern "C" int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream)
+{
+    OOVQE_REQUIRE(nmax >= 0 && nmax <= 4 * OOVQE_GTO_MAX_L, "oovqe_boys: nmax = %d (0 .. %d)", nmax,
+                  4 * OOVQE_GTO_MAX_L);
+    OOVQE_REQUIRE(count >= 0, "oovqe_boys: count = %lld", (long long)count);
+    if (count == 0) return 0;
+    OOVQE_REQUIRE(t && f, "oovqe_boys: null pointer");
+    const dim3 grid((unsigned)((count + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    switch (nmax) {
+    case 0: hipLaunchKernelGGL(gto_boys_kernel<0>, grid, block, 0, st, t, (long)count, f); break;
+    case 1: hipLaunchKernelGGL(gto_boys_kernel<1>, grid, block, 0, st, t, (long)count, f); break;
+    case 2: hipLaunchKernelGGL(gto_boys_kernel<2>, grid, block, 0, st, t, (long)count, f); break;
+    case 3: hipLaunchKernelGGL(gto_boys_kernel<3>, grid, block, 0, st, t, (long)count, f); break;
+    default: hipLaunchKernelGGL(gto_boys_kernel<4>, grid, block, 0, st, t, (long)count, f); break;
+    }
+    OOVQE_CHECK_LAUNCH("gto_boys_kernel");
+    return 0;
+}

@@ -1,0 +1,245 @@
+"""AO integrals of a stack of geometries on the device (``oovqe_gto_integrals_batch``, csrc/gto.hip).
+
+``gaussian.py`` builds the integrals of ONE molecule with numpy loops on the host (0.7 s for formaldimine in
+STO-3G); a scan over the points of a Berry-phase loop spends its time there.  Here one basis description --
+``GTOBasis``: flat tables of contracted Cartesian s and p shells, built on the host once -- is shared by all
+geometries, and ``integrals_batch`` fills overlap, core Hamiltonian, ``S^-1/2``, nuclear repulsion and ``(pq|rs)``
+of G geometries on the device.  Conventions are those of ``gaussian.py`` (atoms in input order; per atom 1s, 2s,
+2px, 2py, 2pz; contracted functions normalised); coordinates are in Angstrom here (``gaussian.BOHR``) and in Bohr
+at the C ABI.  There is no host fallback: without the HIP library and a device these functions raise.
+"""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, dptr, stream_ptr
+from .gaussian import BOHR, _Shell, _STO3G, _STO3G_1S_COEF, _STO3G_2S_COEF, _STO3G_2P_COEF, zmatrix_to_cartesian
+
+F64 = torch.float64
+MAX_L = 1                      # OOVQE_GTO_MAX_L
+MAX_PRIM = 6                   # OOVQE_GTO_MAX_PRIM
+INVSQRT_MAX_N = 64             # OOVQE_INVSQRT_MAX_N
+INVSQRT_MIN_EIG = 1e-8         # OOVQE_INVSQRT_MIN_EIG
+
+_Z = {s: i + 1 for i, s in enumerate(
+    "H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar".split())}
+_L_OF = {"s": 0, "p": 1, "d": 2, "f": 3}
+
+
+def _sto3g_shells(symbol):
+    key = symbol.capitalize()
+    if key not in _STO3G:
+        raise ValueError(f"no STO-3G parameters for element {symbol!r} ({', '.join(_STO3G)} are built in)")
+    par = _STO3G[key]
+    shells = [(0, par["1s"], _STO3G_1S_COEF)]
+    if "2sp" in par:
+        shells += [(0, par["2sp"], _STO3G_2S_COEF), (1, par["2sp"], _STO3G_2P_COEF)]
+    return par["Z"], shells
+
+
+class GTOBasis:
+    """Flat shell tables of a molecule's basis, shared by every geometry of a stack.
+
+    Args:
+        symbols: element symbols, in the order of the atoms of every geometry
+        basis: ``"sto-3g"`` (the tables of ``gaussian.py``: H, C, N, O, F), or a dict
+            ``{element: [(l, exponents, coefficients), ...]}`` of s / p shells (``l`` = 0, 1 or ``"s"``, ``"p"``),
+            coefficients those of normalised primitives as basis-set tables list them
+
+    Host arrays: ``shells`` [nshell, 4] int32 (atom, l, number of primitives, offset), ``exps``, ``coefs``
+    (contraction coefficients of the NORMALISED contracted function, primitive norms included -- ``_Shell.coefs``
+    of ``gaussian.py``), ``charges`` [natm]; ``nao``, ``nelectron`` (neutral molecule), ``max_nprim``.
+    """
+
+    def __init__(self, symbols, basis="sto-3g"):
+        self.symbols = [str(s) for s in symbols]
+        if not self.symbols:
+            raise ValueError("GTOBasis needs at least one atom")
+        rows, exps, coefs, charges = [], [], [], []
+        for atom, sym in enumerate(self.symbols):
+            if isinstance(basis, str):
+                if basis.lower().replace("-", "") != "sto3g":
+                    raise ValueError("the only built-in basis is 'sto-3g'; pass any other s/p basis as a dict "
+                                     "{element: [(l, exponents, coefficients), ...]}")
+                z, shells = _sto3g_shells(sym)
+            else:
+                key = sym.capitalize()
+                if key not in basis:
+                    raise ValueError(f"the basis has no shells for element {sym!r}")
+                if key not in _Z:
+                    raise ValueError(f"unknown element {sym!r}")
+                z, shells = _Z[key], basis[key]
+            charges.append(float(z))
+            for l, ex, co in shells:
+                l = _L_OF.get(str(l).lower(), l)
+                if not isinstance(l, (int, np.integer)) or l < 0:
+                    raise ValueError(f"shell of {sym!r}: angular momentum {l!r}")
+                if l > MAX_L:
+                    raise ValueError(f"shell of {sym!r} has l = {l}: only s and p shells (l <= {MAX_L}) are "
+                                     "implemented")
+                ex = np.asarray(ex, dtype=np.float64).ravel()
+                co = np.asarray(co, dtype=np.float64).ravel()
+                if ex.size != co.size or not 1 <= ex.size <= MAX_PRIM:
+                    raise ValueError(f"shell of {sym!r}: {ex.size} exponents, {co.size} coefficients "
+                                     f"(1 .. {MAX_PRIM} primitives per shell)")
+                norm = _Shell(np.zeros(3), (int(l), 0, 0), ex, co)      # l <= 1: the same for px, py, pz
+                rows.append((atom, int(l), ex.size, len(exps)))
+                exps.extend(norm.exps.tolist())
+                coefs.extend(norm.coefs.tolist())
+        self.shells = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+        self.exps = np.asarray(exps, dtype=np.float64)
+        self.coefs = np.asarray(coefs, dtype=np.float64)
+        self.charges = np.asarray(charges, dtype=np.float64)
+        self.natm = len(self.symbols)
+        self.nshell = self.shells.shape[0]
+        self.nao = int(sum(2 * l + 1 for l in self.shells[:, 1]))
+        self.nelectron = int(round(self.charges.sum()))
+        self.max_nprim = int(self.shells[:, 2].max())
+        self._dev = {}
+        self._work = {}
+
+    # ---- geometry input ----------------------------------------------------------------------------------------
+    def coordinates(self, coords):
+        """``coords`` -> [G, natm, 3] float64 in Angstrom (host).  Accepts an array [G, natm, 3] (or [natm, 3]) or
+        a sequence of the geometries ``Moldata_sto3g`` takes: Z-matrix / Cartesian strings, or lists of
+        ``(symbol, (x, y, z))``.  The Z-matrix conversion runs on the host (microseconds per geometry)."""
+        if isinstance(coords, torch.Tensor):
+            coords = coords.detach().cpu().numpy()
+        if isinstance(coords, str) or (isinstance(coords, (list, tuple)) and coords
+                                       and isinstance(coords[0], (tuple, list)) and len(coords[0]) == 2
+                                       and isinstance(coords[0][0], str)):
+            coords = [coords]
+        if isinstance(coords, np.ndarray):
+            xyz = np.asarray(coords, dtype=np.float64)
+            if xyz.ndim == 2:
+                xyz = xyz[None]
+        else:
+            xyz = np.empty((len(coords), self.natm, 3))
+            for g, geo in enumerate(coords):
+                if isinstance(geo, str):
+                    sym, pos = zmatrix_to_cartesian(geo)
+                elif isinstance(geo, np.ndarray):
+                    sym, pos = self.symbols, np.asarray(geo, dtype=np.float64)
+                else:
+                    sym = [a[0] for a in geo]
+                    pos = np.array([a[1] for a in geo], dtype=np.float64)
+                if [s.capitalize() for s in sym] != [s.capitalize() for s in self.symbols]:
+                    raise ValueError(f"geometry {g} has atoms {sym}, the basis was built for {self.symbols}")
+                xyz[g] = pos
+        if xyz.ndim != 3 or xyz.shape[1:] != (self.natm, 3):
+            raise ValueError(f"coordinates of shape {xyz.shape}, expected [G, {self.natm}, 3]")
+        return np.ascontiguousarray(xyz)
+
+    # ---- device side -------------------------------------------------------------------------------------------
+    def device_tables(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = SimpleNamespace(
+                shells=torch.as_tensor(self.shells).contiguous().to(device),
+                exps=torch.as_tensor(self.exps).to(device), coefs=torch.as_tensor(self.coefs).to(device),
+                charges=torch.as_tensor(self.charges).to(device))
+        return self._dev[key]
+
+    def work(self, device, G):
+        """Work buffer for G geometries, one per (device, stream): calls on different streams never share one."""
+        key = (str(device), torch.cuda.current_stream().cuda_stream)
+        buf = self._work.get(key)
+        size = int(_lib.load().oovqe_gto_work_size(self.nshell, self.max_nprim, G))
+        if size < 0:
+            check(size, "oovqe_gto_work_size")
+        if buf is None or buf.numel() < size:
+            buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
+        return buf
+
+
+def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=None, nuc=None):
+    """The integrals of the geometries ``coords_bohr`` ([G, natm, 3] device tensor, Bohr) written into the given
+    contiguous device tensors ([G, N, N], [G, N, N], [G, N, N, N, N], [G]; None skips one), on the current stream."""
+    lib = _lib.load()
+    G = int(coords_bohr.shape[0])
+    dev = coords_bohr.device
+    t = basis.device_tables(dev)
+    N = basis.nao
+    for name, x, shape in (("overlap", overlap, (G, N, N)), ("int1e_ao", int1e_ao, (G, N, N)),
+                           ("int2e_ao", int2e_ao, (G, N, N, N, N)), ("nuc", nuc, (G,))):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {shape}")
+    work = basis.work(dev, G)
+    check(lib.oovqe_gto_integrals_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(coords_bohr), N, dptr(overlap), dptr(int1e_ao), dptr(int2e_ao), dptr(nuc),
+        dptr(work), stream_ptr()), "oovqe_gto_integrals_batch")
+
+
+def sym_invsqrt_batch(S, out=None):
+    """``S^-1/2`` (symmetric principal root) of a stack [G, n, n] of symmetric positive definite device matrices ->
+    (X [G, n, n], info [G] int32 on the device: 0, or -1 where S has an eigenvalue below ``INVSQRT_MIN_EIG`` -- that
+    matrix of X is NaN)."""
+    lib = _lib.load()
+    if S.dim() == 2:
+        S = S[None]
+    G, n = int(S.shape[0]), int(S.shape[-1])
+    X = torch.empty_like(S) if out is None else out
+    info = torch.empty(G, dtype=torch.int32, device=S.device)
+    check(lib.oovqe_sym_invsqrt_batch(dptr(S), n, G, dptr(X), dptr(info, torch.int32), stream_ptr()),
+          "oovqe_sym_invsqrt_batch")
+    return X, info
+
+
+def boys(nmax, T):
+    """F_0 .. F_nmax of the device Boys function for a device tensor T -> [len(T), nmax + 1]."""
+    lib = _lib.load()
+    T = T.contiguous()
+    out = torch.empty((T.numel(), nmax + 1), dtype=F64, device=T.device)
+    check(lib.oovqe_boys(int(nmax), dptr(T), ctypes.c_int64(T.numel()), dptr(out), stream_ptr()), "oovqe_boys")
+    return out
+
+
+def coords_to_device(basis, coords, device=None):
+    """Geometries as ``GTOBasis.coordinates`` takes them -> [G, natm, 3] device tensor in Bohr."""
+    device = _lib.require_device() if device is None else device
+    if isinstance(coords, torch.Tensor) and coords.is_cuda:
+        xyz = coords.to(F64)
+        if xyz.dim() == 2:
+            xyz = xyz[None]
+        if tuple(xyz.shape[1:]) != (basis.natm, 3):
+            raise ValueError(f"coordinates of shape {tuple(xyz.shape)}, expected [G, {basis.natm}, 3]")
+        return (xyz / BOHR).contiguous()
+    return torch.as_tensor(basis.coordinates(coords) / BOHR).to(device)
+
+
+def integrals_batch(basis, coords, check_overlap=True):
+    """AO integrals of G geometries on the device.
+
+    Args:
+        basis: GTOBasis
+        coords: [G, natm, 3] in Angstrom, or a list of geometries (see ``GTOBasis.coordinates``)
+        check_overlap: read ``info`` back (G integers) and raise for a linearly dependent basis
+
+    Returns a namespace of device tensors: ``overlap`` [G, N, N], ``int1e_ao`` [G, N, N] (kinetic + nuclear
+    attraction), ``oao_coeff`` [G, N, N] (``S^-1/2``), ``nuc`` [G], ``int2e_ao`` [G, N, N, N, N], ``info`` [G]."""
+    device = _lib.require_device()
+    xyz = coords_to_device(basis, coords, device)
+    G, N = int(xyz.shape[0]), basis.nao
+    out = SimpleNamespace(
+        overlap=torch.empty((G, N, N), dtype=F64, device=device),
+        int1e_ao=torch.empty((G, N, N), dtype=F64, device=device),
+        int2e_ao=torch.empty((G, N, N, N, N), dtype=F64, device=device),
+        nuc=torch.empty(G, dtype=F64, device=device))
+    integrals_into(basis, xyz, out.overlap, out.int1e_ao, out.int2e_ao, out.nuc)
+    out.oao_coeff, out.info = sym_invsqrt_batch(out.overlap)
+    if check_overlap:
+        raise_if_dependent(out.info)
+    return out
+
+
+def raise_if_dependent(info, rows=None):
+    bad = torch.nonzero(info < 0).flatten().tolist()
+    if bad:
+        if rows is not None:
+            bad = [int(rows[b]) for b in bad]
+        raise _lib.OovqeError(f"overlap of geometries {bad} has an eigenvalue below {INVSQRT_MIN_EIG}: "
+                              "linearly dependent basis (atoms on top of each other?)")

@@ -629,6 +629,38 @@ int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int batch, const 
                             double* energies, double* ci, double* s2, double* rnorm, int* info, double* work,
                             oovqe_stream_t stream);
 
+/* ---- Gaussian integrals of a stack of geometries (gto.hip): contracted Cartesian s and p shells, McMurchie-Davidson.
+ * One basis description is shared by all geometries, every array is a device array:
+ *   shells [nshell][4] int32: atom index, l, number of primitives, offset of the shell's first primitive in exps / coefs
+ *   exps, coefs [nprim_total]: exponents and contraction coefficients of the NORMALISED contracted function (primitive
+ *     norms included), charges [natm], coords [batch][natm][3] in Bohr.
+ * AO order: shells in table order, a p shell gives px, py, pz.  Outputs (each may be null to skip it): overlap and h_ao
+ * = kinetic + nuclear attraction [batch][nao][nao], exactly symmetric (each unique element computed once and stored to
+ * both places); g_ao [batch][nao]^4 = (pq|rs), chemist order, every unique value stored to its (up to 8) symmetric
+ * places from one register (oovqe_eri_ingest finds both symmetry flags); nuc [batch].
+ * Limits (a negative code is returned and oovqe_last_error gives the text): l <= OOVQE_GTO_MAX_L, at most
+ * OOVQE_GTO_MAX_PRIM primitives per shell, nshell <= OOVQE_GTO_MAX_SHELL, nao equal to the functions of the table.
+ * The call reads the shell table back (one stream synchronisation) to enforce them and to size its launches.
+ * work: oovqe_gto_work_size(nshell, largest number of primitives of a shell, batch) doubles. */
+#define OOVQE_GTO_MAX_L 1
+#define OOVQE_GTO_MAX_PRIM 6
+#define OOVQE_GTO_MAX_SHELL 128
+int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch);
+int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                              const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                              int nao, double* overlap, double* h_ao, double* g_ao, double* nuc, double* work,
+                              oovqe_stream_t stream);
+/* x[b] = s[b]^-1/2 (the symmetric principal root, exactly symmetric) for a stack of symmetric positive definite
+ * matrices [batch][n][n] (the lower triangle of s is read; x may be s), n <= OOVQE_INVSQRT_MAX_N: cyclic Jacobi, one
+ * wave per matrix.  info[b] = 0, or -1 when s[b] has an eigenvalue below OOVQE_INVSQRT_MIN_EIG (linearly dependent
+ * basis) or is not finite: x[b] is then filled with NaN; the other matrices of the call are unaffected. */
+#define OOVQE_INVSQRT_MAX_N 64
+#define OOVQE_INVSQRT_MIN_EIG 1e-8
+int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* info, oovqe_stream_t stream);
+/* f [count][nmax + 1] = F_0 .. F_nmax (Boys function) of t [count], nmax <= 4, through the device function of the
+ * integral kernels. */
+int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
