@@ -209,6 +209,9 @@ SIGNATURES = {
     "oovqe_ci_davidson_batch": (ctypes.c_int, [ctypes.c_int] * 4 + [c_double_p] * 3
                                 + [ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int]
                                 + [c_double_p] * 4 + [c_int32_p, c_double_p, c_stream]),
+    "oovqe_ci_davidson_shift_batch": (ctypes.c_int, [ctypes.c_int] * 4 + [c_double_p] * 3
+                                      + [ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int]
+                                      + [c_double_p] * 4 + [c_int32_p, c_double_p, c_stream]),
     "oovqe_circuit_rdms_is_small": (ctypes.c_int, [ctypes.c_int] * 4),
     "oovqe_gto_work_size": (ctypes.c_int64, [ctypes.c_int] * 3),
     "oovqe_gto_integrals_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,

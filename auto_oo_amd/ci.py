@@ -24,7 +24,11 @@ MAX_NCAS = 8
 MAX_DET = 4900
 MAX_ROOTS = 4
 
-CIResult = namedtuple("CIResult", "energies ci s2 converged rnorm info")
+SPIN_SHIFT = 1.0            # the S^2 penalty a fix_singlet solve starts with
+MAX_SPIN_SHIFT = 64.0       # ... and the largest one tried
+S2_TOL = 1e-6               # |<S^2>| below which a root counts as a singlet
+
+CIResult = namedtuple("CIResult", "energies ci s2 converged rnorm info shift")
 
 
 def ci_dimension(ncas, nelecas):
@@ -47,16 +51,16 @@ def check_scope(ncas, nelecas, nroots=1):
     return dc
 
 
-def casci_packed(coef, c1_offset, ncas, nelecas, nroots=1, fix_singlet=True, tol=1e-9, max_iter=200, count=None):
-    """CI of the problems whose coefficients sit in the rows of ``coef`` [B, stride] (device fp64, rows contiguous
-    in memory one ``coef.stride(0)`` apart): c0 at column 0, c1 [a, a] at ``c1_offset``, c2 [a, a, a, a] right
-    behind c1 -- the layout of ``oovqe_cas_eval_batch``'s packed outputs.  ONE launch for all rows."""
-    dc = check_scope(ncas, nelecas, nroots)
+def singlet_count(ncas, nelecas):
+    """Number of singlets among the determinants of the sector (Weyl's dimension formula at S = 0)."""
+    a, n = int(ncas), int(nelecas) // 2
+    return comb(a + 1, n) * comb(a + 1, n + 1) // (a + 1)
+
+
+def _launch(coef, c1_offset, a, nelecas, nroots, shift, tol, max_iter, B):
+    """One ``oovqe_ci_davidson_shift_batch`` launch on the first B rows of ``coef``."""
     lib = _lib.load()
-    B = coef.shape[0] if count is None else int(count)
-    a = int(ncas)
-    if coef.dtype != F64 or not coef.is_cuda or coef.stride(1) != 1:
-        raise ValueError("coef must be a row-major fp64 device tensor")
+    dc = ci_dimension(a, nelecas)
     dev = coef.device
     e = torch.empty((B, nroots), dtype=F64, device=dev)
     ci = torch.empty((B, nroots, dc), dtype=F64, device=dev)
@@ -69,11 +73,60 @@ def casci_packed(coef, c1_offset, ncas, nelecas, nroots=1, fix_singlet=True, tol
     work = torch.empty(max(nw, 1), dtype=F64, device=dev)
     p0 = coef.data_ptr()
     p1 = p0 + 8 * int(c1_offset)
-    check(lib.oovqe_ci_davidson_batch(a, int(nelecas), int(nroots), B, ctypes.c_void_p(p0), ctypes.c_void_p(p1),
-                                      ctypes.c_void_p(p1 + 8 * a * a), int(coef.stride(0)), int(bool(fix_singlet)),
-                                      float(tol), int(max_iter), dptr(e), dptr(ci), dptr(s2), dptr(rn),
-                                      dptr(info, torch.int32), dptr(work), stream_ptr()), "oovqe_ci_davidson_batch")
+    check(lib.oovqe_ci_davidson_shift_batch(a, int(nelecas), int(nroots), B, ctypes.c_void_p(p0),
+                                            ctypes.c_void_p(p1), ctypes.c_void_p(p1 + 8 * a * a),
+                                            int(coef.stride(0)), float(shift), float(tol), int(max_iter), dptr(e),
+                                            dptr(ci), dptr(s2), dptr(rn), dptr(info, torch.int32), dptr(work),
+                                            stream_ptr()), "oovqe_ci_davidson_shift_batch")
     return e, ci, s2, rn, info
+
+
+def _solve_packed(coef, c1_offset, ncas, nelecas, nroots, fix_singlet, tol, max_iter, count):
+    """``casci_packed`` and the spin shift each problem was solved with, [B]."""
+    check_scope(ncas, nelecas, nroots)
+    B = coef.shape[0] if count is None else int(count)
+    a, nroots = int(ncas), int(nroots)
+    if coef.dtype != F64 or not coef.is_cuda or coef.stride(1) != 1:
+        raise ValueError("coef must be a row-major fp64 device tensor")
+    if not 0 <= B <= coef.shape[0]:
+        raise ValueError(f"count = {B} outside the {coef.shape[0]} rows of coef")
+    lam = SPIN_SHIFT if fix_singlet else 0.0
+    out = _launch(coef, c1_offset, a, nelecas, nroots, lam, tol, max_iter, B)
+    shift = torch.full((B,), lam, dtype=F64, device=coef.device)
+    if not fix_singlet or B == 0:
+        return out + (shift,)
+    e, ci, s2, rn, info = out
+    want = min(nroots, singlet_count(a, nelecas))
+    while lam < MAX_SPIN_SHIFT:
+        # Solved again, together, with the shift doubled: converged problems whose lowest roots are not all
+        # singlets (a state of higher spin lies more than lam S (S + 1) below one of them), and problems that stopped
+        # short of max_iter (a lifted state lies at a root, the Ritz vectors mix the two and the residual of H does
+        # not fall).  A solve that ran out of iterations is left as it is.
+        few = (s2.abs() < S2_TOL).sum(1) < want
+        redo = torch.nonzero(((info == 0) & few) | ((info > 0) & (info < max_iter))).flatten()
+        if redo.numel() == 0:
+            break
+        lam *= 2.0
+        sub = _launch(coef[:B][redo].contiguous(), c1_offset, a, nelecas, nroots, lam, tol, max_iter, redo.numel())
+        for full, part in zip((e, ci, s2, rn, info), sub):
+            full[redo] = part
+        shift[redo] = lam
+    if want < nroots:
+        # fewer singlets than roots: the singlets first, then the other states, each group in its order
+        order = torch.argsort((s2.abs() >= S2_TOL).to(torch.int8), dim=1, stable=True)
+        e, s2, rn = (torch.gather(t, 1, order) for t in (e, s2, rn))
+        ci = torch.gather(ci, 1, order[:, :, None].expand_as(ci))
+    return e, ci, s2, rn, info, shift
+
+
+def casci_packed(coef, c1_offset, ncas, nelecas, nroots=1, fix_singlet=True, tol=1e-9, max_iter=200, count=None):
+    """CI of the problems whose coefficients sit in the rows of ``coef`` [B, stride] (device fp64, rows contiguous
+    in memory one ``coef.stride(0)`` apart): c0 at column 0, c1 [a, a] at ``c1_offset``, c2 [a, a, a, a] right
+    behind c1 -- the layout of ``oovqe_cas_eval_batch``'s packed outputs.  ``count``: solve the first ``count`` rows
+    only.  ONE launch for all rows; with ``fix_singlet`` one more for those rows, if any, whose roots came out with
+    a state of higher spin among them (see ``casci``), which costs one device-to-host read of a flag.
+    -> energies, ci, s2, rnorm, info as in ``casci``."""
+    return _solve_packed(coef, c1_offset, ncas, nelecas, nroots, fix_singlet, tol, max_iter, count)[:5]
 
 
 def casci(c0, c1, c2, ncas, nelecas, nroots=1, fix_singlet=True, tol=1e-9, max_iter=200):
@@ -81,11 +134,32 @@ def casci(c0, c1, c2, ncas, nelecas, nroots=1, fix_singlet=True, tol=1e-9, max_i
     ``molecular_hamiltonian_coefficients``: E = c0 + c1.gamma + c2.Gamma) in the N_alpha = N_beta sector.
 
     Batched over a leading dimension: c0 [B] (or scalar), c1 [B, a, a], c2 [B, a, a, a, a]; unbatched inputs give
-    B = 1.  ``fix_singlet``: the roots are singlets (an S^2 penalty in the sigma; the energies are <H>).
-    ``tol``: residual norm ||H c - E c|| at which a root counts as converged.
-    -> CIResult(energies [B, nroots], ci [B, nroots, Dc] (sector layout), s2 [B, nroots] (<S^2>),
-    converged [B] bool, rnorm [B, nroots], info [B] int32).  Unconverged problems are reported through
-    ``converged`` / ``info`` (> 0: iterations done), not hidden; invalid input raises."""
+    B = 1.  c1 and c2 need no index symmetry: H is that of the coefficients averaged over c1_pq <-> c1_qp and
+    c2_pqrs <-> c2_rspq, c2_qpsr, c2_srqp, which leaves c0 + c1.gamma + c2.Gamma of every real state unchanged.
+
+    ``fix_singlet=False``: the lowest eigenpairs of H in the whole sector, whatever their spin.
+
+    ``fix_singlet=True``: the lowest SINGLET eigenpairs.  The solver iterates on H + shift S^2, which lifts a state
+    of spin S by shift S (S + 1); it starts at shift = 1, and a problem whose roots hold fewer than
+    min(nroots, number of singlets) states with |<S^2>| < 1e-6, or whose solve stopped short of ``max_iter``
+    without converging (a lifted state sits on a root), is solved again with the shift doubled, up to shift = 64.
+    When that bound is reached the roots are returned as they are and ``s2`` shows which are not singlets;
+    ``run_casscf`` / ``run_sa_casscf`` raise on such a root.  The energies are <H>, without the penalty.  A sector with fewer singlets than ``nroots`` (only CAS(2e,2o) with nroots = 4: 3 singlets of 4
+    determinants) returns the singlets first, in ascending order, and then the lowest remaining states of
+    H + shift S^2, in ascending order of that operator, with their <S^2> in ``s2``.
+
+    ``tol``: a problem counts as converged when, for every root, the residual norm |H c - E c| is below ``tol``,
+    and with ``fix_singlet`` that of H + shift S^2 as well; ``rnorm`` is the larger of the two where both were
+    evaluated (at acceptance) and the residual norm of the operator iterated on otherwise.  Converged therefore
+    means: each energy lies within ``rnorm`` of an eigenvalue of H.  The guess space holds a vector with a
+    component on every determinant, so that no eigenvector is out of reach by symmetry; that a converged root is
+    the k-th LOWEST is nevertheless what a Davidson iteration finds in practice, not what it can prove.
+
+    -> CIResult(energies [B, nroots], ci [B, nroots, Dc] (sector layout, orthonormal, the largest |component| of
+    each vector positive), s2 [B, nroots] (<S^2>), converged [B] bool, rnorm [B, nroots], info [B] int32,
+    shift [B]).  Unconverged problems are reported through ``converged`` / ``info`` (> 0: iterations done), not
+    hidden, and one that used all ``max_iter`` iterations is not solved again with another shift; invalid input
+    raises."""
     check_scope(ncas, nelecas, nroots)
     a = int(ncas)
     dev = _lib.require_device()
@@ -96,8 +170,8 @@ def casci(c0, c1, c2, ncas, nelecas, nroots=1, fix_singlet=True, tol=1e-9, max_i
     if c2.shape[0] != B:
         raise ValueError(f"c1 holds {B} problems, c2 {c2.shape[0]}")
     coef = torch.cat((c0[:, None], c1, c2), dim=1).contiguous()
-    e, ci, s2, rn, info = casci_packed(coef, 1, a, nelecas, nroots, fix_singlet, tol, max_iter)
-    return CIResult(e, ci, s2, info == 0, rn, info)
+    e, ci, s2, rn, info, shift = _solve_packed(coef, 1, a, nelecas, nroots, fix_singlet, tol, max_iter, None)
+    return CIResult(e, ci, s2, info == 0, rn, info, shift)
 
 
 # ---- RDMs of CI vectors (the sector engine's kernel) ---------------------------------------------------------
@@ -180,6 +254,9 @@ def _casscf(mol, ncas, nelecas, weights, fix_singlet, verbose, max_macro=100, e_
         res = casci(c0, c1, c2, ncas, nelecas, nroots, bool(fix_singlet))
         if not bool(res.converged.all()):
             raise RuntimeError(f"CASSCF: CASCI did not converge (residuals {res.rnorm.tolist()})")
+        if fix_singlet and not bool((res.s2.abs() < S2_TOL).all()):
+            raise RuntimeError(f"CASSCF: a root is not a singlet (<S^2> = {res.s2.tolist()}, spin shift "
+                               f"{res.shift.tolist()}): it is not averaged into the energy")
         g1s, g2s = sector_rdms(res.ci[0], ncas, nelecas)
         g1 = (w[:, None, None] * g1s).sum(0)
         g2 = (w.reshape(-1, 1, 1, 1, 1) * g2s).sum(0)

@@ -18,9 +18,18 @@
 // pq that reach ia are gathered into X [nv, nb] (LDS), Y = M^T X [a^2, nb] is a small dense product, and
 // sigma(ia, ib) = sum_rs sign * Y[rs][src_rs(ib)] gathers Y with the beta excitations.
 //
-// Spin.  S^2 = S_- S_+ at Ms = 0, S_- S_+ = N_beta - sum_pq A_qp B_pq: with fix_singlet the sigma is that of
-// H + lambda S^2 (lambda = CI_SPIN_SHIFT), the roots are singlets, and the energy reported is
-// <H> = theta - lambda <S^2>, <S^2> from the same sigma routine with the S^2 coefficients.
+// Spin.  S^2 = S_- S_+ at Ms = 0, S_- S_+ = N_beta - sum_pq A_qp B_pq: with a spin shift lambda > 0 the sigma is
+// that of H + lambda S^2, whose lowest roots are the lowest of { E + lambda S (S + 1) }, and the energy reported is
+// <H> = theta - lambda <S^2>, <S^2> from the same sigma routine with the S^2 coefficients.  A state of spin S is
+// lifted by lambda S (S + 1) and no further: whether the roots ARE singlets is for the caller to read off <S^2> and,
+// where they are not, to solve again with a larger shift (ci.casci_packed does).  The residual norms reported are
+// those of H + lambda S^2 at theta.
+//
+// Guess.  Unit vectors on the 2 nroots + 2 lowest diagonal elements, and one more vector with a nonzero component on
+// every other determinant (a fixed hash of its index).  |ia, ib> and |ib, ia> have the same diagonal element, so the
+// unit vectors span whole classes of the alpha/beta-swap symmetry (and of any point group that maps determinants
+// onto determinants); corrections never leave the classes of the Ritz vectors they come from, and without the hash
+// vector an eigenvector of a class the unit vectors miss is never reached while every residual goes below tol.
 //
 // Coefficients are symmetrised on load over the symmetries every real state's RDMs have (gamma_pq = gamma_qp,
 // Gamma_pqrs = Gamma_rspq = Gamma_qpsr = Gamma_srqp), so c0 + c1.gamma + c2.Gamma is unchanged and H is symmetric.
@@ -35,8 +44,10 @@ constexpr int CI_MAXSTR = 70;             // C(8, 4)
 constexpr int CI_MAXDC = CI_MAXSTR * CI_MAXSTR;
 constexpr int CI_MAXSUB = 24;             // Davidson subspace
 constexpr int CI_MAXR = 4;                // roots
+constexpr int CI_MAXKEEP = 2 * CI_MAXR + 2;   // Ritz vectors kept when the subspace is collapsed
+constexpr int CI_MAXREJECT = 3;           // refusals of a solve on the residual of H before it gives up
 constexpr int CI_YREG = (CI_MAXA * CI_MAXA * CI_MAXSTR + CI_NT - 1) / CI_NT;
-constexpr double CI_SPIN_SHIFT = 1.0;
+constexpr double CI_SPIN_SHIFT = 1.0;        // the shift of oovqe_ci_davidson_batch (fix_singlet != 0)
 
 __host__ __device__ inline int ci_binom(int n, int k)
 {
@@ -54,11 +65,11 @@ __host__ __device__ inline int ci_nguess(int Dc, int nroots)
     return g < ms ? g : ms;
 }
 
-// per-problem global scratch (doubles): V [ms][Dc] | W [ms][Dc] | T [nroots][Dc] | Hd [Dc] | Ga [na][na]
+// per-problem global scratch (doubles): V [ms][Dc] | W [ms][Dc] | T [nroots][Dc] | Hd [Dc] | Ga [na][na] | Sx [Dc]
 inline size_t ci_work_per_problem(int na, int nroots)
 {
     const int Dc = na * na;
-    return (size_t)(2 * ci_maxsub(Dc) + nroots + 2) * Dc;
+    return (size_t)(2 * ci_maxsub(Dc) + nroots + 3) * Dc;
 }
 
 struct CiLds {
@@ -156,6 +167,16 @@ __device__ void ci_dots(const double* __restrict__ x, const double* __restrict__
         out[threadIdx.x] = s;
     }
     __syncthreads();
+}
+
+// component I of the last guess vector: a fixed hash of the index in (-1/2, 1/2), never zero
+__device__ __forceinline__ double ci_guess_hash(int I)
+{
+    uint32_t h = (uint32_t)I * 2654435761u + 0x9e3779b9u;
+    h ^= h >> 15;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    return ((double)((h >> 8) & 0xffffu) + 0.5) / 65536.0 - 0.5;
 }
 
 // the lowest value of v (global) whose index is not in excl[0 .. nex); (value, index) order, ties by index
@@ -363,7 +384,7 @@ __device__ void ci_load_m(double* M, const double* __restrict__ c2, int a, doubl
 
 __global__ __launch_bounds__(CI_NT)
 void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g, const double* __restrict__ c1g,
-                        const double* __restrict__ c2g, long c_stride, int fix_singlet, double tol, int max_iter,
+                        const double* __restrict__ c2g, long c_stride, double lam, double tol, int max_iter,
                         double* __restrict__ energies, double* __restrict__ ci, double* __restrict__ s2out,
                         double* __restrict__ rnorm, int* __restrict__ info, double* __restrict__ work,
                         size_t per_problem)
@@ -378,9 +399,9 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
     double* T = W + (size_t)ms * Dc;
     double* Hd = T + (size_t)nroots * Dc;
     double* Ga = Hd + Dc;
+    double* Sx = Ga + Dc;                           // S^2 x_k of one Ritz vector
     const double* c1 = c1g + (size_t)b * c_stride;
     const double* c2 = c2g + (size_t)b * c_stride;
-    const double lam = fix_singlet ? CI_SPIN_SHIFT : 0.0;
 
     // ---- strings, excitation table, coefficients ------------------------------------------------------------
     if (tid == 0) {
@@ -460,7 +481,7 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
     }
     __syncthreads();
 
-    // ---- guess: unit vectors on the lowest diagonal elements ---------------------------------------------------
+    // ---- guess: unit vectors on the lowest diagonal elements, and the hash vector orthogonal to them -----------
     const int ng = ci_nguess(Dc, nroots);
     for (int k = 0; k < ng; ++k) {
         const int I = ci_argmin(T, Dc, L.chosen, k, L.red, L.ints);
@@ -468,14 +489,31 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
         for (int J = tid; J < Dc; J += CI_NT) V[(size_t)k * Dc + J] = (J == I) ? 1.0 : 0.0;
         __syncthreads();
     }
+    int m = ng;
+    if (ng < ms) {                                   // (so Dc > ng: some determinant is not a unit guess)
+        double* t = V + (size_t)ng * Dc;
+        for (int J = tid; J < Dc; J += CI_NT) {
+            bool unit = false;
+            for (int k = 0; k < ng; ++k) unit |= L.chosen[k] == J;
+            t[J] = unit ? 0.0 : ci_guess_hash(J);
+        }
+        __syncthreads();
+        ci_dots(t, t, 0, 1, Dc, L.dots, L.red);
+        const double inv = 1.0 / sqrt(L.dots[0]);
+        for (int J = tid; J < Dc; J += CI_NT) t[J] *= inv;
+        __syncthreads();
+        m = ng + 1;
+    }
 
     // ---- Davidson iterations ------------------------------------------------------------------------------------
-    int m = ng, mold = 0, iters = 0, conv_all = 0;
-    double rn[CI_MAXR];                  // residual norms (every thread holds them)
-#pragma unroll
-    for (int k = 0; k < CI_MAXR; ++k) rn[k] = 0.0;
+    int mold = 0, iters = 0, conv_all = 0, nreject = 0;
+    bool have_s2 = false;                // L.scal holds <S^2> of the current Ritz vectors
+    double* rn = L.scal + CI_MAXR;       // residual norms
+    if (tid < CI_MAXR) rn[tid] = 0.0;
+    __syncthreads();
     for (int it = 0; it < max_iter; ++it) {
         iters = it + 1;
+        have_s2 = false;
         for (int i = mold; i < m; ++i) {
             for (int J = tid; J < Dc; J += CI_NT) L.Cv[J] = V[(size_t)i * Dc + J];
             __syncthreads();
@@ -513,28 +551,77 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
         for (int k = 0; k < CI_MAXR; ++k) {
             if (k < nr) {
                 ci_dots(T + (size_t)k * Dc, T + (size_t)k * Dc, 0, 1, Dc, L.dots, L.red);
-                rn[k] = sqrt(fmax(L.dots[0], 0.0));
-                nunc += (rn[k] < tol) ? 0 : 1;          // (NaN counts as not converged)
+                const double r = sqrt(fmax(L.dots[0], 0.0));
+                if (tid == 0) rn[k] = r;
+                nunc += (r < tol) ? 0 : 1;              // (NaN counts as not converged)
             }
+        }
+        __syncthreads();
+        // With a spin shift the residuals above are those of H + lam S^2.  A component of spin S along an eigenvector
+        // of H at E enters them with E + lam S (S + 1) - theta, and the residual of H with E - <H>, which is the larger
+        // one for a state of higher spin below the root.  So a solve is accepted only when the residuals of H,
+        // r_k - lam (S^2 x_k - <S^2> x_k), are below tol as well; the norms reported are the larger of the two.
+        // Iterating on drives both down together, unless a lifted state lies at a root: the Ritz vector then mixes
+        // the two spins whatever the residual of H + lam S^2.  After CI_MAXREJECT refusals the solve stops as not
+        // converged (info < max_iter) and the caller's remedy is another shift.
+        if (nunc == 0 && lam > 0.0) {
+            ci_load_m(L.M, nullptr, a, 1.0, true);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < CI_MAXR; ++k) {
+                if (k < nr) {
+                    for (int J = tid; J < Dc; J += CI_NT) {
+                        double x = 0.0;
+                        for (int j = 0; j < m; ++j) x += L.U[j * CI_MAXSUB + k] * V[(size_t)j * Dc + J];
+                        L.Cv[J] = x;
+                    }
+                    __syncthreads();
+                    ci_sigma(L, a, na, nullptr, (double)n, Sx);
+                    ci_dots(Sx, L.Cv, 0, 1, Dc, L.dots, L.red);
+                    const double s2 = L.dots[0];
+                    for (int J = tid; J < Dc; J += CI_NT)
+                        Sx[J] = T[(size_t)k * Dc + J] - lam * (Sx[J] - s2 * L.Cv[J]);
+                    __syncthreads();
+                    ci_dots(Sx, Sx, 0, 1, Dc, L.dots, L.red);
+                    if (tid == 0) L.scal[k] = s2;          // (read in the output stage, many barriers on)
+                    const double r = fmax(rn[k], sqrt(fmax(L.dots[0], 0.0)));
+                    nunc += (r < tol) ? 0 : 1;
+                    __syncthreads();                       // (every thread has read rn[k])
+                    if (tid == 0) rn[k] = r;
+                }
+            }
+            have_s2 = true;
+            __syncthreads();
         }
         if (nunc == 0) { conv_all = 1; break; }
         if (it == max_iter - 1) break;
-        // collapse onto the current Ritz vectors when the new directions do not fit
+        if (have_s2 && ++nreject >= CI_MAXREJECT) break;
+        if (have_s2) {                                 // (M held the S^2 coefficients for the check)
+            ci_load_m(L.M, c2, a, lam, false);
+            __syncthreads();
+        }
+        // collapse when the new directions do not fit: onto the lowest 2 nroots + 2 Ritz vectors (those above the
+        // roots carry what the subspace has learnt about the next eigenvalues, which sets the rate of the last root)
         if (m + nunc > ms) {
-            const int nk = nr;
-            for (int I = tid; I < Dc; I += CI_NT) {
-                double xv[CI_MAXR], xw[CI_MAXR];
+            int nk = 2 * nr + 2;
+            if (nk > ms - nunc) nk = ms - nunc;
+            if (nk < nr) nk = nr;
+            for (int pass = 0; pass < 2; ++pass) {      // V, then W (each element is read before it is written)
+                double* Z = pass ? W : V;
+                for (int I = tid; I < Dc; I += CI_NT) {
+                    double x[CI_MAXKEEP];
 #pragma unroll
-                for (int k = 0; k < CI_MAXR; ++k) { xv[k] = 0.0; xw[k] = 0.0; }
-                for (int j = 0; j < m; ++j) {
-                    const double w = W[(size_t)j * Dc + I], v = V[(size_t)j * Dc + I];
+                    for (int k = 0; k < CI_MAXKEEP; ++k) x[k] = 0.0;
+                    for (int j = 0; j < m; ++j) {
+                        const double z = Z[(size_t)j * Dc + I];
 #pragma unroll
-                    for (int k = 0; k < CI_MAXR; ++k)
-                        if (k < nk) { xv[k] += L.U[j * CI_MAXSUB + k] * v; xw[k] += L.U[j * CI_MAXSUB + k] * w; }
+                        for (int k = 0; k < CI_MAXKEEP; ++k)
+                            if (k < nk) x[k] += L.U[j * CI_MAXSUB + k] * z;
+                    }
+#pragma unroll
+                    for (int k = 0; k < CI_MAXKEEP; ++k)
+                        if (k < nk) Z[(size_t)k * Dc + I] = x[k];
                 }
-#pragma unroll
-                for (int k = 0; k < CI_MAXR; ++k)
-                    if (k < nk) { V[(size_t)k * Dc + I] = xv[k]; W[(size_t)k * Dc + I] = xw[k]; }
             }
             __syncthreads();                           // (every thread has read U before it is reset)
             for (int o = tid; o < CI_MAXSUB * CI_MAXSUB; o += CI_NT) {
@@ -595,15 +682,17 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
         for (int k = 0; k < CI_MAXR; ++k)
             if (k < nroots) T[(size_t)k * Dc + I] = x[k];
     }
-    ci_load_m(L.M, nullptr, a, 1.0, true);
+    if (!have_s2) ci_load_m(L.M, nullptr, a, 1.0, true);
     __syncthreads();
-    double* s2v = W;                                // (W is free now: S^2 x_k)
     for (int k = 0; k < nroots; ++k) {
-        for (int J = tid; J < Dc; J += CI_NT) L.Cv[J] = T[(size_t)k * Dc + J];
-        __syncthreads();
-        ci_sigma(L, a, na, nullptr, (double)n, s2v);
-        ci_dots(s2v, T + (size_t)k * Dc, 0, 1, Dc, L.dots, L.red);
-        const double s2 = L.dots[0];
+        double s2 = have_s2 ? L.scal[k] : 0.0;
+        if (!have_s2) {
+            for (int J = tid; J < Dc; J += CI_NT) L.Cv[J] = T[(size_t)k * Dc + J];
+            __syncthreads();
+            ci_sigma(L, a, na, nullptr, (double)n, Sx);
+            ci_dots(Sx, T + (size_t)k * Dc, 0, 1, Dc, L.dots, L.red);
+            s2 = L.dots[0];
+        }
         // sign: the largest |component| (first on ties) positive, in the sector layout
         double best = -1.0;
         int bi = 0x7fffffff;
@@ -640,10 +729,7 @@ void ci_davidson_kernel(int a, int n, int nroots, const double* __restrict__ c0g
         if (tid == 0) {
             energies[b * nroots + k] = c0g[(size_t)b * c_stride] + L.theta[k] - lam * s2;
             s2out[b * nroots + k] = s2;
-            double r = rn[0];
-#pragma unroll
-            for (int j = 1; j < CI_MAXR; ++j) if (j == k) r = rn[j];
-            rnorm[b * nroots + k] = r;
+            rnorm[b * nroots + k] = rn[k];
         }
         __syncthreads();
     }
@@ -675,10 +761,11 @@ extern "C" int64_t oovqe_ci_work_size(int ncas, int nelecas, int nroots, int bat
     return (int64_t)ci_work_per_problem(na, nroots) * batch;
 }
 
-extern "C" int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int batch, const double* c0,
-                                       const double* c1, const double* c2, int64_t c_stride, int fix_singlet,
-                                       double tol, int max_iter, double* energies, double* ci, double* s2,
-                                       double* rnorm, int* info, double* work, oovqe_stream_t stream)
+extern "C" int oovqe_ci_davidson_shift_batch(int ncas, int nelecas, int nroots, int batch, const double* c0,
+                                             const double* c1, const double* c2, int64_t c_stride,
+                                             double spin_shift, double tol, int max_iter, double* energies,
+                                             double* ci, double* s2, double* rnorm, int* info, double* work,
+                                             oovqe_stream_t stream)
 {
     int na = 0;
     const int rc = ci_shape(ncas, nelecas, nroots, &na);
@@ -689,13 +776,24 @@ extern "C" int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int ba
                   "oovqe_ci_davidson_batch: null pointer");
     OOVQE_REQUIRE(c_stride >= 0, "oovqe_ci_davidson_batch: c_stride = %lld", (long long)c_stride);
     OOVQE_REQUIRE(tol > 0.0 && max_iter >= 1, "oovqe_ci_davidson_batch: tol = %g, max_iter = %d", tol, max_iter);
+    OOVQE_REQUIRE(spin_shift >= 0.0 && spin_shift <= 1e6, "oovqe_ci_davidson_batch: spin_shift = %g", spin_shift);
     const size_t lds = ci_lds_bytes(ncas, na);
     OOVQE_REQUIRE(lds <= 160 * 1024, "oovqe_ci_davidson_batch: %zu bytes of LDS", lds);
     if (oovqe_ensure_dynamic_lds(reinterpret_cast<const void*>(&ci_davidson_kernel), lds) != 0)
         return OOVQE_ERR_HIP;
     hipLaunchKernelGGL(ci_davidson_kernel, dim3(batch), dim3(CI_NT), lds, (hipStream_t)stream, ncas, nelecas / 2,
-                       nroots, c0, c1, c2, (long)c_stride, fix_singlet ? 1 : 0, tol, max_iter, energies, ci, s2,
-                       rnorm, info, work, ci_work_per_problem(na, nroots));
+                       nroots, c0, c1, c2, (long)c_stride, spin_shift, tol, max_iter, energies, ci, s2, rnorm,
+                       info, work, ci_work_per_problem(na, nroots));
     OOVQE_CHECK_LAUNCH("ci_davidson_kernel");
     return 0;
+}
+
+extern "C" int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int batch, const double* c0,
+                                       const double* c1, const double* c2, int64_t c_stride, int fix_singlet,
+                                       double tol, int max_iter, double* energies, double* ci, double* s2,
+                                       double* rnorm, int* info, double* work, oovqe_stream_t stream)
+{
+    return oovqe_ci_davidson_shift_batch(ncas, nelecas, nroots, batch, c0, c1, c2, c_stride,
+                                         fix_singlet ? CI_SPIN_SHIFT : 0.0, tol, max_iter, energies, ci, s2, rnorm,
+                                         info, work, stream);
 }

@@ -621,13 +621,25 @@ int oovqe_newton_step_size(void);
  * Outputs per problem: energies [nroots] (<H>), ci [nroots][Dc] in the sector layout c = ia * nb + ib with the
  * strings and signs of the sector engine (orthonormal; the largest |component| positive), s2 [nroots] (<S^2>),
  * rnorm [nroots] (residual norms), info = 0 converged, > 0 iterations done when stopped unconverged.
- * fix_singlet: the sigma is that of H + S^2 (roots are singlets); the energy reported is <H>.
+ * spin_shift >= 0: the sigma is that of H + spin_shift S^2, the roots are the lowest of that operator (a state of
+ * spin S lifted by spin_shift S (S + 1)), the energy reported is <H> and rnorm the residual norm of the shifted
+ * operator.  The roots are singlets only where the shift lifts every other state above them: read s2, and solve
+ * again with a larger shift where it is not 0.  oovqe_ci_davidson_batch is the same solve with spin_shift = 1
+ * (fix_singlet != 0) or 0.
+ * With a shift a solve is accepted only when the residual norms of H itself are below tol too; rnorm is then the
+ * larger of the two, and a solve refused three times stops with 0 < info < max_iter (a lifted state lies on a root:
+ * take another shift).  info = 0 says that every rnorm is below tol.  The guess holds a vector with a component on
+ * every determinant, so no eigenvector is orthogonal to the start space by symmetry.
  * work: oovqe_ci_work_size(ncas, nelecas, nroots, batch) doubles. */
 int64_t oovqe_ci_work_size(int ncas, int nelecas, int nroots, int batch);
 int oovqe_ci_davidson_batch(int ncas, int nelecas, int nroots, int batch, const double* c0, const double* c1,
                             const double* c2, int64_t c_stride, int fix_singlet, double tol, int max_iter,
                             double* energies, double* ci, double* s2, double* rnorm, int* info, double* work,
                             oovqe_stream_t stream);
+int oovqe_ci_davidson_shift_batch(int ncas, int nelecas, int nroots, int batch, const double* c0, const double* c1,
+                                  const double* c2, int64_t c_stride, double spin_shift, double tol, int max_iter,
+                                  double* energies, double* ci, double* s2, double* rnorm, int* info, double* work,
+                                  oovqe_stream_t stream);
 
 /* ---- Gaussian integrals of a stack of geometries (gto.hip): contracted Cartesian s and p shells, McMurchie-Davidson.
  * One basis description is shared by all geometries, every array is a device array:
