@@ -220,6 +220,14 @@ SIGNATURES = {
     "oovqe_sym_invsqrt_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_int32_p,
                                                c_stream]),
     "oovqe_boys": (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_int64, c_double_p, c_stream]),
+    "oovqe_fock_jk_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                           c_stream]),
+    "oovqe_sym_eig_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_int32_p,
+                                           c_stream]),
+    "oovqe_rhf_work_size": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
+    "oovqe_rhf_batch": (ctypes.c_int, [c_double_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_double,
+                                                                              ctypes.c_int] + [c_double_p] * 5
+                        + [c_int32_p, c_int32_p, c_double_p, ctypes.c_void_p, c_stream]),
     "oovqe_spin_rdms": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                        c_double_p, c_stream]),
     "oovqe_debug_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),

@@ -21,7 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _lib, excitations as X, gto as GTO, ops
+from . import _lib, excitations as X, gto as GTO, ops, scf
 from ._lib import check, dptr, stream_ptr
 from .gaussian import rhf
 from .moldata import Moldata
@@ -74,6 +74,7 @@ class OO_pqc_batch:
         if self.G < 1:
             raise ValueError("need at least one geometry")
         self.nao = int(nao)
+        self.nelectron = int(nelectron)
         self.ncas, self.nelecas = ncas, nelecas
         self.occ_idx, self.act_idx, self.virt_idx = Moldata.get_active_space_idx(
             SimpleNamespace(nelectron=int(nelectron), nao=self.nao), ncas, nelecas)
@@ -113,15 +114,20 @@ class OO_pqc_batch:
             basis: gto.GTOBasis of the molecule
             coords: [G, natm, 3] in Angstrom, or a list of geometries as ``Moldata_sto3g`` takes them
             ncas, nelecas: active space
-            oao_mo_coeffs: [G][N, N] OAO->MO coefficients.  Default: RHF orbitals of every geometry from the host
-                ``gaussian.rhf`` on the (small) integrals copied back once -- the only host copy on this path
+            oao_mo_coeffs: [G][N, N] OAO->MO coefficients, or ``"rhf"``: RHF orbitals of every geometry from the device
+                solver (``OO_pqc_batch.rhf``; no integral tensor is copied to the host, ``OovqeError`` names the
+                geometries that did not converge).  Default (None): RHF orbitals from the host ``gaussian.rhf`` on
+                the integrals copied back once -- slow for a large stack, prefer ``"rhf"``
         """
         self = cls.__new__(cls)
         xyz = GTO.coords_to_device(basis, coords)
         self._allocate(pqc, int(xyz.shape[0]), basis.nao, basis.nelectron, ncas, nelecas, freeze_active)
         self.basis = basis
         self._write_integrals(xyz, None)
-        if oao_mo_coeffs is None:
+        if isinstance(oao_mo_coeffs, str):
+            self._rhf_orbitals(oao_mo_coeffs, None)
+            oao_mo_coeffs = ()
+        elif oao_mo_coeffs is None:
             S, h, g = self.overlap.cpu().numpy(), self.int1e_ao.cpu().numpy(), self.int2e_ao.cpu().numpy()
             oao_mo_coeffs = [mo_ao_to_mo_oao(rhf(h[k], g[k], S[k], basis.nelectron // 2)[0], S[k])
                              for k in range(self.G)]
@@ -159,14 +165,17 @@ class OO_pqc_batch:
         """Move the batch (or its rows ``index``) to new geometries: ``int2e_ao``, ``int1e_ao``, ``oao_coeff`` and
         ``nuc`` are computed in place on the device, then the symmetry flags / packed copy are re-made (``_ingest``)
         and ``mo_coeff = S^-1/2 C_oao`` refreshed.  ``oao_mo_coeffs=None`` keeps the current orbitals (the tracking
-        regime of a Berry-phase loop); otherwise one [N, N] matrix per new geometry.  No integral tensor passes through
-        the host."""
+        regime of a Berry-phase loop); ``"rhf"`` takes the RHF orbitals of the new geometries from the device solver
+        (``OO_pqc_batch.rhf``; ``OovqeError`` names the geometries that did not converge); otherwise one [N, N] matrix
+        per new geometry.  No integral tensor passes through the host."""
         if self.basis is None:
             raise RuntimeError("set_geometries needs a batch made by OO_pqc_batch.from_geometries")
         xyz = GTO.coords_to_device(self.basis, coords, self.device)
         rows = None if index is None else [int(i) for i in np.atleast_1d(index)]
         self._write_integrals(xyz, rows)
-        if oao_mo_coeffs is not None:
+        if isinstance(oao_mo_coeffs, str):
+            self._rhf_orbitals(oao_mo_coeffs, rows)
+        elif oao_mo_coeffs is not None:
             targets = range(self.G) if rows is None else rows
             if len(oao_mo_coeffs) != len(targets):
                 raise ValueError("one orbital matrix per new geometry")
@@ -177,6 +186,39 @@ class OO_pqc_batch:
         else:
             self._ingest()
         self.refresh_mo_coeff()
+
+    # ---- starting orbitals made on the device (auto_oo_amd/scf.py) ---------------------------------------------------
+    def rhf(self, index=None, **kw):
+        """Closed-shell RHF of the batch's geometries (or its rows ``index``) on the batch's own device tensors
+        (``scf.rhf_batch``; keywords ``conv_tol``, ``err_tol``, ``max_cycle``) -> ``scf.RHFResult`` with ``e_tot =
+        e_elec + nuc``.  The batch is not changed.  Needs the overlap, so a batch made by ``from_geometries``."""
+        if getattr(self, "overlap", None) is None:
+            raise RuntimeError("OO_pqc_batch.rhf needs a batch made by OO_pqc_batch.from_geometries")
+        scf.check_scope(self.nao, nelectron=self.nelectron)
+        if index is None:
+            sel = slice(None)
+        else:
+            rows = [int(i) for i in np.atleast_1d(index)]
+            if any(not 0 <= r < self.G for r in rows):
+                raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+            if rows == list(range(rows[0], rows[0] + len(rows))):
+                sel = slice(rows[0], rows[0] + len(rows))             # (a view: no copy of the integrals)
+            else:
+                sel = torch.as_tensor(rows, device=self.device)
+        res = scf.rhf_batch(self.int1e_ao[sel], self.int2e_ao[sel], self.overlap[sel], self.nelectron // 2,
+                            oao_coeff=self.oao_coeff[sel], **kw)
+        return res._replace(e_tot=res.e_elec + self.nuc[sel])
+
+    def _rhf_orbitals(self, how, rows):
+        """``oao_mo_coeffs="rhf"``: the orbitals of the rows (None: all) from the device solver."""
+        if how != "rhf":
+            raise ValueError(f"oao_mo_coeffs = {how!r}: the only named choice is 'rhf'")
+        res = self.rhf(index=rows)
+        scf.raise_unless_converged(res.info, rows)
+        if rows is None:
+            self.oao_mo_coeff.copy_(res.oao_mo_coeff)
+        else:
+            self.oao_mo_coeff[torch.as_tensor(rows, device=self.device)] = res.oao_mo_coeff
 
     def set_oao_mo_coeff(self, g, oao_mo_coeff):
         """Replace the orbitals of geometry g and refresh mo_coeff[g] = S^-1/2 C_oao

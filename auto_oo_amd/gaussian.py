@@ -346,8 +346,11 @@ class Moldata_sto3g(Moldata):
                   for i in range(len(charges)) for j in range(i))
         super().__init__(T + V, g, S, nuc, sum(charges) - charge)
 
-    def run_rhf(self, verbose=0):
-        """moldata_pyscf.py:58-61"""
+    def run_rhf(self, verbose=0, device=False):
+        """moldata_pyscf.py:58-61: the host ``rhf`` above; ``device=True`` takes the orbitals from the device solver
+        (``scf.rhf_batch``) instead."""
+        if device:
+            return Moldata.run_rhf(self, verbose, device=True)
         if self.hf is None:
             C, e, e_elec = rhf(self.int1e_ao, self.int2e_ao, self.overlap, self.nelectron // 2)
             self.hf = SimpleNamespace(mo_coeff=C, mo_energy=e, e_tot=e_elec + self.nuc)

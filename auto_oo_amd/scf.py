@@ -1,0 +1,163 @@
+"""Closed-shell restricted Hartree-Fock for a stack of geometries on the device (auto_oo_amd/csrc/scf.hip).
+
+The starting orbitals of "geometries in, OO-VQE out": the reference's ``Moldata_pyscf.run_rhf()``
+(src/auto_oo/moldata_pyscf.py:58-61) for G geometries at once, on the integrals that already live on the device.  The
+algorithm is that of the host ``gaussian.rhf`` iterate for iterate (core-Hamiltonian guess, F = h + J - K / 2, DIIS on
+e = F D S - S D F over the last 8 Fock matrices, diagonalisation in the S^-1/2 basis, aufbau occupation), so the host
+routine is the oracle of the tests.  No tensor crosses to the host; the driver watches one pinned word.
+"""
+import ctypes
+from collections import namedtuple
+
+import torch
+
+from . import _lib
+from ._lib import check, dptr, stream_ptr
+
+F64 = torch.float64
+MAX_N = 64                      # OOVQE_INVSQRT_MAX_N
+
+_RHF_FIELDS = ("mo_coeff", "oao_mo_coeff", "mo_energy", "e_elec", "converged", "iterations", "diis_error", "info")
+
+
+class RHFResult(namedtuple("RHFResult", _RHF_FIELDS + ("e_tot",), defaults=(None,))):
+    """Device tensors of ``rhf_batch``, the leading axis over the geometries (absent for a single problem):
+    ``mo_coeff`` AO->MO, ``oao_mo_coeff`` OAO->MO (``mo_coeff = S^-1/2 oao_mo_coeff``), ``mo_energy``, ``e_elec``,
+    ``converged`` (bool), ``iterations`` (Fock builds), ``diis_error`` (the last max|F D S - S D F|) and ``info``:
+    0 converged, 1 ``max_cycle`` reached, -1 overlap with an eigenvalue below ``gto.INVSQRT_MIN_EIG``, -3 NaN or Inf
+    in the inputs.  ``e_tot`` = ``e_elec`` + nuclear repulsion where the caller knows it (``OO_pqc_batch.rhf``)."""
+    __slots__ = ()
+
+
+def check_scope(n, n_occ=None, nelectron=None):
+    """ValueError for what the device solver does not cover: 1 <= n_occ < N <= 64, an even electron count."""
+    n = int(n)
+    if nelectron is not None:
+        if int(nelectron) % 2 != 0:
+            raise ValueError(f"restricted closed-shell Hartree-Fock needs an even electron count, got {nelectron}")
+        n_occ = int(nelectron) // 2
+    if not 2 <= n <= MAX_N:
+        raise ValueError(f"N = {n} basis functions: the device RHF covers 2 .. {MAX_N}")
+    if n_occ is not None and not 1 <= int(n_occ) < n:
+        raise ValueError(f"n_occ = {n_occ}: the device RHF covers 1 <= n_occ < N = {n}")
+
+
+def _stack(name, t, n, rank):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor on the device")
+    if tuple(t.shape[-rank:]) != (n,) * rank or t.dim() not in (rank, rank + 1):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [G]{[n] * rank} or {[n] * rank}")
+    return t if t.dim() == rank + 1 else t[None]
+
+
+_pinned = {}
+
+
+def _verdict_words(device):
+    """Two pinned ints per device through which oovqe_rhf_batch watches the count of finished geometries (the call has
+    read its last copy before it returns, so the words are free again at the next call)."""
+    key = device.index
+    if key not in _pinned:
+        _pinned[key] = torch.zeros(2, dtype=torch.int32).pin_memory()
+    return _pinned[key]
+
+
+def rhf_batch(int1e, int2e, overlap, n_occ, oao_coeff=None, conv_tol=1e-12, err_tol=1e-9, max_cycle=200):
+    """RHF of G problems that share N and ``n_occ``: device tensors ``int1e`` [G, N, N], ``int2e`` [G, N, N, N, N]
+    (chemist order), ``overlap`` [G, N, N] -- or one problem without the leading axis -- and optionally ``oao_coeff``
+    = S^-1/2 (made on the device otherwise).  Converged when |dE| < ``conv_tol`` and max|F D S - S D F| < ``err_tol``.
+    -> ``RHFResult`` of device tensors; nothing is read back, so ask ``result.converged.all()`` (or ``info``) before
+    the orbitals are used."""
+    if not isinstance(overlap, torch.Tensor) or overlap.dim() < 2:
+        raise TypeError("overlap must be a torch tensor [G, N, N] or [N, N]")
+    n = int(overlap.shape[-1])
+    check_scope(n, n_occ=n_occ)
+    if int(max_cycle) < 1:
+        raise ValueError(f"max_cycle = {max_cycle}")
+    if not (conv_tol > 0 and err_tol > 0):
+        raise ValueError("conv_tol and err_tol must be positive")
+    single = overlap.dim() == 2
+    S = _stack("overlap", overlap, n, 2)
+    h = _stack("int1e", int1e, n, 2)
+    g = _stack("int2e", int2e, n, 4)
+    X = None if oao_coeff is None else _stack("oao_coeff", oao_coeff, n, 2)
+    G = int(S.shape[0])
+    if any(int(t.shape[0]) != G for t in (h, g) + (() if X is None else (X,))):
+        raise ValueError("int1e, int2e, overlap and oao_coeff must hold the same number of geometries")
+    lib = _lib.load()
+    dev = _lib.require_device()
+    S, h, g = S.contiguous(), h.contiguous(), g.contiguous()
+    X = None if X is None else X.contiguous()
+    size = int(lib.oovqe_rhf_work_size(n, G))
+    if size < 0:
+        check(size, "oovqe_rhf_work_size")
+    work = torch.empty(size, dtype=F64, device=dev)
+    mo = torch.empty((G, n, n), dtype=F64, device=dev)
+    oao_mo = torch.empty((G, n, n), dtype=F64, device=dev)
+    eps = torch.empty((G, n), dtype=F64, device=dev)
+    e_elec = torch.empty(G, dtype=F64, device=dev)
+    err = torch.empty(G, dtype=F64, device=dev)
+    iters = torch.empty(G, dtype=torch.int32, device=dev)
+    info = torch.empty(G, dtype=torch.int32, device=dev)
+    verdict = _verdict_words(dev)
+    check(lib.oovqe_rhf_batch(dptr(h), dptr(g), dptr(S), dptr(X), n, int(n_occ), G, float(conv_tol), float(err_tol),
+                              int(max_cycle), dptr(mo), dptr(oao_mo), dptr(eps), dptr(e_elec), dptr(err),
+                              dptr(iters, torch.int32), dptr(info, torch.int32), dptr(work),
+                              ctypes.c_void_p(verdict.data_ptr()), stream_ptr()), "oovqe_rhf_batch")
+    out = (mo, oao_mo, eps, e_elec, info == 0, iters, err, info)
+    if single:
+        out = tuple(t[0] for t in out)
+    return RHFResult(*out)
+
+
+def fock_jk(int2e, dm):
+    """J[p,q] = sum_rs g[p,q,r,s] D[r,s] and K[p,q] = sum_rs g[p,r,q,s] D[r,s] for a stack [G, ...] (or one problem)
+    of device tensors: one pass over ``int2e``, no symmetry assumed -> (J, K)."""
+    if not isinstance(dm, torch.Tensor) or dm.dim() < 2:
+        raise TypeError("dm must be a torch tensor [G, N, N] or [N, N]")
+    n = int(dm.shape[-1])
+    if not 1 <= n <= MAX_N:
+        raise ValueError(f"N = {n}: fock_jk covers 1 .. {MAX_N}")
+    single = dm.dim() == 2
+    D = _stack("dm", dm, n, 2).contiguous()
+    g = _stack("int2e", int2e, n, 4).contiguous()
+    if g.shape[0] != D.shape[0]:
+        raise ValueError("int2e and dm must hold the same number of geometries")
+    lib = _lib.load()
+    _lib.require_device()
+    J, K = torch.empty_like(D), torch.empty_like(D)
+    check(lib.oovqe_fock_jk_batch(dptr(g), dptr(D), n, int(D.shape[0]), dptr(J), dptr(K), stream_ptr()),
+          "oovqe_fock_jk_batch")
+    return (J[0], K[0]) if single else (J, K)
+
+
+def sym_eigh_batch(A):
+    """Eigen-decomposition of a stack [G, n, n] (or one matrix) of symmetric device matrices, n <= 64 (the lower
+    triangle is read) -> (w ascending, V with the eigenvectors in columns, each with its component of largest
+    magnitude positive, info: 0, or -3 for a matrix that is not finite)."""
+    if not isinstance(A, torch.Tensor) or A.dim() < 2:
+        raise TypeError("A must be a torch tensor [G, n, n] or [n, n]")
+    n = int(A.shape[-1])
+    if not 1 <= n <= MAX_N:
+        raise ValueError(f"n = {n}: sym_eigh_batch covers 1 .. {MAX_N}")
+    single = A.dim() == 2
+    A = _stack("A", A, n, 2).contiguous()
+    lib = _lib.load()
+    _lib.require_device()
+    G = int(A.shape[0])
+    w = torch.empty((G, n), dtype=F64, device=A.device)
+    V = torch.empty_like(A)
+    info = torch.empty(G, dtype=torch.int32, device=A.device)
+    check(lib.oovqe_sym_eig_batch(dptr(A), n, G, dptr(w), dptr(V), dptr(info, torch.int32), stream_ptr()),
+          "oovqe_sym_eig_batch")
+    return (w[0], V[0], info[0]) if single else (w, V, info)
+
+
+def raise_unless_converged(info, rows=None, what="device RHF"):
+    """OovqeError naming the geometries whose ``info`` is not 0 (G integers are read back)."""
+    info = info.reshape(-1).tolist()
+    bad = [(k if rows is None else int(rows[k]), c) for k, c in enumerate(info) if c != 0]
+    if bad:
+        names = {1: "max_cycle reached", -1: "linearly dependent basis", -3: "NaN or Inf in the integrals"}
+        raise _lib.OovqeError(f"{what} did not converge for geometries "
+                              + ", ".join(f"{k} ({names.get(c, c)})" for k, c in bad))

@@ -673,6 +673,37 @@ int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* i
  * integral kernels. */
 int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream);
 
+/* ---- restricted Hartree-Fock for a stack of geometries (auto_oo_amd/csrc/scf.hip) -----------------------------------
+ * j[b,p,q] = sum_rs g[b,p,q,r,s] d[b,r,s], k[b,p,q] = sum_rs g[b,p,r,q,s] d[b,r,s]   (g [batch][n]^4, d, j, k
+ * [batch][n][n], 1 <= n <= OOVQE_INVSQRT_MAX_N).  One pass over g, no symmetry of g or d assumed, no floating-point
+ * atomics: the result of a geometry does not depend on the stack around it. */
+int oovqe_fock_jk_batch(const double* g, const double* d, int n, int batch, double* j, double* k,
+                        oovqe_stream_t stream);
+/* Eigen-decomposition of a stack of symmetric matrices a [batch][n][n] (the lower triangle is read), n <=
+ * OOVQE_INVSQRT_MAX_N, by the cyclic Jacobi of oovqe_sym_invsqrt_batch: w [batch][n] ascending, v [batch][n][n] with the
+ * eigenvectors in columns, each with its component of largest magnitude positive (the first one on ties).  info[b] = 0,
+ * or -3 when a[b] is not finite (w[b], v[b] are then NaN). */
+int oovqe_sym_eig_batch(const double* a, int n, int batch, double* w, double* v, int* info, oovqe_stream_t stream);
+/* Closed-shell RHF of `batch` problems that share n and n_occ (1 <= n_occ < n <= OOVQE_INVSQRT_MAX_N): core-Hamiltonian
+ * guess, F = h + J - K / 2, E = 1/2 sum D (h + F), DIIS on e = F D S - S D F over the last 8 Fock matrices (the plain F
+ * when the DIIS system is singular), diagonalisation in the S^-1/2 basis, aufbau occupation; converged when
+ * |dE| < conv_tol and max|e| < err_tol.
+ * h, s [batch][n][n], g [batch][n]^4; x = s^-1/2 [batch][n][n] or null (then made by oovqe_sym_invsqrt_batch).
+ * Outputs per geometry, all on the device: mo_coeff [n][n] (AO -> MO, columns), oao_mo_coeff [n][n] (the eigenvectors
+ * c of X F X: mo_coeff = X c), mo_energy [n], e_elec, diis_error (the last max|e|), iterations (Fock builds),
+ * info = 0 converged, 1 max_cycle reached, -1 overlap with an eigenvalue below OOVQE_INVSQRT_MIN_EIG, -3 NaN or Inf in
+ * the inputs (the floating-point outputs of such a geometry are NaN; its neighbours are unaffected).  A geometry that
+ * has finished is frozen: no later iteration of the stack touches its outputs.
+ * work: oovqe_rhf_work_size(n, batch) doubles.  verdict_host: two ints of pinned host memory through which the call
+ * watches the count of finished geometries every few iterations without draining the queue, or null (then it
+ * synchronises the stream at every look).  No tensor crosses to the host.
+ * Sizes out of scope return a negative code before any launch. */
+int64_t oovqe_rhf_work_size(int n, int batch);
+int oovqe_rhf_batch(const double* h, const double* g, const double* s, const double* x, int n, int n_occ, int batch,
+                    double conv_tol, double err_tol, int max_cycle, double* mo_coeff, double* oao_mo_coeff,
+                    double* mo_energy, double* e_elec, double* diis_error, int32_t* iterations, int32_t* info,
+                    double* work, int32_t* verdict_host, oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
