@@ -1,8 +1,11 @@
 // Library-level entry points of liboovqe_hip.so (include/oovqe.h).
 #include "common.h"
 #include <stdarg.h>
-#include <vector>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <utility>
+#include <vector>
 
 static thread_local char g_err[512] = "";
 
@@ -33,8 +36,6 @@ extern "C" int oovqe_device_count(void)
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: a process-wide `static` next to the
 // launch would skip the call on a second device (or race between host threads) and the launch above 64 KB
 // would fail there.
-#include <mutex>
-#include <map>
 int oovqe_ensure_dynamic_lds(const void* kernel, size_t bytes)
 {
     static std::mutex mu;
@@ -53,13 +54,44 @@ int oovqe_ensure_dynamic_lds(const void* kernel, size_t bytes)
     return 0;
 }
 
+// Resident workgroups per CU of a persistent kernel (its dynamic-LDS limit already raised), per (kernel, device,
+// workgroup shape) like the limit itself; >= 1, or OOVQE_ERR_HIP
+int oovqe_blocks_per_cu(const void* kernel, int threads, size_t lds_bytes)
+{
+    static std::mutex mu;
+    static std::map<std::tuple<const void*, int, int, size_t>, int> known;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    std::lock_guard<std::mutex> lock(mu);
+    int& occ = known[std::make_tuple(kernel, dev, threads, lds_bytes)];
+    if (occ > 0) return occ;
+    int nb = 0;
+    OOVQE_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds_bytes), "oovqe_blocks_per_cu");
+    return occ = nb < 1 ? 1 : nb;
+}
+
+// CUs of the current device (256 when the query fails)
+int oovqe_cu_count()
+{
+    static int n_cu[16];
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!n_cu[dev]) {
+        hipDeviceProp_t prop;
+        n_cu[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return n_cu[dev];
+}
+
 // ---- test / measurement switches (common.h: oovqe_option_t) -------------------------------------
 static int g_opts[OOVQE_OPT_COUNT] = {0};
 static const char* const g_opt_names[OOVQE_OPT_COUNT] = {
-    "half_stream_old", "gm_two_per_cu", "gm_one_per_cu", "fused_chunks", "tri_plain_w", "cas_unfused",
-    "sym_no_rs", "sym_mirror", "sym_simple", "sym_two_step", "no_ride", "tri_mode", "k1_no_pair", "k1_force_wide", "gm_plain_grid",
-    "newton_one_wg", "sector_unfused", "sector_probe", "hess_vk_pass", "hess_own_stage1", "panel_rows",
-    "k1_force_nt", "newton_no_chol", "tiles_variant", "sector_lambda_w", "sector_rdm_r3", "gm_three_per_cu", "panel_no_w",
+    "gm_two_per_cu", "gm_one_per_cu", "fused_chunks", "tri_plain_w", "cas_unfused",
+    "sym_no_rs", "sym_mirror", "sym_simple", "sym_two_step", "no_ride", "k1_no_pair", "k1_force_wide", "gm_plain_grid",
+    "newton_one_wg", "sector_unfused", "hess_vk_pass", "hess_own_stage1", "panel_rows",
+    "k1_force_nt", "newton_no_chol", "sector_lambda_w", "sector_rdm_r3", "panel_no_w",
     "stage1_free_run", "one_stream", "tail_split"};
 static_assert(sizeof(g_opt_names) / sizeof(g_opt_names[0]) == OOVQE_OPT_COUNT, "option name table out of step with oovqe_option_t");
 

@@ -74,7 +74,6 @@ constexpr int AUX_PLAIN = 0, AUX_NT = 2;
 // upper triangle, t = p(2N - p + 1)/2 + (q - p); the result goes to T2[p,q] AND T2[q,p] (sym == 1)
 // or to the packed triangle J[t] (sym == 2).
 constexpr int SYM_FULL = 0, SYM_MIRROR = 1, SYM_PACKED = 2;
-constexpr int OOVQE_TRI_MODE_DEFAULT = 3;      // realisation of the packed-triangle stage 1 (half_tri_batched)
 __device__ __forceinline__ void tri_decode(long t, int N, int& p, int& q)
 {
     const double b = 2.0 * N + 1.0;
@@ -86,23 +85,18 @@ __device__ __forceinline__ void tri_decode(long t, int N, int& p, int& q)
     q = pp + (int)(t - (long)pp * (2 * N - pp + 1) / 2);
 }
 
-// NST > 0: the slab has exactly NST column tiles and nkc == 1; ALL its loads (NST*KCH per lane) are
-// issued at kernel entry, before the prologue barrier, so the HBM latency is paid once per wave.
-// NST == 0: streaming variant for large N (register double buffer, one chunk ahead).
+// N <= 48: the slab has exactly NST column tiles and one k-chunk; ALL its loads (NST*KCH per lane) are
+// issued at kernel entry, so the HBM latency is paid once per wave.  (N > 48: half_stream_kernel.)
 template <int ZT, int KCH, int NST>
 __global__ __launch_bounds__(HALF_WAVES * 64)
 void half_transform_kernel(const double* __restrict__ g, const double* __restrict__ C,
-                           double* __restrict__ T2, int N, int M, int nst, int nkc, long nslabs, int sym,
+                           double* __restrict__ T2, int N, int M, long nslabs, int sym,
                            double* __restrict__ Vk)
 {
-    // Vk (NST > 0, sym == SYM_MIRROR only; else null): the first product of every slab p <= q as well,
+    static_assert(NST > 0, "N > 48 goes through half_stream_kernel");
+    // Vk (sym == SYM_MIRROR only; else null): the first product of every slab p <= q as well,
     // Vk[tri(p,q)][s][y] = sum_r g[p,q,r,s] C[r,y] -- the quarter-transformed integrals the K-type
     // (exchange) blocks of the orbital Hessian start from (hessian.hip), from the same read of the slab
-    constexpr int LDM = 16 * (ZT | 1);
-    extern __shared__ double lds[];
-    const int RT16 = nst * 16;
-    double* Cl = lds;   // [RT16][LDM], zero padded
-
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lq = lane >> 4, lr = lane & 15;
     // blockIdx.y = geometry of a batch (stacked g_ao [G][N^4], C [G][N^2], T2 [G][N^2 M^2] or the
@@ -112,7 +106,7 @@ void half_transform_kernel(const double* __restrict__ g, const double* __restric
     T2 += (size_t)blockIdx.y * (sym == SYM_PACKED ? (size_t)nslabs : (size_t)N * N) * M * M;
     if (Vk) Vk += (size_t)blockIdx.y * (size_t)nslabs * N * M;
 
-    // (NST > 0: the waves are independent, the host picks the workgroup size: four waves, so that three
+    // (the waves are independent, the host picks the workgroup size: four waves, so that three
     // workgroups = all 12 waves the 158 registers allow are resident on a CU instead of one workgroup of 8)
     const long slab = (long)blockIdx.x * (blockDim.x >> 6) + wave;
     const bool have = slab < nslabs;
@@ -139,180 +133,96 @@ void half_transform_kernel(const double* __restrict__ g, const double* __restric
 #pragma unroll
     for (int y = 0; y < ZT; ++y) xt[y] = d4{0.0, 0.0, 0.0, 0.0};
 
-    // one column tile st (s = st*16 + lr), k-steps kc*KCH .. +KCH-1 over r.  Loads are
-    // unconditional on clamped addresses, masked by a select: no branches between them.
-    auto load_chunk = [&](int st, int kc, double* dst) {
-        const int col = st * 16 + lr;
-        const int colc = col < N ? col : N - 1;
-        const int r0 = kc * KCH * 4 + lq;
+    // No LDS, no barrier.  Each lane fetches its own C fragments straight from L2
+    // (cfr[j][y] = C[4j + lq][16y + lr]), then the whole slab; all loads of the wave are in
+    // flight together and every wave runs independently of the others.
+    //
+    // Column tiles come in PAIRS: a pair covers 32 consecutive columns, lane lr loads the two
+    // adjacent columns (2lr, 2lr+1) of row 4i+lq with ONE 16-byte load (8-byte loads reach
+    // only ~0.55x of the per-CU HBM rate); .x feeds the "even" tile, .y the "odd" tile, whose
+    // MFMA row index m = lr therefore stands for column c0 + 2lr (+1).  An odd last tile is a
+    // single 16-column tile on 8-byte loads.
+    if (!have) return;
+    constexpr int NP = NST / 2, NS1 = NST % 2;
+    constexpr int NROW = NST * 16;                 // rows of C touched by stage 2
+    constexpr int NCF = NROW / 4;
+    static_assert(KCH <= NCF, "C fragments must cover every k-step");
+    double cfr[NCF][ZT];
+#pragma unroll
+    for (int j = 0; j < NCF; ++j)
+#pragma unroll
+        for (int y = 0; y < ZT; ++y) {
+            const int r = 4 * j + lq, z = 16 * y + lr;
+            cfr[j][y] = C[(size_t)(r < N ? r : N - 1) * N + (z < M ? z : M - 1)];
+        }
+    d2u apair[NP > 0 ? NP : 1][KCH];
+    double asing[KCH];
+#pragma unroll
+    for (int pp = 0; pp < NP; ++pp) {
+        const int col = pp * 32 + 2 * lr;
+        const int colc = col + 1 < N ? col : (N >= 2 ? N - 2 : 0);
 #pragma unroll
         for (int i = 0; i < KCH; ++i) {
-            const int r = r0 + 4 * i;
-            const int rc = r < N ? r : N - 1;
-            const double v = gs[(size_t)rc * N + colc];
-            // multiplicative mask (the clamped load is always finite): a select here is turned
-            // back into a branch around the load by the compiler, serialising the loads
-            dst[i] = v * ((have && col < N && r < N) ? 1.0 : 0.0);
+            const int r = 4 * i + lq;
+            apair[pp][i] = *reinterpret_cast<const d2u*>(gs + (size_t)(r < N ? r : N - 1) * N + colc);
         }
-    };
-    // Rows of Cl beyond N are zero and masked A values are zero, so every k-step can be executed
-    // unconditionally (straight-line MFMA stream, C fragments read ahead).
-    auto compute_chunk = [&](int st, int kc, const double* a) {
-        const double* cb = Cl + (size_t)(kc * KCH * 4 + lq) * LDM + lr;
-        double cf[KCH][ZT];
+    }
+    if constexpr (NS1) {
+        const int col = NP * 32 + lr;
+        const int colc = col < N ? col : N - 1;
 #pragma unroll
-        for (int i = 0; i < KCH; ++i)
+        for (int i = 0; i < KCH; ++i) {
+            const int r = 4 * i + lq;
+            asing[i] = gs[(size_t)(r < N ? r : N - 1) * N + colc];
+        }
+    }
+    // stage 2 needs C rows in the order of the MFMA row index of each tile:
+    //   even tile of pair pp: row m = lq + 4i  <->  column pp*32 + 2(lq+4i)
+    //   odd  tile of pair pp:                       column pp*32 + 2(lq+4i) + 1
+    //   single tile         :                       column NP*32 + lq + 4i  (= cfr[NP*8 + i])
+    double cpr[NP > 0 ? NP : 1][2][4][ZT];
 #pragma unroll
-            for (int y = 0; y < ZT; ++y) cf[i][y] = cb[i * 4 * LDM + y * 16];
+    for (int pp = 0; pp < NP; ++pp)
 #pragma unroll
-        for (int i = 0; i < KCH; ++i)
-#pragma unroll
-            for (int y = 0; y < ZT; ++y) xt[y] = mfma_f64(a[i], cf[i][y], xt[y]);
-        if (kc == nkc - 1) {
-            const double* ca = Cl + (size_t)(st * 16 + lq) * LDM + lr;
-            double af[4][ZT];
+        for (int half = 0; half < 2; ++half)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int z = 0; z < ZT; ++z) af[i][z] = ca[i * 4 * LDM + z * 16];
+                for (int z = 0; z < ZT; ++z) {
+                    const int col = pp * 32 + 2 * (lq + 4 * i) + half, zz = 16 * z + lr;
+                    cpr[pp][half][i][z] =
+                        C[(size_t)(col < N ? col : N - 1) * N + (zz < M ? zz : M - 1)];
+                }
+    __builtin_amdgcn_sched_barrier(0);
+    // masks (multiplicative: a select would be turned back into a branch around the load)
+#pragma unroll
+    for (int j = 0; j < NCF; ++j)
+#pragma unroll
+        for (int y = 0; y < ZT; ++y)
+            cfr[j][y] *= ((4 * j + lq) < N && (16 * y + lr) < M) ? 1.0 : 0.0;
+#pragma unroll
+    for (int pp = 0; pp < NP; ++pp)
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int z = 0; z < ZT; ++z)
+                    cpr[pp][half][i][z] *= ((pp * 32 + 2 * (lq + 4 * i) + half) < N &&
+                                            (16 * z + lr) < M) ? 1.0 : 0.0;
 #pragma unroll
-                    for (int y = 0; y < ZT; ++y) jt[z][y] = mfma_f64(af[i][z], xt[y][i], jt[z][y]);
+    for (int pp = 0; pp < NP; ++pp) {
+        const int c0 = pp * 32 + 2 * lr;
 #pragma unroll
-            for (int y = 0; y < ZT; ++y) xt[y] = d4{0.0, 0.0, 0.0, 0.0};
-        }
-    };
-    auto stage_C = [&]() {
-        for (int idx = tid; idx < RT16 * LDM; idx += HALF_WAVES * 64) {
-            const int r = idx / LDM, z = idx - r * LDM;
-            Cl[idx] = (r < N && z < M) ? C[(size_t)r * N + z] : 0.0;
-        }
-        __syncthreads();
-    };
-
-    if constexpr (NST > 0) {
-        // Small N: no LDS, no barrier.  Each lane fetches its own C fragments straight from L2
-        // (cfr[j][y] = C[4j + lq][16y + lr]), then the whole slab; all loads of the wave are in
-        // flight together and every wave runs independently of the others.
-        //
-        // Column tiles come in PAIRS: a pair covers 32 consecutive columns, lane lr loads the two
-        // adjacent columns (2lr, 2lr+1) of row 4i+lq with ONE 16-byte load (8-byte loads reach
-        // only ~0.55x of the per-CU HBM rate); .x feeds the "even" tile, .y the "odd" tile, whose
-        // MFMA row index m = lr therefore stands for column c0 + 2lr (+1).  An odd last tile is a
-        // single 16-column tile on 8-byte loads.
-        if (!have) return;
-        constexpr int NP = NST / 2, NS1 = NST % 2;
-        constexpr int NROW = NST * 16;                 // rows of C touched by stage 2
-        constexpr int NCF = NROW / 4;
-        static_assert(KCH <= NCF, "C fragments must cover every k-step");
-        double cfr[NCF][ZT];
-#pragma unroll
-        for (int j = 0; j < NCF; ++j)
-#pragma unroll
-            for (int y = 0; y < ZT; ++y) {
-                const int r = 4 * j + lq, z = 16 * y + lr;
-                cfr[j][y] = C[(size_t)(r < N ? r : N - 1) * N + (z < M ? z : M - 1)];
-            }
-        d2u apair[NP > 0 ? NP : 1][KCH];
-        double asing[KCH];
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-            const int col = pp * 32 + 2 * lr;
-            const int colc = col + 1 < N ? col : (N >= 2 ? N - 2 : 0);
+        for (int half = 0; half < 2; ++half) {
+            const double colok = (c0 + half < N) ? 1.0 : 0.0;
 #pragma unroll
             for (int i = 0; i < KCH; ++i) {
-                const int r = 4 * i + lq;
-                apair[pp][i] = *reinterpret_cast<const d2u*>(gs + (size_t)(r < N ? r : N - 1) * N + colc);
-            }
-        }
-        if constexpr (NS1) {
-            const int col = NP * 32 + lr;
-            const int colc = col < N ? col : N - 1;
-#pragma unroll
-            for (int i = 0; i < KCH; ++i) {
-                const int r = 4 * i + lq;
-                asing[i] = gs[(size_t)(r < N ? r : N - 1) * N + colc];
-            }
-        }
-        // stage 2 needs C rows in the order of the MFMA row index of each tile:
-        //   even tile of pair pp: row m = lq + 4i  <->  column pp*32 + 2(lq+4i)
-        //   odd  tile of pair pp:                       column pp*32 + 2(lq+4i) + 1
-        //   single tile         :                       column NP*32 + lq + 4i  (= cfr[NP*8 + i])
-        double cpr[NP > 0 ? NP : 1][2][4][ZT];
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int z = 0; z < ZT; ++z) {
-                        const int col = pp * 32 + 2 * (lq + 4 * i) + half, zz = 16 * z + lr;
-                        cpr[pp][half][i][z] =
-                            C[(size_t)(col < N ? col : N - 1) * N + (zz < M ? zz : M - 1)];
-                    }
-        __builtin_amdgcn_sched_barrier(0);
-        // masks (multiplicative: a select would be turned back into a branch around the load)
-#pragma unroll
-        for (int j = 0; j < NCF; ++j)
-#pragma unroll
-            for (int y = 0; y < ZT; ++y)
-                cfr[j][y] *= ((4 * j + lq) < N && (16 * y + lr) < M) ? 1.0 : 0.0;
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int z = 0; z < ZT; ++z)
-                        cpr[pp][half][i][z] *= ((pp * 32 + 2 * (lq + 4 * i) + half) < N &&
-                                                (16 * z + lr) < M) ? 1.0 : 0.0;
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-            const int c0 = pp * 32 + 2 * lr;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const double colok = (c0 + half < N) ? 1.0 : 0.0;
-#pragma unroll
-                for (int i = 0; i < KCH; ++i) {
-                    const double rowok = (4 * i + lq) < N ? colok : 0.0;
-                    // odd N: the lane whose even column is the LAST one (c0 == N-1) loaded the pair
-                    // (N-2, N-1), so its value sits in .y
-                    const double ev = (c0 == N - 1) ? apair[pp][i].y : apair[pp][i].x;
-                    const double av = (half == 0 ? ev : apair[pp][i].y) * rowok;
-#pragma unroll
-                    for (int y = 0; y < ZT; ++y) xt[y] = mfma_f64(av, cfr[i][y], xt[y]);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int z = 0; z < ZT; ++z) {
-                        const double cz = cpr[pp][half][i][z];
-#pragma unroll
-                        for (int y = 0; y < ZT; ++y) jt[z][y] = mfma_f64(cz, xt[y][i], jt[z][y]);
-                    }
-                if (Vk) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int sc = pp * 32 + 2 * (lq + 4 * i) + half;      // column of this row of the tile
-#pragma unroll
-                        for (int y = 0; y < ZT; ++y)
-                            if (sc < N && 16 * y + lr < M) Vk[((size_t)slab * N + sc) * M + 16 * y + lr] = xt[y][i];
-                    }
-                }
-#pragma unroll
-                for (int y = 0; y < ZT; ++y) xt[y] = d4{0.0, 0.0, 0.0, 0.0};
-            }
-        }
-        if constexpr (NS1) {
-            const double colok = (NP * 32 + lr) < N ? 1.0 : 0.0;
-#pragma unroll
-            for (int i = 0; i < KCH; ++i) {
-                const double av = asing[i] * ((4 * i + lq) < N ? colok : 0.0);
+                const double rowok = (4 * i + lq) < N ? colok : 0.0;
+                // odd N: the lane whose even column is the LAST one (c0 == N-1) loaded the pair
+                // (N-2, N-1), so its value sits in .y
+                const double ev = (c0 == N - 1) ? apair[pp][i].y : apair[pp][i].x;
+                const double av = (half == 0 ? ev : apair[pp][i].y) * rowok;
 #pragma unroll
                 for (int y = 0; y < ZT; ++y) xt[y] = mfma_f64(av, cfr[i][y], xt[y]);
             }
@@ -320,33 +230,48 @@ void half_transform_kernel(const double* __restrict__ g, const double* __restric
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int z = 0; z < ZT; ++z) {
-                    // column NP*32 + lq + 4i = row (NP*8 + i)*4 + lq of C: an existing fragment
-                    const double cz = cfr[NP * 8 + i][z];
+                    const double cz = cpr[pp][half][i][z];
 #pragma unroll
                     for (int y = 0; y < ZT; ++y) jt[z][y] = mfma_f64(cz, xt[y][i], jt[z][y]);
                 }
             if (Vk) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int sc = NP * 32 + lq + 4 * i;
+                    const int sc = pp * 32 + 2 * (lq + 4 * i) + half;      // column of this row of the tile
 #pragma unroll
                     for (int y = 0; y < ZT; ++y)
                         if (sc < N && 16 * y + lr < M) Vk[((size_t)slab * N + sc) * M + 16 * y + lr] = xt[y][i];
                 }
             }
-        }
-    } else {
-        // chunk c = st * nkc + kc
-        const int nchunks = nst * nkc;
-        double acur[KCH], anext[KCH];
-        load_chunk(0, 0, acur);
-        stage_C();
-        if (!have) return;
-        for (int c = 0; c < nchunks; ++c) {
-            if (c + 1 < nchunks) load_chunk((c + 1) / nkc, (c + 1) % nkc, anext);
-            compute_chunk(c / nkc, c % nkc, acur);
 #pragma unroll
-            for (int i = 0; i < KCH; ++i) acur[i] = anext[i];
+            for (int y = 0; y < ZT; ++y) xt[y] = d4{0.0, 0.0, 0.0, 0.0};
+        }
+    }
+    if constexpr (NS1) {
+        const double colok = (NP * 32 + lr) < N ? 1.0 : 0.0;
+#pragma unroll
+        for (int i = 0; i < KCH; ++i) {
+            const double av = asing[i] * ((4 * i + lq) < N ? colok : 0.0);
+#pragma unroll
+            for (int y = 0; y < ZT; ++y) xt[y] = mfma_f64(av, cfr[i][y], xt[y]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int z = 0; z < ZT; ++z) {
+                // column NP*32 + lq + 4i = row (NP*8 + i)*4 + lq of C: an existing fragment
+                const double cz = cfr[NP * 8 + i][z];
+#pragma unroll
+                for (int y = 0; y < ZT; ++y) jt[z][y] = mfma_f64(cz, xt[y][i], jt[z][y]);
+            }
+        if (Vk) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int sc = NP * 32 + lq + 4 * i;
+#pragma unroll
+                for (int y = 0; y < ZT; ++y)
+                    if (sc < N && 16 * y + lr < M) Vk[((size_t)slab * N + sc) * M + 16 * y + lr] = xt[y][i];
+            }
         }
     }
 
@@ -943,7 +868,7 @@ void sym_gm_kernel(const double* __restrict__ J, const double* __restrict__ C,
             af[ks] = __builtin_bit_cast(double, v);
         }
         // PB rows of the wave at a time: PB * KS loads of a lane in flight, then their MFMA chains
-        constexpr int PB = WPE >= 6 ? 1 : WPE >= 4 ? 2 : PW;
+        constexpr int PB = WPE >= 4 ? 2 : PW;
 #pragma unroll
         for (int h = 0; h < PW; h += PB) {
             double bf[PB][KS];
@@ -1408,7 +1333,7 @@ void half_transform_fused_kernel(const double* __restrict__ g, const double* __r
     }
 }
 
-// Packed copy of p <-> q and r <-> s symmetric integrals for half_tri_kernel<.,.,2>: slab t = (p <= q)
+// Packed copy of p <-> q and r <-> s symmetric integrals for half_tri_reg_kernel: slab t = (p <= q)
 // of the triangle; of each slab only the upper triangle, row r holding its columns (r & ~1) .. N-1
 // (an even start keeps the 16-byte column-pair loads inside the row; the element left of the
 // diagonal in an odd row is stored as 0) and the DIAGONAL HALVED, so that the slab product needs no
@@ -1422,7 +1347,7 @@ __device__ __host__ inline unsigned eri_tri_row_start(int r, int N)
 }
 
 // Pitch of a packed slab in doubles: the triangle rounded up to an even count, so that every slab
-// (and every LDS slot it is copied to by 16-byte DMA lanes) starts on a 16-byte boundary.
+// (and every LDS slot it is copied to in 16-byte pieces) starts on a 16-byte boundary.
 __device__ __host__ inline unsigned eri_slab_pitch(int N) { return (eri_tri_row_start(N, N) + 1u) & ~1u; }
 
 __global__ __launch_bounds__(256)
@@ -1559,15 +1484,12 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
     double* dump = lds;             // [64] sink for lanes outside the M x M tile
     int* ctab = reinterpret_cast<int*>(lds + 64);   // [ncol <= 256] column -> position y*M + z in a tile
     double* stg = lds + 64 + 128;   // [phase_rounds][NWV][M2]
-    // RS == 2: g is the PACKED copy made by eri_pack_kernel: per slab t = (p <= q) the upper triangle
-    // with the diagonal halved, row r = its columns (r & ~1) .. N-1, rows back to back
-    constexpr bool rs = RS != 0, pk = RS == 2;
-    const unsigned slab_pk = (unsigned)(eri_slab_pitch(N) * sizeof(double));
+    constexpr bool rs = RS != 0;
 #if defined(OOVQE_TRI_PROBE) && OOVQE_TRI_PROBE == 2
     // tools/tri_spread.hip: every geometry reads geometry 0's integrals (cache-resident): the kernel
     // without its HBM stream
 #else
-    g += (size_t)blockIdx.y * (pk ? (size_t)tri * (slab_pk / sizeof(double)) : slab_elems * slab_elems);
+    g += (size_t)blockIdx.y * slab_elems * slab_elems;
 #endif
     C += (size_t)blockIdx.y * N * N;
     // tiled == 0: J[t][M2].  tiled == 1: J[ty][t][16], 16-wide tiles of the M2 (y z) columns
@@ -1586,58 +1508,30 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
     // lower block get an out-of-range offset: no traffic), the MFMA chain forms
     // T = C^T (L + D/2) C, and the burst writes J = T + T^T.  For N = 43: 67 % of the slab.
     // (RS != 0 goes with tiled == 2; a template parameter: the k-steps of lower blocks vanish at
-    // compile time.  RS == 1 reads the full layout, where the rows keep their 8 N-byte pitch and
-    // the skipped parts mostly share cache lines with the loaded ones: 7 % faster only; RS == 2
-    // streams the packed copy.)
-    // (the packed copy carries the weights itself: halved diagonal, nothing below it)
-    constexpr bool wts = rs && !pk;
-    const double wA_lo = wts ? 0.5 : 1.0, wB_lo = wts ? 0.0 : 1.0, wB_hi = wts ? 0.5 : 1.0, wD = wts ? 0.5 : 1.0;
+    // compile time.  The rows keep their 8 N-byte pitch and the skipped parts mostly share cache
+    // lines with the loaded ones: 7 % faster only; half_tri_reg_kernel streams the packed copy.)
+    const double wA_lo = rs ? 0.5 : 1.0, wB_lo = rs ? 0.0 : 1.0, wB_hi = rs ? 0.5 : 1.0, wD = rs ? 0.5 : 1.0;
 
     // Byte offsets inside a slab (see half_transform_fused_kernel): a per-lane part (VGPR) and a
     // wave-uniform part per k-step (SGPR).  Lanes that must not load (row >= N in the last k-step,
     // columns below the diagonal with rs) get an out-of-range offset: dropped, no traffic.
-    //   full layout: row r = 4i + lq starts r * N doubles into the slab;
-    //   packed     : row r starts 2k(N-k+1) + (r&1)(N-2k), k = r/2, and holds the columns >= (r & ~1);
-    //                with r = 4i + lq, element (r, c) sits at  (4iN - 8i^2)  [uniform]
-    //                + (2hN - 2h^2 + bN - 2hb) + c  [lane; h = lq>>1, b = lq&1]  - 4 i lq  [lane step per
-    //                k-step]; the row's first column is r & ~1 = 4i + 2h.
+    // Row r = 4i + lq starts r * N doubles into the slab.
     constexpr int MINK = KCH == 4 ? 1 : KCH == 8 ? 5 : KCH == 11 ? 9 : KCH;
     const int i_last = (N - 1) / 4;
-    const unsigned slab_bytes = pk ? slab_pk : (unsigned)(slab_elems * sizeof(double));
-    const unsigned total_bytes = pk ? (unsigned)(tri * slab_pk) : (unsigned)(slab_elems * slab_elems * sizeof(double));
+    const unsigned slab_bytes = (unsigned)(slab_elems * sizeof(double));
+    const unsigned total_bytes = (unsigned)(slab_elems * slab_elems * sizeof(double));
     const bool row_ok_last = 4 * i_last + lq < N;
-    const int h2 = lq >> 1, b2l = lq & 1;
-    const int lane_row = pk ? 2 * h2 * N - 2 * h2 * h2 + b2l * N - 2 * h2 * b2l : lq * N;
-    const unsigned lstep = pk ? (unsigned)(4 * lq * sizeof(double)) : 0u;   // subtracted once per k-step
-    unsigned offp[NPA][2];              // pair pp: [0] rows of blocks <= 2pp, [1] rows of block 2pp+1 (full layout)
-    int colp[NPA];
+    const int lane_row = lq * N;
+    unsigned offp[NPA][2];              // pair pp: [0] rows of blocks <= 2pp, [1] rows of block 2pp+1
     bool last_even[NPA];
-    // Packed copy: the two operands of pair pp are the columns of its first block (32 pp + lr, in .x)
-    // and of its second block (32 pp + 16 + lr, in .y), one 8-byte load each: the first block's columns
-    // only have rows up to their own block, so its products stop there (the column-pair form of the
-    // full layout, .x = even and .y = odd columns from one 16-byte load, runs both over both blocks).
-    int colh[NPA][2];
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) {
-        if constexpr (pk) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int col = pp * 32 + 16 * h + lr;
-                colh[pp][h] = col;
-                offp[pp][h] = (unsigned)((lane_row + (col < N ? col : N - 1)) * (int)sizeof(double));
-            }
-            colp[pp] = colh[pp][0];
-            last_even[pp] = false;
-        } else {
-            const int col = pp * 32 + 2 * lr;
-            // the last column of an odd N: the pair (N-2, N-1) is loaded and .y taken
-            const int cc = col + 1 < N ? col : (N >= 2 ? N - 2 : 0);
-            colp[pp] = col;
-            colh[pp][0] = colh[pp][1] = col;
-            offp[pp][0] = (unsigned)((lane_row + cc) * (int)sizeof(double));
-            offp[pp][1] = (wts && lr < 8) ? total_bytes : offp[pp][0];   // first block's columns below the diagonal
-            last_even[pp] = col == N - 1;
-        }
+        const int col = pp * 32 + 2 * lr;
+        // the last column of an odd N: the pair (N-2, N-1) is loaded and .y taken
+        const int cc = col + 1 < N ? col : (N >= 2 ? N - 2 : 0);
+        offp[pp][0] = (unsigned)((lane_row + cc) * (int)sizeof(double));
+        offp[pp][1] = (rs && lr < 8) ? total_bytes : offp[pp][0];   // first block's columns below the diagonal
+        last_even[pp] = col == N - 1;
     }
     const int col1 = NP * 32 + lr;
     const int col1c = col1 < N ? col1 : N - 1;
@@ -1648,14 +1542,13 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
         const_cast<double*>(g), 0, (int)total_bytes, 0x00020000);
     // scalar part of k-step i; k-steps past the last row are dropped
     auto soff = [&](unsigned sb, int i) -> unsigned {
-        const unsigned o = pk ? sb + (unsigned)((4 * i * N - 8 * i * i) * (int)sizeof(double))
-                              : sb + (unsigned)(4 * i * N * sizeof(double));
+        const unsigned o = sb + (unsigned)(4 * i * N * sizeof(double));
         return (i < MINK || i <= i_last) ? o : total_bytes;
     };
-    // lane part of k-step i for a lane whose (first) column is col
-    auto voff = [&](unsigned vo, int col, int i) -> unsigned {
-        const bool drop = (i >= MINK - 1 && i == i_last && !row_ok_last) || (pk && col < 4 * i + 2 * h2);
-        return drop ? total_bytes : vo - (unsigned)i * lstep;
+    // lane part of k-step i
+    auto voff = [&](unsigned vo, int i) -> unsigned {
+        const bool drop = i >= MINK - 1 && i == i_last && !row_ok_last;
+        return drop ? total_bytes : vo;
     };
 
     const int SW = gridDim.x * NWV;                  // waves per geometry
@@ -1664,7 +1557,6 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
     // round r of this wave: slab t = r*SW + gw of the triangle; past the end -> dropped loads
     auto slab_off = [&](int r) -> unsigned {
         const long t = (long)r * SW + gw;
-        if (pk) return __builtin_amdgcn_readfirstlane(t < tri ? (unsigned)t * slab_bytes : total_bytes);
         int p, q;
         tri_decode(t < tri ? t : 0, N, p, q);
         return __builtin_amdgcn_readfirstlane(t < tri ? (unsigned)(p * N + q) * slab_bytes : total_bytes);
@@ -1688,24 +1580,15 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
             for (int i = 0; i < KCH; ++i) {
                 const int blk = i / 4;                 // 16-row block of this k-step (compile time)
                 if (rs && blk > 2 * pp + 1) continue;  // rows below both blocks of the pair: lower blocks
-                if constexpr (pk) {
-                    if (blk <= 2 * pp) {
-                        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff(offp[pp][0], colh[pp][0], i), soff(sb, i), AUX_NT);
-                        ap[pp][i].x = __builtin_bit_cast(double, v);
-                    }
-                    const v2u w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff(offp[pp][1], colh[pp][1], i), soff(sb, i), AUX_NT);
-                    ap[pp][i].y = __builtin_bit_cast(double, w);
-                    continue;
-                }
                 // (row blocks above the pair, blk < 2pp, only exist for NST > 3: not instantiated)
                 const unsigned vo = offp[pp][blk == 2 * pp + 1 ? 1 : 0];
-                const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff(vo, colp[pp], i), soff(sb, i), rs ? AUX_NT : AUX_PLAIN);
+                const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff(vo, i), soff(sb, i), rs ? AUX_NT : AUX_PLAIN);
                 ap[pp][i] = __builtin_bit_cast(d2u, v);
             }
         if constexpr (NS1) {
 #pragma unroll
             for (int i = 0; i < KCH; ++i) {
-                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff(offs, col1c, i), soff(sb, i), rs ? AUX_NT : AUX_PLAIN);
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff(offs, i), soff(sb, i), rs ? AUX_NT : AUX_PLAIN);
                 as[i] = __builtin_bit_cast(double, v);
             }
         }
@@ -1728,7 +1611,7 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
         for (int half = 0; half < 2; ++half)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int col = pk ? pp * 32 + 16 * half + lq + 4 * i : pp * 32 + 2 * (lq + 4 * i) + half;
+                const int col = pp * 32 + 2 * (lq + 4 * i) + half;
                 cpr[pp][half][i] = C[(size_t)(col < N ? col : N - 1) * N + (lr < M ? lr : M - 1)];
             }
 #pragma unroll
@@ -1739,7 +1622,7 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
         for (int half = 0; half < 2; ++half)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                cpr[pp][half][i] *= ((pk ? pp * 32 + 16 * half + lq + 4 * i : pp * 32 + 2 * (lq + 4 * i) + half) < N && lr < M) ? 1.0 : 0.0;
+                cpr[pp][half][i] *= ((pp * 32 + 2 * (lq + 4 * i) + half) < N && lr < M) ? 1.0 : 0.0;
 
     // LDS destination of jt[i] = Jt[z = lq + 4i][y = lr] inside a staged tile: [y*M + z]
     int tile_off[4];
@@ -1750,42 +1633,6 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
     }
     auto compute = [&](int r, int base, const d2u (&ap)[NPA][KCH], const double (&as)[KCH]) {
         d4 jt = d4{0.0, 0.0, 0.0, 0.0};
-        if constexpr (pk) {
-            // The packed copy carries its weights (halved diagonal): every first product is ONE
-            // accumulator chain, its result goes to the second product as it leaves the MFMA pipe.
-            // No VALU instruction in between: on gfx950 a VALU instruction does not run in the shadow
-            // of a v_mfma_f64 (tools/mfma_dep_probe.hip: 8 cycles of the pipe each).
-            d4 xs = d4{0.0, 0.0, 0.0, 0.0};
-            if constexpr (NS1) {
-#pragma unroll
-                for (int i = 0; i < KCH; ++i) xs = mfma_f64(as[i], cfr[i], xs);
-            }
-            d4 xh[NPA][2];
-#pragma unroll
-            for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    d4 x = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int i = 0; i < KCH; ++i) {
-                        if (i / 4 > 2 * pp + half) continue;   // rows below the block of these columns
-                        x = mfma_f64(half == 0 ? ap[pp][i].x : ap[pp][i].y, cfr[i], x);
-                    }
-                    xh[pp][half] = x;
-                }
-            if constexpr (NS1) {
-                // columns of the last tile that exist for this KCH (rows and columns share the k-steps)
-                constexpr int KS1 = KCH - NP * 8 < 4 ? KCH - NP * 8 : 4;
-#pragma unroll
-                for (int i = 0; i < KS1; ++i) jt = mfma_f64(cfr[NP * 8 + i], xs[i], jt);
-            }
-#pragma unroll
-            for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-                for (int half = 0; half < 2; ++half)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) jt = mfma_f64(cpr[pp][half][i], xh[pp][half][i], jt);
-        } else {
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp)
 #pragma unroll
@@ -1823,7 +1670,6 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
             for (int e = 0; e < 4; ++e) xt[e] = xu[e] + wD * xd[e];
 #pragma unroll
             for (int i = 0; i < 4; ++i) jt = mfma_f64(cfr[NP * 8 + i], xt[i], jt);
-        }
         }
         if ((long)r * SW + gw >= tri) return;          // padding round
         double* row = stg + ((size_t)(r - base) * NWV + wave) * M2;
@@ -1888,255 +1734,6 @@ void half_tri_kernel(const double* __restrict__ g, const double* __restrict__ C,
 #endif
 }
 
-// ------------------------------------------------------------------------------------------
-// Stage 1 on the packed copy (both symmetries), slabs delivered by LDS-DMA.
-//
-// Same arithmetic and the same staging / burst of the results as half_tri_kernel<KCH,NST,2>; what
-// changes is how a slab reaches the matrix cores.  There every lane fetches its MFMA operands
-// straight from HBM: 8- and 16-byte pieces of ragged triangle rows, most of them straddling
-// 128-byte lines, a third of the lanes masked off, and two slabs of operand registers per wave
-// (234 VGPRs) to keep bytes in flight -- 4.7 TB/s where whole contiguous slabs stream at 5.7.
-// Here a wave copies its packed slab (7.7 KB at N = 43, contiguous) into a private LDS slot with
-// `global_load_lds_dwordx4` -- full 1 KB pieces, 16 bytes per lane, line-aligned, nothing masked
-// but the tail of the last piece, no VGPR destination -- two slots per wave, so the slab after
-// next is requested as soon as this one's operands have been read out of LDS into registers.
-// The fragment reads then happen on chip (ds_read with the triangle's row offsets, zero for the
-// positions below the diagonal) and cost ~60 LDS cycles per slab against the ~1000 cycles a CU
-// has per slab at the HBM-bound pace.  Ordering: only the issuing wave reads its slots, so its
-// own counted `s_waitcnt vmcnt` is the whole protocol (MI355X_MICROARCH.md, co-residence item 7);
-// the burst's barriers are raw `s_barrier`s that leave the DMAs in flight.
-// ------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void oovqe_lds_void;
-typedef const __attribute__((address_space(1))) void oovqe_glob_void;
-
-template <int KCH, int NST>
-__global__ __launch_bounds__(HALF_WAVES * 64)
-void half_tri_dma_kernel(const double* __restrict__ g, const double* __restrict__ C,
-                         double* __restrict__ J, int N, int M, int phase_rounds)
-{
-    constexpr int NP = NST / 2, NS1 = NST % 2;
-    constexpr int NPA = NP > 0 ? NP : 1;
-    constexpr int NCF = NST * 4;
-    static_assert(KCH <= NCF, "C fragments must cover every k-step");
-    static_assert(NP <= 1, "row blocks above a pair are not handled by the offsets below");
-    extern __shared__ double lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lq = lane >> 4, lr = lane & 15;
-    const int M2 = M * M;
-    const long tri = (long)N * (N + 1) / 2;
-    const unsigned slab_d = eri_slab_pitch(N);                       // doubles per packed slab (even)
-    const unsigned slab_bytes = slab_d * (unsigned)sizeof(double);
-    const int npiece = (int)((slab_bytes + 1023u) / 1024u);          // 1 KB DMA pieces per slab
-    double* dump = lds;             // [64] sink for lanes outside the M x M tile
-    int* ctab = reinterpret_cast<int*>(lds + 64);   // [ncol <= 256] column -> position y*M + z in a tile
-    const unsigned slot_d = slab_d + 2;                              // + a zero word the DMA never writes
-    double* ring = lds + 64 + 128;  // [HALF_WAVES][2][slot_d]: two slots per wave
-    double* stg = ring + (size_t)HALF_WAVES * 2 * slot_d;   // [phase_rounds][HALF_WAVES][M2]
-    g += (size_t)blockIdx.y * (size_t)tri * slab_d;
-    C += (size_t)blockIdx.y * N * N;
-    const int ncol = M * (M + 1) / 2;                                // columns y <= z of J
-    const int nty = (ncol + 15) / 16;
-    J += (size_t)blockIdx.y * tri * nty * 16;                        // J[ty][t][16]
-    if (tid < ncol) {               // read after the first barrier of the phase loop
-        int y, z;
-        tri_decode(tid, M, y, z);
-        ctab[tid] = (y * M + z) | ((z * M + y) << 16);
-    }
-
-    const int SW = gridDim.x * HALF_WAVES;                  // waves per geometry
-    const int gw = blockIdx.x * HALF_WAVES + wave;
-    const int n_rounds = (int)((tri + SW - 1) / SW);        // the same for every wave of the grid
-    const int my_rounds = gw < tri ? (int)((tri - 1 - gw) / SW) + 1 : 0;   // rounds with a slab for this wave
-    double* my_ring = ring + (size_t)wave * 2 * slot_d;
-    if (lane < 2) my_ring[(size_t)lane * slot_d + slab_d] = 0.0;
-    // round r of this wave: slab t = r*SW + gw, into slot r & 1
-    auto dma = [&](int r) {
-        const char* src = reinterpret_cast<const char*>(g + ((size_t)r * SW + gw) * slab_d) + lane * 16;
-        char* dst = reinterpret_cast<char*>(my_ring + (size_t)(r & 1) * slot_d);
-        for (int p = 0; p < npiece; ++p) {
-            if ((unsigned)(p * 1024 + lane * 16) < slab_bytes)
-                __builtin_amdgcn_global_load_lds((oovqe_glob_void*)(src + p * 1024),
-                                                 (oovqe_lds_void*)(dst + p * 1024), 16, 0, AUX_NT);
-        }
-    };
-    if (my_rounds > 0) dma(0);
-    if (my_rounds > 1) dma(1);
-
-    // Offsets (in doubles) of this lane's operands inside a packed slab: row r = 4i + lq starts
-    // 2k(N-k+1) + (r&1)(N-2k) doubles in, k = r/2, and holds the columns (r & ~1) .. N-1.
-    // A position below the diagonal (or a row past N) reads as zero.
-    // (elements outside the stored triangle point at the zero word behind the slot; pair pp = the
-    // columns of its first block, k-steps of that block's rows only, and of its second block: see
-    // half_tri_reg_kernel)
-    const int zoff = (int)slab_d;
-    int offp[NPA][2][KCH < 8 ? KCH : 8];
-    int offs[KCH];
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int col = pp * 32 + 16 * h + lr;
-#pragma unroll
-            for (int i = 0; i < (KCH < 8 ? KCH : 8); ++i) {
-                const int r = 4 * i + lq, e = r & ~1;
-                offp[pp][h][i] = (r < N && col >= e && col < N) ? (int)eri_tri_row_start(r, N) + col - e : zoff;
-            }
-        }
-    {
-        const int col1 = NP * 32 + lr;
-#pragma unroll
-        for (int i = 0; i < KCH; ++i) {
-            const int r = 4 * i + lq, e = r & ~1;
-            offs[i] = (r < N && col1 < N && col1 >= e) ? (int)eri_tri_row_start(r, N) + col1 - e : zoff;
-        }
-    }
-
-    // C fragments: see half_transform_fused_kernel
-    double cfr[NCF];
-#pragma unroll
-    for (int j = 0; j < NCF; ++j) {
-        const int r = 4 * j + lq;
-        cfr[j] = C[(size_t)(r < N ? r : N - 1) * N + (lr < M ? lr : M - 1)];
-    }
-    double cpr[NPA][2][4];
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int col = pp * 32 + 16 * half + lq + 4 * i;
-                cpr[pp][half][i] = C[(size_t)(col < N ? col : N - 1) * N + (lr < M ? lr : M - 1)];
-            }
-#pragma unroll
-    for (int j = 0; j < NCF; ++j) cfr[j] *= ((4 * j + lq) < N && lr < M) ? 1.0 : 0.0;
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                cpr[pp][half][i] *= ((pp * 32 + 16 * half + lq + 4 * i) < N && lr < M) ? 1.0 : 0.0;
-
-    // LDS destination of jt[i] = Jt[z = lq + 4i][y = lr] inside a staged tile: [y*M + z]
-    int tile_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int zz = lq + 4 * i;
-        tile_off[i] = (lr < M && zz < M) ? lr * M + zz : -1;
-    }
-
-    double a0[NPA][4], a1[NPA][KCH < 8 ? KCH : 8];
-    double as[KCH];
-    // operands of the slab in slot `slot` out of LDS into registers (the slot is then free for the DMA
-    // of the slab two rounds ahead)
-    auto fetch = [&](int slot) {
-        const double* sl = my_ring + (size_t)slot * slot_d;
-        if constexpr (NS1) {
-#pragma unroll
-            for (int i = 0; i < KCH; ++i) as[i] = sl[offs[i]];
-        }
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-#pragma unroll
-            for (int i = 0; i < 4 && i < KCH; ++i) a0[pp][i] = sl[offp[pp][0][i]];
-#pragma unroll
-            for (int i = 0; i < (KCH < 8 ? KCH : 8); ++i) a1[pp][i] = sl[offp[pp][1][i]];
-        }
-    };
-    // every first product one accumulator chain, its result straight into the second product
-    auto compute = [&](int r, int base) {
-        d4 jt = d4{0.0, 0.0, 0.0, 0.0};
-        d4 xs = d4{0.0, 0.0, 0.0, 0.0};
-        if constexpr (NS1) {
-#pragma unroll
-            for (int i = 0; i < KCH; ++i) xs = mfma_f64(as[i], cfr[i], xs);
-        }
-        d4 xh[NPA][2];
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-            d4 x = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int i = 0; i < 4 && i < KCH; ++i) {
-                if (i / 4 > 2 * pp) continue;
-                x = mfma_f64(a0[pp][i], cfr[i], x);
-            }
-            xh[pp][0] = x;
-            x = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int i = 0; i < (KCH < 8 ? KCH : 8); ++i) {
-                if (i / 4 > 2 * pp + 1) continue;
-                x = mfma_f64(a1[pp][i], cfr[i], x);
-            }
-            xh[pp][1] = x;
-        }
-        if constexpr (NS1) {
-            constexpr int KS1 = KCH - NP * 8 < 4 ? KCH - NP * 8 : 4;
-#pragma unroll
-            for (int i = 0; i < KS1; ++i) jt = mfma_f64(cfr[NP * 8 + i], xs[i], jt);
-        }
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) jt = mfma_f64(cpr[pp][half][i], xh[pp][half][i], jt);
-        double* row = stg + ((size_t)(r - base) * HALF_WAVES + wave) * M2;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double* dst = tile_off[i] >= 0 ? row + tile_off[i] : dump + lane;
-            *dst = jt[i];
-        }
-    };
-
-    for (int base = 0; base < n_rounds; base += phase_rounds) {
-        const int end = base + phase_rounds < n_rounds ? base + phase_rounds : n_rounds;
-        for (int it = base; it < end; ++it) {
-            if (it < my_rounds) {                         // wave-uniform
-                // round `it` has landed once at most the pieces of round it+1 are outstanding
-                // (vector-memory operations retire in issue order; the burst's stores count too
-                // and only make this wait conservative)
-                if (it + 1 < my_rounds) {
-                    switch (npiece) {                     // wave-uniform; the count is an immediate
-                    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-                    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-                    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-                    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-                    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-                    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-                    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-                    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-                    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-                    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-                    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-                    }
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                fetch(it & 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // operands are in registers: the slot is free
-                __builtin_amdgcn_sched_barrier(0);
-                if (it + 2 < my_rounds) dma(it + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(it, base);
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        const int nslot = (end - base) * HALF_WAVES;
-        for (int e = tid; e < nslot * ncol; e += HALF_WAVES * 64) {
-            const int slot = e / ncol, c = e - slot * ncol;
-            const long t = (long)(base + slot / HALF_WAVES) * SW + blockIdx.x * HALF_WAVES + slot % HALF_WAVES;
-            if (t < tri) {
-                const int cc2 = ctab[c];
-                const double v = stg[(size_t)slot * M2 + (cc2 & 0xffff)] + stg[(size_t)slot * M2 + (cc2 >> 16)];
-                J[((size_t)(c >> 4) * tri + t) * 16 + (c & 15)] = v;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-}
-
 typedef __attribute__((address_space(3))) double lds_double_t;
 __device__ __forceinline__ unsigned lds_address(const double* p)     // p points into LDS
 {
@@ -2146,18 +1743,19 @@ __device__ __forceinline__ unsigned lds_address(const double* p)     // p points
 // ------------------------------------------------------------------------------------------
 // Stage 1 on the packed copy, slabs fetched as CONTIGUOUS 16-byte-per-lane register loads.
 //
-// The packed stream of half_tri_kernel<.,.,2> runs at 4.7 TB/s where whole slabs reach 5.7, and
-// neither the matrix cores nor the memory side is the reason: its operand-shaped loads leave a
-// third of the lanes masked, so the two slabs a wave keeps in flight occupy 132 VGPRs but carry
-// only 15 KB -- 124 KB per CU, against 236 KB for the whole-slab kernel (the LDS-DMA variant above
-// has the same cap: its in-flight bytes ARE its LDS ring).  Here a slab is fetched as it lies in
-// memory, NPC pieces of 1 KB per wave instruction, 4 VGPRs per piece: 32 VGPRs hold a 7.7 KB slab,
-// so a wave keeps R = 3 or 4 slabs in flight (186 / 247 KB per CU) in the register budget the old
-// kernel spends on two.  A landed slab is written to the wave's private LDS slot with
-// ds_write_b128, its registers are reloaded with the slab R rounds ahead, and the MFMA operands
-// are read back from LDS with the triangle's row offsets (zero below the diagonal) -- the same
-// fragment reads as half_tri_dma_kernel.  Straight-line rounds, unrolled R times, so the
-// compiler's vmcnt bookkeeping is exact; no barrier except around the result bursts.
+// g is the PACKED copy made by eri_pack_kernel: per slab t = (p <= q) the upper triangle with the
+// diagonal halved, row r = its columns (r & ~1) .. N-1, rows back to back.  Operand-shaped loads of
+// that stream (every lane fetching its own MFMA fragment) leave a third of the lanes masked and ran
+// at 4.7 TB/s where whole slabs reach 5.7 (retired realisations).  Here a slab is fetched
+// as it lies in memory, NPC pieces of 1 KB per wave instruction, 4 VGPRs per piece: 32 VGPRs hold a
+// 7.7 KB slab, so a wave keeps R = 3 slabs in flight (186 KB per CU).  A landed slab is written to
+// the wave's private LDS slot with ds_write_b128, its registers are reloaded with the slab R rounds
+// ahead, and the MFMA operands are read back from LDS with the triangle's row offsets (zero below
+// the diagonal).  The packed copy carries its weights, so every first product is ONE accumulator
+// chain whose result goes to the second product as it leaves the MFMA pipe, with no VALU
+// instruction in between: on gfx950 a VALU instruction does not run in the shadow of a v_mfma_f64
+// (tools/mfma_dep_probe.hip: 8 cycles of the pipe each).  Straight-line rounds, unrolled R times,
+// so the compiler's vmcnt bookkeeping is exact; no barrier except around the result bursts.
 // ------------------------------------------------------------------------------------------
 template <int KCH, int NST, int NPC, int R>
 __global__ __launch_bounds__(HALF_WAVES * 64)
@@ -2304,8 +1902,8 @@ void half_tri_reg_kernel(const double* __restrict__ g, const double* __restrict_
         __builtin_amdgcn_sched_barrier(0);
         load(r + R, b);
         __builtin_amdgcn_sched_barrier(0);
-        // every first product one accumulator chain, its result straight into the second product
-        // (half_tri_kernel<.,.,2>); operands read from the slot as they are needed
+        // every first product one accumulator chain, its result straight into the second product;
+        // operands read from the slot as they are needed
         d4 jt = d4{0.0, 0.0, 0.0, 0.0};
         d4 xs = d4{0.0, 0.0, 0.0, 0.0};
         if constexpr (NS1) {
@@ -3600,7 +3198,6 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
 static int half_transform_batched(const double* g_ao, const double* C, int N, int M, double* T2,
                                   int batch, oovqe_stream_t stream, int sym = SYM_FULL, bool rs = false,
                                   double* Vk_tri = nullptr, const double* g_tiles = nullptr);
-static int device_cu_count();
 
 extern "C" int oovqe_cas_half_transform(const double* g_ao, const double* C, int N, int M, double* T2,
                                         oovqe_stream_t stream)
@@ -3631,26 +3228,13 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
     const long nslabs = sym == SYM_FULL ? (long)N * N : (long)N * (N + 1) / 2;
     // k-steps per register chunk: the whole row when it fits (<= 16 k-steps), else chunks of 16
     int kch = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : ksteps <= 11 ? 11 : ksteps <= 12 ? 12 : 16;
-    const int nkc = (ksteps + kch - 1) / kch;
 #define OOVQE_LAUNCH_HALF(Z, KC_, NS_)                                                            \
     do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        if (!attr_done) {                                                                         \
-            hipError_t e = hipFuncSetAttribute((const void*)half_transform_kernel<Z, KC_, NS_>,   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                               160 * 1024);                                       \
-            if (e != hipSuccess) {                                                                \
-                oovqe_set_error("cas_half_transform: hipFuncSetAttribute: %s",                    \
-                                hipGetErrorString(e));                                            \
-                return OOVQE_ERR_HIP;                                                             \
-            }                                                                                     \
-            attr_done = true;                                                                     \
-        }                                                                                         \
         oovqe_note_stage1("half_transform_kernel<%d,%d,%d>%s", Z, KC_, NS_, sym ? " (slabs p <= q)" : ""); \
-        const unsigned wpg = (NS_) > 0 ? 4u : (unsigned)HALF_WAVES;       /* waves per workgroup */      \
+        const unsigned wpg = 4u;                                          /* waves per workgroup */      \
         hipLaunchKernelGGL((half_transform_kernel<Z, KC_, NS_>),                                  \
                            dim3((unsigned)((nslabs + wpg - 1) / wpg), batch), dim3(wpg * 64),     \
-                           (NS_) > 0 ? 0 : lds_bytes, st, g_ao, C, T2, N, M, nrb, nkc, nslabs, sym, Vk_tri); \
+                           0, st, g_ao, C, T2, N, M, nslabs, sym, Vk_tri);                        \
     } while (0)
 #define OOVQE_DISPATCH_KCH(Z)                                                                     \
     do {                                                                                          \
@@ -3659,11 +3243,13 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
         else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_HALF(Z, 8, 2);                                \
         else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_HALF(Z, 11, 3);                              \
         else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_HALF(Z, 12, 3);                              \
-        else OOVQE_LAUNCH_HALF(Z, 16, 0);   /* N > 48 (kch == 16 there) */                        \
+        else {                                                                                    \
+            oovqe_set_error("cas_half_transform: no half_transform variant for N=%d", N);         \
+            return OOVQE_ERR_ARG;                                                                 \
+        }                                                                                         \
     } while (0)
     // N > 48: persistent streaming kernel.  k-chunk depth with the least padding (ties: deeper)
-    const bool stream_old = oovqe_opt(OOVQE_OPT_HALF_STREAM_OLD) != 0;   // A/B hook for tools/
-    if (nrb > 3 && !stream_old) {
+    if (nrb > 3) {
         int skch = 16, waste = 1 << 30;
         for (int k = 16; k >= 10; --k) {
             const int w = (ksteps + k - 1) / k * k - ksteps;
@@ -3682,7 +3268,7 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
         const void* fn = (const void*)half_tiles_kernel<Z, D_, A_>;                               \
         int rc_ = oovqe_ensure_dynamic_lds(fn, 160 * 1024);                                       \
         if (rc_) return rc_;                                                                      \
-        long per = (long)device_cu_count() / batch;      /* one workgroup per CU (LDS) */         \
+        long per = (long)oovqe_cu_count() / batch;      /* one workgroup per CU (LDS) */         \
         if (per < 1) per = 1;                                                                     \
         if (per > want) per = want;                                                               \
         oovqe_note_stage1("half_tiles_kernel<%d,%d>", Z, D_);                                     \
@@ -3690,13 +3276,9 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
                            dim3(HALF_WAVES * 64), lds_rs, st, g_tiles, C, T2, N, M, nrb, nslabs,  \
                            nslabs * slab_doubles);                                                \
     } while (0)
-            const int variant = oovqe_opt(OOVQE_OPT_TILES_VARIANT);
             oovqe_profile_mark_start(st);
             if (ZT == 1) OOVQE_LAUNCH_TILES(1, 8, AUX_NT);
             else if (ZT == 3) OOVQE_LAUNCH_TILES(3, 4, AUX_NT);
-            else if (variant == 1) OOVQE_LAUNCH_TILES(2, 4, AUX_NT);
-            else if (variant == 2) OOVQE_LAUNCH_TILES(2, 6, AUX_NT);
-            else if (variant == 4) OOVQE_LAUNCH_TILES(2, 8, AUX_PLAIN);
             else OOVQE_LAUNCH_TILES(2, 8, AUX_NT);   // (N = 200, M = 26: 833 us per evaluation; ring of 6: 860-920, of 4: 858; default cache policy: 900)
             oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_TILES
@@ -3710,24 +3292,11 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
     } while (0)
 #define OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, RS_, lds_bytes)                                        \
     do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        static size_t occ_lds = 0;                                                                \
-        static int occ = 1;                                                                       \
         const void* fn = (const void*)half_stream_kernel<Z, KC_, D_, RS_>;                        \
-        if (!attr_done) {                                                                         \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                                160 * 1024), "cas_half_transform");               \
-            attr_done = true;                                                                     \
-        }                                                                                         \
-        if (occ_lds != lds_bytes) {                                                               \
-            int nb = 0;                                                                           \
-            OOVQE_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, HALF_WAVES * 64,\
-                                                                         lds_bytes),              \
-                            "cas_half_transform");                                                \
-            occ = nb < 1 ? 1 : nb;                                                                \
-            occ_lds = lds_bytes;                                                                  \
-        }                                                                                         \
-        long per = ((long)occ * device_cu_count()) / batch;                                       \
+        if (int rc_ = oovqe_ensure_dynamic_lds(fn, 160 * 1024)) return rc_;                       \
+        const int occ = oovqe_blocks_per_cu(fn, HALF_WAVES * 64, lds_bytes);                      \
+        if (occ < 0) return occ;                                                                  \
+        long per = ((long)occ * oovqe_cu_count()) / batch;                                        \
         if (per < 1) per = 1;                                                                     \
         if (per > want) per = want;                                                               \
         oovqe_note_stage1("half_stream_kernel<%d,%d,%d,%s>", Z, KC_, D_, RS_ ? "true" : "false"); \
@@ -3854,16 +3423,9 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
 {
     OOVQE_REQUIRE(M >= 1 && M <= 16 && N >= 1 && N <= 48, "sym_gm: N=%d M=%d", N, M);
     const int ksteps = (N + 3) / 4;
-    int KSr = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : 12;
+    const int KSr = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : 12;
     size_t lds_bytes = (size_t)4 * KSr * (M * 16 + 8) * sizeof(double);
     if (cj && cj->lds_bytes > lds_bytes) lds_bytes = cj->lds_bytes;
-    // N = 41 ... 44 (cc-pVDZ formaldimine: 43): T3 in exactly 44 rows leaves room for a THIRD workgroup per CU (3 x
-    // 53.5 KB), built for 80 VGPRs with one row of J in flight per wave.  Measured (round 4, 256 geometries): 86 us
-    // against 58 us for two workgroups per CU with two rows in flight -- 24 registers spilled and half the loads in
-    // flight per wave cost more than the third workgroup hides.  Kept behind the option gm_three_per_cu = 1.
-    const size_t lds11 = (size_t)44 * (M * 16 + 8) * sizeof(double);
-    const bool three_per_cu = ksteps == 11 && (!cj || cj->lds_bytes <= lds11) && 3 * lds11 <= 160 * 1024 &&
-                              oovqe_opt(OOVQE_OPT_GM_THREE_PER_CU) == 1;
     const unsigned nty = (unsigned)(((packed ? M * (M + 1) / 2 : M * M) + 15) / 16);
     oovqe_circuit_job_t job;
     memset(&job, 0, sizeof(job));
@@ -3873,19 +3435,13 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
     const dim3 grid = xcd_grid ? dim3(nx * (unsigned)((batch + 7) / 8 * 8)) : dim3(nx, batch);
 #define OOVQE_LAUNCH_GM2(KS_, WPE_)                                                               \
     do {                                                                                          \
-        static size_t attr_bytes = 0;                                                             \
-        if (lds_bytes > attr_bytes) {                                                             \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)sym_gm_kernel<KS_, WPE_>,            \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                                (int)lds_bytes), "cas_eval/sym_gm");              \
-            attr_bytes = lds_bytes;                                                               \
-        }                                                                                         \
+        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)sym_gm_kernel<KS_, WPE_>, lds_bytes)) return rc_; \
         hipLaunchKernelGGL((sym_gm_kernel<KS_, WPE_>), grid, dim3(SMALL_THREADS), lds_bytes, st,  \
                            J, C, Gm, N, M, packed ? 1 : 0, job, cj ? 1 : 0, batch);               \
     } while (0)
     // (measurement hooks: OOVQE_GM_TWO_PER_CU / OOVQE_GM_ONE_PER_CU force a build; 128 geometries:
     // 45 -> 38 us with two per CU, 64 geometries: no difference)
-    const bool multi_round = ((long)(nty + (cj ? 1 : 0)) * batch > (long)device_cu_count() || oovqe_opt(OOVQE_OPT_GM_TWO_PER_CU)) &&
+    const bool multi_round = ((long)(nty + (cj ? 1 : 0)) * batch > (long)oovqe_cu_count() || oovqe_opt(OOVQE_OPT_GM_TWO_PER_CU)) &&
                              2 * lds_bytes <= 160 * 1024 && oovqe_opt(OOVQE_OPT_GM_ONE_PER_CU) == 0;
 #define OOVQE_LAUNCH_GM(KS_)                                                                      \
     do {                                                                                          \
@@ -3893,11 +3449,7 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
         else OOVQE_LAUNCH_GM2(KS_, 2);                                                            \
     } while (0)
     oovqe_profile_mark_start_l(st, 2);
-    if (three_per_cu) {
-        KSr = 11;
-        lds_bytes = lds11;
-        OOVQE_LAUNCH_GM2(11, 6);
-    } else if (KSr == 4) OOVQE_LAUNCH_GM(4);
+    if (KSr == 4) OOVQE_LAUNCH_GM(4);
     else if (KSr == 8) OOVQE_LAUNCH_GM(8);
     else OOVQE_LAUNCH_GM(12);
     oovqe_profile_mark_stop(st);
@@ -3944,13 +3496,7 @@ static int cas_tail_batched(const double* J, const double* C, const double* Wpre
     const int ksteps = (N + 3) / 4;
 #define OOVQE_LAUNCH_TAIL(KS_)                                                                    \
     do {                                                                                          \
-        static size_t attr_bytes = 0;                                                             \
-        if (lds_bytes > attr_bytes) {                                                             \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)cas_tail_kernel<KS_>,                \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                                (int)lds_bytes), "cas_eval/tail");                \
-            attr_bytes = lds_bytes;                                                               \
-        }                                                                                         \
+        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)cas_tail_kernel<KS_>, lds_bytes)) return rc_; \
         hipLaunchKernelGGL((cas_tail_kernel<KS_>), dim3(batch), dim3(TAIL_THREADS), lds_bytes, st, J, C, Wpre, \
                            gamma, Gamma, nrdm, N, n_occ, ncas, NC, nuc, nuc_arr, kap_row, kap_col, n_kappa, c0, \
                            E, gvec, dE, c1, c2, out_stride);                                      \
@@ -3973,26 +3519,13 @@ struct FusedPlan {
     size_t lds_bytes;
 };
 
-static int device_cu_count()
-{
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
-    return n_cu;
-}
-
 static bool fused_plan(int N, int M, int batch, FusedPlan* fp)
 {
     if (M > 16 || N > 48 || N < 1) return false;
     // test hook: option fused_chunks = n forces n chunks of the q range (and the fused path)
     const long chunks_env = oovqe_opt(OOVQE_OPT_FUSED_CHUNKS);
     const long m2 = (long)M * M, m3 = m2 * M;
-    const int n_cu = device_cu_count();
+    const int n_cu = oovqe_cu_count();
     // The persistent kernel pays off once the sweep is bandwidth-bound (>= ~6 slabs per wave on
     // every CU); below that the one-slab-per-wave T2 kernels have the shorter latency
     // (measured crossover at N = 43: 7-8 geometries).
@@ -4044,17 +3577,7 @@ static int half_transform_fused_batched(const double* g_ao, const double* C, int
     const int kch = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : ksteps <= 11 ? 11 : 12;
 #define OOVQE_LAUNCH_FUSED(KC_, NS_)                                                              \
     do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        if (!attr_done) {                                                                         \
-            hipError_t e = hipFuncSetAttribute((const void*)half_transform_fused_kernel<KC_, NS_>, \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                               160 * 1024);                                       \
-            if (e != hipSuccess) {                                                                \
-                oovqe_set_error("cas_eval: hipFuncSetAttribute: %s", hipGetErrorString(e));       \
-                return OOVQE_ERR_HIP;                                                             \
-            }                                                                                     \
-            attr_done = true;                                                                     \
-        }                                                                                         \
+        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)half_transform_fused_kernel<KC_, NS_>, 160 * 1024)) return rc_lds; \
         oovqe_note_stage1("half_transform_fused_kernel<%d,%d>", KC_, NS_);                        \
         hipLaunchKernelGGL((half_transform_fused_kernel<KC_, NS_>), dim3(fp.wpg, batch),          \
                            dim3(HALF_WAVES * 64), fp.lds_bytes, st, g_ao, C, T3, Cdup, N, M,      \
@@ -4120,7 +3643,7 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
     // whose W * batch workgroups run in several rounds can waste less of the last one (96
     // geometries: W = 8, three rounds of 256, instead of W = 2 on 192 CUs); cost model: resident
     // rounds x (slab rounds per workgroup + ~3 for prologue and burst).
-    const long n_cu = device_cu_count();
+    const long n_cu = oovqe_cu_count();
     const long w_max = (tri + HALF_WAVES - 1) / HALF_WAVES;
     long W = n_cu / batch;
     if (W < 1) W = 1;
@@ -4136,85 +3659,37 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
     const long n_rounds = (tri + W * HALF_WAVES - 1) / (W * HALF_WAVES);
     const size_t round_bytes = (size_t)HALF_WAVES * M * M * sizeof(double);
     const size_t fixed_bytes = (64 + 128) * sizeof(double);   // dump + column table
-    // packed copy: three realisations of the same stage (option tri_mode; 0 = the default below):
-    //   1 half_tri_kernel<.,.,2>   operand-shaped loads, two slabs per wave in registers
-    //   2 half_tri_dma_kernel      LDS-DMA ring, two slots per wave
-    //   3 / 4 half_tri_reg_kernel  contiguous register loads, R = 3 / 4 slabs per wave in flight
-    const int tri_mode = oovqe_opt(OOVQE_OPT_TRI_MODE) ? oovqe_opt(OOVQE_OPT_TRI_MODE) : OOVQE_TRI_MODE_DEFAULT;
-    const size_t ring_bytes = (size_t)HALF_WAVES * 2 * (eri_slab_packed_elems(N) + 2) * sizeof(double);
-    if (packed_src && tiled == 2 && tri_mode == 2 && fixed_bytes + ring_bytes + round_bytes <= 160 * 1024) {
-        long ph = (long)((160 * 1024 - fixed_bytes - ring_bytes) / round_bytes);
-        if (ph > n_rounds) ph = n_rounds;
-        const size_t lds_dma = fixed_bytes + ring_bytes + (size_t)ph * round_bytes;
-#define OOVQE_LAUNCH_TRI_DMA(KC_, NS_)                                                            \
-    do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        if (!attr_done) {                                                                         \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)half_tri_dma_kernel<KC_, NS_>,       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                                160 * 1024), "cas_eval/half_tri_dma");            \
-            attr_done = true;                                                                     \
-        }                                                                                         \
-        oovqe_note_stage1("half_tri_dma_kernel<%d,%d>", KC_, NS_);                                \
-        hipLaunchKernelGGL((half_tri_dma_kernel<KC_, NS_>), dim3((unsigned)W, batch),             \
-                           dim3(HALF_WAVES * 64), lds_dma, st, g_ao, C, J, N, M, (int)ph);        \
-    } while (0)
-        oovqe_profile_mark_start(st);
-        if (kch == 4 && nrb == 1) OOVQE_LAUNCH_TRI_DMA(4, 1);
-        else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_TRI_DMA(8, 2);
-        else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_TRI_DMA(11, 3);
-        else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_TRI_DMA(12, 3);
-        else {
-            oovqe_set_error("cas_eval: no half_tri_dma variant for N=%d", N);
-            return OOVQE_ERR_ARG;
-        }
-        oovqe_profile_mark_stop(st);
-#undef OOVQE_LAUNCH_TRI_DMA
-        OOVQE_CHECK_LAUNCH("cas_eval/half_tri_dma");
-        return 0;
-    }
-    if (packed_src && tiled == 2 && (tri_mode == 3 || tri_mode == 4)) {
-        // pieces of 1 KB per slab for the largest N of each variant: N <= 16 / 32 / 44 / 48
+    if (packed_src) {
+        // the packed copy: contiguous register loads, R = 3 slabs per wave in flight; pieces of 1 KB per
+        // slab for the largest N of each variant: N <= 16 / 32 / 44 / 48
         const int npc = kch == 4 ? 2 : kch == 8 ? 5 : kch == 11 ? 8 : 10;
         OOVQE_REQUIRE((size_t)npc * 1024 >= eri_slab_packed_elems(N) * sizeof(double),
                       "cas_eval: half_tri_reg slab of N=%d exceeds %d KB", N, npc);
-        const int R = tri_mode;
+        constexpr int R = 3;
         const size_t slot_bytes = (size_t)HALF_WAVES * npc * 1024;
         long ph = (long)((160 * 1024 - fixed_bytes - slot_bytes) / round_bytes) / R * R;
         OOVQE_REQUIRE(ph >= R, "cas_eval: half_tri_reg staging does not fit LDS (M=%d)", M);
         const long nr_up = (n_rounds + R - 1) / R * R;
         if (ph > nr_up) ph = nr_up;
         const size_t lds_reg = fixed_bytes + slot_bytes + (size_t)ph * round_bytes;
-#define OOVQE_LAUNCH_TRI_REG(KC_, NS_, NPC_, R_)                                                  \
+#define OOVQE_LAUNCH_TRI_REG(KC_, NS_, NPC_)                                                      \
     do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        if (!attr_done) {                                                                         \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)half_tri_reg_kernel<KC_, NS_, NPC_, R_>, \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                                160 * 1024), "cas_eval/half_tri_reg");            \
-            attr_done = true;                                                                     \
-        }                                                                                         \
-        oovqe_note_stage1("half_tri_reg_kernel<%d,%d,%d,%d>", KC_, NS_, NPC_, R_);                \
-        hipLaunchKernelGGL((half_tri_reg_kernel<KC_, NS_, NPC_, R_>), dim3((unsigned)W, batch),   \
+        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)half_tri_reg_kernel<KC_, NS_, NPC_, R>, 160 * 1024)) return rc_; \
+        oovqe_note_stage1("half_tri_reg_kernel<%d,%d,%d,%d>", KC_, NS_, NPC_, R);                 \
+        hipLaunchKernelGGL((half_tri_reg_kernel<KC_, NS_, NPC_, R>), dim3((unsigned)W, batch),    \
                            dim3(HALF_WAVES * 64), lds_reg, st, g_ao, C, J, N, M, (int)ph);        \
-    } while (0)
-#define OOVQE_LAUNCH_TRI_REG_R(KC_, NS_, NPC_)                                                    \
-    do {                                                                                          \
-        if (R == 3) OOVQE_LAUNCH_TRI_REG(KC_, NS_, NPC_, 3);                                      \
-        else OOVQE_LAUNCH_TRI_REG(KC_, NS_, NPC_, 4);                                             \
     } while (0)
         if (int rc_s1 = oovqe_stage1_enter(st)) return rc_s1;
         oovqe_profile_mark_start(st);
-        if (kch == 4 && nrb == 1) OOVQE_LAUNCH_TRI_REG_R(4, 1, 2);
-        else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_TRI_REG_R(8, 2, 5);
-        else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_TRI_REG_R(11, 3, 8);
-        else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_TRI_REG_R(12, 3, 10);
+        if (kch == 4 && nrb == 1) OOVQE_LAUNCH_TRI_REG(4, 1, 2);
+        else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_TRI_REG(8, 2, 5);
+        else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_TRI_REG(11, 3, 8);
+        else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_TRI_REG(12, 3, 10);
         else {
             oovqe_set_error("cas_eval: no half_tri_reg variant for N=%d", N);
             return OOVQE_ERR_ARG;
         }
         oovqe_profile_mark_stop(st);
-#undef OOVQE_LAUNCH_TRI_REG_R
 #undef OOVQE_LAUNCH_TRI_REG
         OOVQE_CHECK_LAUNCH("cas_eval/half_tri_reg");
         return oovqe_stage1_leave(st);
@@ -4225,13 +3700,7 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
     const size_t lds_bytes = fixed_bytes + (size_t)phase * round_bytes;
 #define OOVQE_LAUNCH_TRI2(KC_, NS_, RS_)                                                          \
     do {                                                                                          \
-        static bool attr_done = false;                                                            \
-        if (!attr_done) {                                                                         \
-            OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)half_tri_kernel<KC_, NS_, RS_>,      \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                                160 * 1024), "cas_eval/half_tri");                \
-            attr_done = true;                                                                     \
-        }                                                                                         \
+        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)half_tri_kernel<KC_, NS_, RS_>, 160 * 1024)) return rc_; \
         oovqe_note_stage1("half_tri_kernel<%d,%d,%d>", KC_, NS_, RS_);                            \
         hipLaunchKernelGGL((half_tri_kernel<KC_, NS_, RS_>), dim3((unsigned)W, batch),            \
                            dim3(HALF_WAVES * 64), lds_bytes, st, g_ao, C, J, N, M, (int)phase,    \
@@ -4239,8 +3708,7 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
     } while (0)
 #define OOVQE_LAUNCH_TRI(KC_, NS_)                                                                \
     do {                                                                                          \
-        if (tiled == 2 && packed_src) OOVQE_LAUNCH_TRI2(KC_, NS_, 2);                             \
-        else if (tiled == 2) OOVQE_LAUNCH_TRI2(KC_, NS_, 1);                                      \
+        if (tiled == 2) OOVQE_LAUNCH_TRI2(KC_, NS_, 1);                                           \
         else OOVQE_LAUNCH_TRI2(KC_, NS_, 0);                                                      \
     } while (0)
     oovqe_profile_mark_start(st);
@@ -4314,16 +3782,7 @@ static int cas_energy_gradient_impl(const double* Gm, const double* hmo, const d
     const int M = n_occ + ncas;
     const size_t lds_bytes = ((size_t)2 * N * M + FOCK_THREADS) * sizeof(double);
     OOVQE_REQUIRE(lds_bytes <= 160 * 1024, "cas_energy_gradient: N*M too large for LDS");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)fock_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            oovqe_set_error("cas_energy_gradient: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return OOVQE_ERR_HIP;
-        }
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)fock_kernel, 160 * 1024)) return rc_lds;
     hipLaunchKernelGGL(fock_kernel, dim3(nrdm), dim3(FOCK_THREADS), lds_bytes, (hipStream_t)stream,
                        Gm, hmo, gamma, Gamma, nuc, N, n_occ, ncas, kap_row, kap_col, n_kappa, c0, c1,
                        c2, E, fock, gmat, gvec, dE, nuc_dev);
@@ -4345,12 +3804,7 @@ static int cas_energy_gradient_rows(const double* Gm, const double* hmo, const d
     hipStream_t st = (hipStream_t)stream;
     const size_t lds_bytes = fock_rows_lds_elems(n_occ, ncas) * sizeof(double);
     OOVQE_REQUIRE(lds_bytes <= FROW_LDS_MAX, "cas_energy_gradient: %zu B of LDS", lds_bytes);
-    static bool attr_done = false;
-    if (!attr_done) {
-        OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)fock_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)FROW_LDS_MAX), "cas_energy_gradient");
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)fock_rows_kernel, FROW_LDS_MAX)) return rc_lds;
     hipLaunchKernelGGL(fock_rows_kernel, dim3(N, nrdm), dim3(FROW_THREADS), lds_bytes, st, Gm, hmo, gamma, Gamma,
                        N, n_occ, ncas, Fcol, Epart, Cpart, c1, c2);
     OOVQE_CHECK_LAUNCH("cas_energy_gradient/rows");
@@ -4512,7 +3966,7 @@ static int cas_eval_batched(const double* g_ao, const double* h_ao, const double
         // nothing beyond the packed outputs is asked for; otherwise sym_gm, panel and final launches
         int tail_nc = 0;
         const bool tail = !two_step && rs_sym && g_packed != nullptr && !T2_ready && !cj && w_ready && !fock && !gmat && !Gm && !hmo &&
-                          2L * batch > (long)device_cu_count() && tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &tail_nc) > 0 &&
+                          2L * batch > (long)oovqe_cu_count() && tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &tail_nc) > 0 &&
                           oovqe_opt(OOVQE_OPT_TAIL_SPLIT) == 0;
         if (tail) {
             double* wchk = nullptr;
@@ -4649,16 +4103,7 @@ static int cas_eval_batched(const double* g_ao, const double* h_ao, const double
         int rdm_chunk = (int)((lds_cap - fixed_bytes - (size_t)npan * per_n) / set_bytes);
         if (rdm_chunk > nrdm) rdm_chunk = nrdm;
         const size_t lds_bytes = fixed_bytes + (size_t)npan * per_n + (size_t)rdm_chunk * set_bytes;
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)cas_panel_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
-            if (e != hipSuccess) {
-                oovqe_set_error("cas_eval: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                return OOVQE_ERR_HIP;
-            }
-            attr_done = true;
-        }
+        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_panel_kernel, lds_cap)) return rc_lds;
         oovqe_profile_mark_start_l(st, 3);
         const unsigned npanels = (unsigned)((N + npan - 1) / npan);
         const bool xcd_grid = batch > 1 && oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) == 0;
@@ -4677,23 +4122,14 @@ static int cas_eval_batched(const double* g_ao, const double* h_ao, const double
         int rdm_chunk = (int)((lds_cap - base_bytes) / set_bytes);
         if (rdm_chunk > nrdm) rdm_chunk = nrdm;
         const size_t lds_bytes = base_bytes + (size_t)rdm_chunk * set_bytes;
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)cas_column_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
-            if (e != hipSuccess) {
-                oovqe_set_error("cas_eval: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                return OOVQE_ERR_HIP;
-            }
-            attr_done = true;
-        }
+        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_column_kernel, lds_cap)) return rc_lds;
         oovqe_profile_mark_start_l(st, 3);
         // many large RDM sets (a derivative evaluation of a big active space): their chunks are dealt to
         // zsplit workgroups per n, about one resident round of workgroups in all
         int zsplit = 1;
         if (ncas * ncas * ncas >= 128 && rdm_chunk > 0) {
             const int nchunks = (nrdm + rdm_chunk - 1) / rdm_chunk;
-            zsplit = (int)((long)device_cu_count() * 2 / ((long)N * batch));
+            zsplit = (int)((long)oovqe_cu_count() * 2 / ((long)N * batch));
             if (zsplit > nchunks) zsplit = nchunks;
             if (zsplit > 64) zsplit = 64;
             if (zsplit < 1) zsplit = 1;
@@ -4859,7 +4295,7 @@ static int oo_eval_batched(const double* theta, int n_theta, const oovqe_gate_t*
             oovqe_opt(OOVQE_OPT_NO_RIDE) != 2) {
             const bool rs = (eri_flags & OOVQE_ERI_RS_SYMMETRIC) != 0 && oovqe_opt(OOVQE_OPT_SYM_NO_RS) == 0;
             const long ntile = ((rs ? (long)M * (M + 1) / 2 : m2) + 15) / 16;
-            if ((ntile + 1) * batch > 3L * device_cu_count()) ride = false;
+            if ((ntile + 1) * batch > 3L * oovqe_cu_count()) ride = false;
         }
     }
     bool w_ready = false;

@@ -573,17 +573,7 @@ extern "C" int oovqe_circuit_state(const double* theta, int n_theta, const oovqe
     const int use_lds = D <= (uint32_t)LDS_STATE_MAX;
     const int n_tan = dpsi ? n_theta : 0;
     const size_t lds_bytes = use_lds ? (size_t)D * sizeof(double) : 0;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)circuit_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDS_STATE_MAX * (int)sizeof(double));
-        if (e != hipSuccess) {
-            oovqe_set_error("circuit_state: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return OOVQE_ERR_HIP;
-        }
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)circuit_kernel, LDS_STATE_MAX * (int)sizeof(double))) return rc_lds;
     const long nblocks = (long)batch * (1 + n_tan);
     OOVQE_REQUIRE(nblocks <= 0x7fffffffL, "circuit_state: grid too large");
     hipLaunchKernelGGL(circuit_kernel, dim3((unsigned)nblocks), dim3(CIRC_THREADS), lds_bytes,
@@ -687,17 +677,7 @@ int oovqe_circuit_rdms_w(const double* theta, int n_theta, const oovqe_gate_t* g
                   "circuit_rdms: W = C^T h rides with the one-workgroup circuit kernel (N <= 48)");
     if (Wpre && (size_t)2 * N * N * sizeof(double) > lds_bytes) lds_bytes = (size_t)2 * N * N * sizeof(double);
     if (oovqe_circuit_rdms_is_small(n_qubits, ncas, nvec, n_gates)) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)circuit_rdm_small_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               150 * 1024);
-            if (e != hipSuccess) {
-                oovqe_set_error("circuit_rdms: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                return OOVQE_ERR_HIP;
-            }
-            attr_done = true;
-        }
+        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)circuit_rdm_small_kernel, 150 * 1024)) return rc_lds;
         hipLaunchKernelGGL(circuit_rdm_small_kernel, dim3(Wpre ? 2 * batch : batch), dim3(SMALL_THREADS), lds_bytes,
                            (hipStream_t)stream, theta, n_theta, gates, n_gates, n_qubits, ncas,
                            init_index, n_tan, psi, dpsi, gamma, Gamma, batch, h_ao, C, N, Wpre);

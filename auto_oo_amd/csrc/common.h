@@ -25,8 +25,7 @@ void oovqe_profile_mark_stop(hipStream_t st);
 // oovqe_debug_set_option, never from the environment: the production path does not depend on the
 // caller's environment variables).  All default to 0.
 enum oovqe_option_t {
-    OOVQE_OPT_HALF_STREAM_OLD = 0,   // pre-persistent streaming kernel for N > 48
-    OOVQE_OPT_GM_TWO_PER_CU,         // force the 128-VGPR build of sym_gm_kernel
+    OOVQE_OPT_GM_TWO_PER_CU = 0,     // force the 128-VGPR build of sym_gm_kernel
     OOVQE_OPT_GM_ONE_PER_CU,         // force its one-workgroup-per-CU build
     OOVQE_OPT_FUSED_CHUNKS,          // n > 0: force the batched plan with n chunks of q
     OOVQE_OPT_TRI_PLAIN_W,           // W = CUs / batch in half_tri_kernel (no cost model)
@@ -36,22 +35,18 @@ enum oovqe_option_t {
     OOVQE_OPT_SYM_SIMPLE,            // one-slab-per-wave triangle kernel
     OOVQE_OPT_SYM_TWO_STEP,          // q->x kernel + K1 instead of the one-launch kernel
     OOVQE_OPT_NO_RIDE,               // 1: circuit + RDM step as its own launch whatever the batch; 2: riding whatever the batch
-    OOVQE_OPT_TRI_MODE,              // packed-triangle stage 1: 1 operand loads, 2 LDS-DMA, 3/4 contiguous loads
     OOVQE_OPT_K1_NO_PAIR,            // K1: never the two-strips-per-wave kernel
     OOVQE_OPT_K1_FORCE_WIDE,         // K1: INNER contractions on the long-stride kernels (one descriptor per k-step)
     OOVQE_OPT_GM_PLAIN_GRID,         // sym_gm_kernel: (tile, geometry) grid instead of the XCD-aware 1-D one
     OOVQE_OPT_NEWTON_ONE_WG,         // oovqe_newton_direction: the one-workgroup tridiagonalisation kernel (n <= 480)
     OOVQE_OPT_SECTOR_UNFUSED,        // sector RDMs / adjoint: E_pq vectors through memory (the round-2 kernels)
-    OOVQE_OPT_SECTOR_PROBE,          // timing probe of sector_rdm_fused_kernel (wrong results): 1 no chunk build, 2 no MFMA
     OOVQE_OPT_HESS_VK_PASS,          // orbital Hessian: the K-type quarter transform as its own pass over the AO tensor (round 2)
     OOVQE_OPT_HESS_OWN_STAGE1,       // Hessian call: the evaluation streams the integrals itself instead of taking J from the orbital Hessian's T2
     OOVQE_OPT_PANEL_ROWS,            // cas_panel_kernel: general indices per workgroup (0: chosen by the host code)
     OOVQE_OPT_K1_FORCE_NT,           // K1 / K1P: this many 16-wide tiles of J per wave (0: all that fit, up to 13)
     OOVQE_OPT_NEWTON_NO_CHOL,        // oovqe_newton_direction: never the Cholesky fast path (band route for every problem)
-    OOVQE_OPT_TILES_VARIANT,         // half_tiles_kernel (measurement, M in 17..32): 1 / 2 = ring of 4 / 6 tiles instead of 8, 4 = default cache policy for the loads
-    OOVQE_OPT_SECTOR_LAMBDA_W,       // sector adjoint: 1 = lambda through W = Ms^T V in memory (round 3) whatever the batch, 2 = the string-driven form whatever the batch, 3 = the same (kept for the tools), 4 = that with multiplier / helper waves (sector_lambda_pipe_kernel: measured, slower) (0: by batch size)
+    OOVQE_OPT_SECTOR_LAMBDA_W,       // sector adjoint: 1 = lambda through W = Ms^T V in memory (round 3) whatever the batch, 2 = the string-driven form whatever the batch (0: by batch size)
     OOVQE_OPT_SECTOR_RDM_R3,         // sector RDMs: 1 = the round-3 fused kernel (chunks of 128 consecutive determinants) whatever the batch, 2 = row chunks in the sigma basis whatever the batch (0: by batch size)
-    OOVQE_OPT_GM_THREE_PER_CU,       // sym_gm_kernel at N = 41 ... 44: 1 = the three-workgroups-per-CU build (measured: slower)
     OOVQE_OPT_PANEL_NO_W,            // cas_panel_kernel always stages h_ao and forms its rows of C^T h itself (no W from the circuit launch)
     OOVQE_OPT_STAGE1_FREE_RUN,       // 1: N^4 sweeps enqueued on different streams are not ordered one after the other
     OOVQE_OPT_ONE_STREAM,            // 1: every launch of a call on the caller's stream (no chain of a call on the library's internal streams)
@@ -61,6 +56,10 @@ enum oovqe_option_t {
 int oovqe_opt(int id);
 // raise a kernel's dynamic-LDS limit to `bytes` (cached per kernel AND device, thread-safe); 0 or OOVQE_ERR_HIP
 int oovqe_ensure_dynamic_lds(const void* kernel, size_t bytes);
+// resident workgroups per CU of `kernel` launched with `threads` and `lds_bytes` (cached the same way); >= 1 or OOVQE_ERR_HIP
+int oovqe_blocks_per_cu(const void* kernel, int threads, size_t lds_bytes);
+// CUs of the current device
+int oovqe_cu_count();
 void oovqe_note_stage1(const char* fmt, ...);
 // the next event of a small per-device ring (timing disabled; nullptr on failure), and the library's internal
 // stream of the current device (k = 0; made on first use, non-blocking; nullptr on failure or with option

@@ -540,17 +540,7 @@ int launch_nt(const double* T, const double* Cm, double* out, long A, int K, int
     if constexpr (KS == 12) {
         if (cj) {
             if (cj->lds_bytes > lds_bytes) lds_bytes = cj->lds_bytes;
-            static size_t attr_bytes = 0;   // per instantiation
-            if (lds_bytes > attr_bytes) {
-                hipError_t e = hipFuncSetAttribute((const void*)contract_circuit_kernel<NT, LAST, KS>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)lds_bytes);
-                if (e != hipSuccess) {
-                    oovqe_set_error("mode_contract: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                    return OOVQE_ERR_HIP;
-                }
-                attr_bytes = lds_bytes;
-            }
+            if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)contract_circuit_kernel<NT, LAST, KS>, lds_bytes)) return rc_lds;
             hipLaunchKernelGGL((contract_circuit_kernel<NT, LAST, KS>),
                                dim3((unsigned)nblocks + 1, (unsigned)ngroups, (unsigned)batch),
                                dim3(NTH), lds_bytes, st, T, Cm, out, A, K, J, B, ldc, n_items, nbt,
@@ -561,17 +551,7 @@ int launch_nt(const double* T, const double* Cm, double* out, long A, int K, int
     } else {
         OOVQE_REQUIRE(!cj, "mode_contract: this shape cannot host circuit workgroups");
     }
-    static bool attr_done = false;   // per instantiation
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)contract_kernel<NT, LAST, KS, WIDE>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes);
-        if (e != hipSuccess) {
-            oovqe_set_error("mode_contract: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return OOVQE_ERR_HIP;
-        }
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)contract_kernel<NT, LAST, KS, WIDE>, lds_bytes)) return rc_lds;
     hipLaunchKernelGGL((contract_kernel<NT, LAST, KS, WIDE>),
                        dim3((unsigned)nblocks, (unsigned)ngroups, (unsigned)batch), dim3(NTH),
                        lds_bytes, st, T, Cm, out, A, K, J, B, ldc, n_items, nbt, t_bs, c_bs, o_bs);

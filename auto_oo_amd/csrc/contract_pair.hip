@@ -327,16 +327,7 @@ int launch_pair_nt(const double* T, const double* Cm, double* out, long A, int K
     long per_slice = 256 / ((long)ngroups * batch);   // persistent: one workgroup per CU
     if (per_slice < 1) per_slice = 1;
     const long nblocks = ngroups_items < per_slice ? ngroups_items : per_slice;
-    static bool attr_done = false;   // per instantiation
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)contract_pair_kernel<NT, KS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            oovqe_set_error("mode_contract: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return OOVQE_ERR_HIP;
-        }
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)contract_pair_kernel<NT, KS>, lds_bytes)) return rc_lds;
     hipLaunchKernelGGL((contract_pair_kernel<NT, KS>),
                        dim3((unsigned)nblocks, (unsigned)ngroups, (unsigned)batch), dim3(PTHREADS), lds_bytes, st,
                        T, Cm, out, A, K, J, B, ldc, n_items, (int)nbt, t_bs, c_bs, o_bs);

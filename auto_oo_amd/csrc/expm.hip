@@ -317,16 +317,7 @@ int expm_small(const double* X, const double* kappa, const int32_t* kap_row, con
 {
     const int nt = (N + 15) / 16, NP = nt * 16, LD = NP + 2;
     const size_t lds_bytes = (size_t)6 * NP * LD * sizeof(double);
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)expm_small_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) {
-            oovqe_set_error("expm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return OOVQE_ERR_HIP;
-        }
-        attr_done = true;
-    }
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)expm_small_kernel, 150 * 1024)) return rc_lds;
     hipLaunchKernelGGL(expm_small_kernel, dim3(batch), dim3(EX_THREADS), lds_bytes, st, X, kappa,
                        kap_row, kap_col, n_kappa, sign, N, Kout, U, Cin, Cout);
     OOVQE_CHECK_LAUNCH("expm_small");

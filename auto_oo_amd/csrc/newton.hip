@@ -2021,12 +2021,8 @@ static int n3_direction(const double* hessian, const double* gradient, int n, in
     const size_t panel_lds = (size_t)(2 * 64 * RQ_MID + 64 + 64 + 16) * sizeof(double);
     const size_t solve_lds = (size_t)(n2_lds2(16).total + GL.npv + 2 * RW + 16) * sizeof(double);
     OOVQE_REQUIRE(panel_lds <= 159 * 1024 && solve_lds <= 159 * 1024, "oovqe_newton_direction: n = %d too large", n);
-    OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)n2l_panel_kernel<RQ_MID>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)panel_lds),
-                    "oovqe_newton_direction: hipFuncSetAttribute");
-    OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)newton_band_solve_kernel<true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds),
-                    "oovqe_newton_direction: hipFuncSetAttribute");
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)n2l_panel_kernel<RQ_MID>, panel_lds)) return rc_lds;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)newton_band_solve_kernel<true>, solve_lds)) return rc_lds;
     for (int b = 0; b < batch; ++b) {
         double* wk = work + (size_t)b * GL.total;
         const double* Hb = hessian + (size_t)b * n * n;
@@ -2108,11 +2104,8 @@ static int n2_band_route(const double* hessian, const double* gradient, int n, i
                   "oovqe_newton_direction: workspace per problem too large");
     const bool small_q = n - BW <= 64 * RQ_SMALL;
     const void* k1 = small_q ? (const void*)newton_band_kernel<RQ_SMALL> : (const void*)newton_band_kernel<RQ_LARGE>;
-    OOVQE_CHECK_HIP(hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                    "oovqe_newton_direction: hipFuncSetAttribute");
-    OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)newton_band_solve_kernel<false>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2),
-                    "oovqe_newton_direction: hipFuncSetAttribute");
+    if (int rc_lds = oovqe_ensure_dynamic_lds(k1, lds)) return rc_lds;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)newton_band_solve_kernel<false>, lds2)) return rc_lds;
     // workgroups per problem: all of them must be resident together (they wait for each other)
     const int lim1 = n2_resident_limit(k1, NT, lds);
     const int lim2 = n2_resident_limit((const void*)newton_band_solve_kernel<false>, NT2, lds2);
@@ -2171,9 +2164,7 @@ extern "C" int oovqe_newton_direction_rest(const double* hessian, const double* 
     const Layout L = make_layout(n);
     const size_t lds = (size_t)L.total * sizeof(double);
     OOVQE_REQUIRE(lds <= 160 * 1024, "oovqe_newton_direction: %zu bytes of LDS needed", lds);
-    OOVQE_CHECK_HIP(hipFuncSetAttribute((const void*)newton_direction_kernel,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                    "oovqe_newton_direction: hipFuncSetAttribute");
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)newton_direction_kernel, lds)) return rc_lds;
     hipLaunchKernelGGL(newton_direction_kernel, dim3(batch), dim3(NT), lds, st, hessian,
                        gradient, n, lambda_min, mu, rho, aug, work, dp, lowest_eigenvalue, shift);
     OOVQE_CHECK_LAUNCH("oovqe_newton_direction");

@@ -461,9 +461,10 @@ def test_in_place_edit_of_int2e_ao_reverifies_symmetry_flags():
 
 @pytest.mark.parametrize("N,G", [(43, 9), (13, 40), (30, 11), (47, 5)])
 def test_packed_stage1_realisations_agree(N, G, lib_options):
-    """The three realisations of stage 1 on the packed copy (operand-shaped HBM loads, LDS-DMA ring,
-    contiguous register loads with 3 / 4 slabs in flight; debug option tri_mode) form the same sums:
-    in the same order: bit-identical energies and gradients, equal to the oracle's."""
+    """Stage 1 on the packed copy (half_tri_reg_kernel) beside an independent realisation of the same stage:
+    option sym_no_rs makes the call stream the full tensor through half_tri_kernel (the stack keeps int2e_ao) --
+    the same sums in another order.  The builds and grids of the q -> x, p -> n kernel behind stage 1 are
+    bit-identical to the default; energies and gradients equal the oracle's."""
     from auto_oo_amd.synthetic import synthetic_problem
     ncas, nelecas, nelec = 3, 4, 16
     pqc = aoo.Parameterized_circuit(ncas, nelecas, None, ansatz="ucc")
@@ -476,17 +477,15 @@ def test_packed_stage1_realisations_agree(N, G, lib_options):
     assert batch._eri_packed is not None
     thetas = torch.tensor(np.random.default_rng(2).uniform(0, 2 * np.pi, (G, pqc.theta_shape)))
     lib_options(fused_chunks=1)                      # the batched (packed-triangle) plan at any batch size
-    outs = []
-    for mode in (1, 2, 3, 4):
-        lib_options(tri_mode=mode)
-        outs.append(batch.energy_and_gradient(thetas).clone())
-    # every mode runs the first products as single accumulator chains in the same order: bit-identical
-    for o in outs[1:]:
-        assert torch.equal(o, outs[0])
-    # the builds of the q -> x, p -> n kernel behind it (one / two workgroups per CU; at N = 41 ... 44 the measured
-    # and not adopted three-per-CU build): the same chains of products with more or fewer zero k-steps
-    lib_options(tri_mode=0)
-    for opt in ("gm_one_per_cu", "gm_two_per_cu", "gm_three_per_cu", "gm_plain_grid"):
+    outs = [batch.energy_and_gradient(thetas).clone()]
+    # the full tensor through half_tri_kernel: the same first products summed in another order
+    lib_options(sym_no_rs=1)
+    full = batch.energy_and_gradient(thetas).clone()
+    lib_options(sym_no_rs=0)
+    assert (full - outs[0]).abs().max() <= 1e-12 * max(1.0, float(outs[0].abs().max()))
+    # the builds of the q -> x, p -> n kernel behind it (one / two workgroups per CU, the plain grid): the same
+    # chains of products with more or fewer zero k-steps
+    for opt in ("gm_one_per_cu", "gm_two_per_cu", "gm_plain_grid"):
         lib_options(**{opt: 1})
         assert torch.equal(batch.energy_and_gradient(thetas), outs[0]), opt
         lib_options(**{opt: 0})

@@ -33,6 +33,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.oovqe_version() >= 100
 
 
+def test_debug_option_names_follow_the_header():
+    """Every option named in the comment of include/oovqe.h is accepted and starts at 0; any other name is refused."""
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "include", "oovqe.h")) as fh:
+        hdr = fh.read()
+    block = hdr[hdr.index("Test / measurement switches"):hdr.index("int oovqe_debug_set_option")]
+    names = set(re.findall(r'"([a-z0-9_]+)"', block))
+    assert {"sym_no_rs", "gm_one_per_cu", "sector_lambda_w", "tail_split"} <= names
+    for name in sorted(names):
+        assert lib.oovqe_debug_get_option(name.encode()) == 0, name
+    assert lib.oovqe_debug_get_option(b"no_such_option") == -1
+    assert lib.oovqe_debug_set_option(b"no_such_option", 1) != 0
+    assert b"unknown option" in lib.oovqe_last_error()
+    with pytest.raises(_lib.OovqeError):
+        with _lib.debug_options(no_such_option=1):
+            pass
+
+
 def test_gate_struct_layout():
     assert _lib.GATE_NBYTES == 40
 

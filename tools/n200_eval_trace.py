@@ -34,14 +34,12 @@ if sym and len(sys.argv) > 2 and sys.argv[2] == "packed":
     packed = ops.eri_pack(g)
     torch.cuda.synchronize()
     print(f"eri_pack: {(time.perf_counter() - t0) * 1e3:.2f} ms, {packed.numel() * 8 / 1e9:.2f} GB")
-for variant in ([0, 1, 2, 4, 0] if packed is not None and len(sys.argv) > 3 else [0]):
-    with aoo._lib.debug_options(tiles_variant=variant):
-        for _ in range(3):
-            ops.cas_eval(g, h, Q, g1, g2, 31.0, n_occ, ncas, kr, kc, work=work, eri_flags=flags, g_packed=packed)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(8):
-            ops.cas_eval(g, h, Q, g1, g2, 31.0, n_occ, ncas, kr, kc, work=work, eri_flags=flags, g_packed=packed)
-        torch.cuda.synchronize()
-    print(f"flags {flags}{' packed' if packed is not None else ''} variant {variant}: "
-          f"{(time.perf_counter() - t0) / 8 * 1e6:.1f} us per evaluation", flush=True)
+for _ in range(3):
+    ops.cas_eval(g, h, Q, g1, g2, 31.0, n_occ, ncas, kr, kc, work=work, eri_flags=flags, g_packed=packed)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+for _ in range(8):
+    ops.cas_eval(g, h, Q, g1, g2, 31.0, n_occ, ncas, kr, kc, work=work, eri_flags=flags, g_packed=packed)
+torch.cuda.synchronize()
+print(f"flags {flags}{' packed' if packed is not None else ''}: "
+      f"{(time.perf_counter() - t0) / 8 * 1e6:.1f} us per evaluation", flush=True)

@@ -13,7 +13,7 @@ def T(f, n=50):
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / n * 1e6, r
 for G in sizes:
     ref = None
-    for opts in ({}, {"sym_simple": 1}, {"tri_mode": 1}, {"tri_mode": 2}, {"tri_mode": 4}, {"tri_plain_w": 1}, {"sym_mirror": 1}, {"cas_unfused": 1}):
+    for opts in ({}, {"sym_simple": 1}, {"tri_plain_w": 1}, {"sym_mirror": 1}, {"cas_unfused": 1}):
         with _lib.debug_options(**opts):
             t, out = T(lambda: batch.evaluate(thetas[:G], derivatives=False, count=G))
             ops.profile_begin(detail=True)
