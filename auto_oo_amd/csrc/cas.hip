@@ -10,37 +10,31 @@
 //   stage 1  T2[p,q,y,z] = sum_rs C[r,y] g_ao[p,q,r,s] C[s,z]        (this file, slab kernels)
 //   stage 2  Gm = contract q->x, p->n; hmo = C^T h C[:, :M]
 //   stage 3  c0,c1,c2,E, Fock matrices, orbital gradient
-// Two realisations, chosen per call by oovqe_cas_eval (cas_eval_batched):
-//   T3 path (bandwidth-bound sweeps, M <= 16, N <= 48): half_transform_fused_kernel does stage 1 and
-//     the q->x half of stage 2 in one persistent kernel (T2 never leaves the chip), K1 contracts
-//     p->n, cas_panel_kernel does stage 3 on panels of general indices, cas_final_kernel assembles;
-//   T2 path (few geometries, or larger M / N): half_transform_kernel writes T2, K1 contracts p->n,
-//     cas_column_kernel contracts q->x and does stage 3 per general index, cas_final_kernel.
+// What runs for a call is decided once, as plain data, by oovqe_eval_plan (plan.h; host code at the end of this
+// file) from the shape, the symmetry flags, what the caller holds (packed integrals, a T2, extra outputs), the
+// circuit's size, the option values and the CU count; cas_eval_batched is a switch over the plan's path that only
+// launches.  Six paths (DESIGN.md section 10 has the conditions):
+//   packed triangle, one-launch tail   half_tri[_reg]_kernel -> J (slabs p <= q); cas_tail_kernel: q -> x, p -> n,
+//                                      stage 3 and assembly, one workgroup per geometry
+//   packed triangle, three launches    J as above (or j_from_t2_kernel); sym_gm_kernel (q -> x, p -> n, + the circuit
+//                                      workgroups), cas_panel_kernel, cas_final_kernel
+//   packed triangle, two steps         (options only) sym_q_contract_kernel, K1 p -> n, panel, final
+//   fused                              half_transform_fused_kernel: stage 1 + q -> x in one persistent kernel (T2
+//                                      never leaves the chip), K1 p -> n, panel, final          (M <= 16, N <= 48)
+//   column                             half_transform / half_stream / half_tiles kernel writes T2, K1 p -> n,
+//                                      cas_column_kernel: q -> x and stage 3 per general index, final
+//   staged                             T2, then per geometry K1 q -> x, p -> n, h_mo and the Fock kernels on g_mo in
+//                                      memory (large N * M^2: neither U[n] nor a panel fits LDS)
+// The circuit + RDM step of oovqe_oo_eval[_batch] rides along the p -> n launch or has a launch of its own ahead of
+// stage 1, which then may leave W = C^T h_ao for the panel / tail kernel (plan.circuit, plan.w).
+// The stage-1 kernels for N <= 48 come in four builds by slab shape (stage1_variant); every launcher dispatches on
+// that one table.
 // The staged entry points (oovqe_cas_half_transform / _finish_transform / _energy_gradient) keep
 // the three stages separate for callers that want the intermediates.
-#include "common.h"
+#include "plan.h"
 #include "circuit_small.h"
 #include <type_traits>
 #include <stdlib.h>
-
-int oovqe_mode_contract_impl(const double* T, const double* Cm, double* out, long A, int K, int J,
-                             long B, int ldc, int last, hipStream_t st);
-int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st);
-int oovqe_mode_contract_batched_circ(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                     long B, int ldc, int last, int batch, long t_bs, long c_bs,
-                                     long o_bs, hipStream_t st, const oovqe_circuit_job_t* cj);
-int oovqe_contract_hosts_circuit(long A, int K, int J, long B, int last, int batch);
-int oovqe_circuit_rdms_w(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates, int n_qubits,
-                         int ncas, uint32_t init_index, int want_tangents, int batch, double* psi, double* dpsi,
-                         double* gamma, double* Gamma, double* work, const double* h_ao, const double* C, int N,
-                         double* Wpre, oovqe_stream_t stream);
-extern "C" int oovqe_circuit_rdms(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
-                                  int n_qubits, int ncas, uint32_t init_index, int want_tangents, int batch,
-                                  double* psi, double* dpsi, double* gamma, double* Gamma, double* work,
-                                  oovqe_stream_t stream);
-extern "C" int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
 namespace {
 
@@ -60,6 +54,11 @@ namespace {
 // Algorithmic HBM bytes: 8 N^4 read + 8 N^2 M^2 written.
 // ------------------------------------------------------------------------------------------
 constexpr int HALF_WAVES = 8;
+// slabs per wave in flight of half_tri_reg_kernel; ring depths of half_tiles_kernel / half_stream_kernel by 16-wide
+// tiles of M (N = 200, M = 26, tiles: 833 us per evaluation; ring of 6: 860-920, of 4: 858; default cache policy: 900)
+constexpr int TRI_REG_R = 3;
+constexpr int tiles_depth(int zt) { return zt == 3 ? 4 : 8; }
+constexpr int stream_depth(int zt) { return zt == 3 ? 2 : 3; }
 // Cache policy of the g_ao stream (gfx950 buffer-load aux bits: 1 = sc0, 2 = nt, 16 = sc1).  Every
 // byte is used once, but the non-temporal hint only pays where the stream is irregular or short:
 // measured (tools/half_standalone.hip, stream_standalone.hip) packed triangle 109 -> 101 us,
@@ -3195,74 +3194,114 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
 
 }  // namespace
 
-static int half_transform_batched(const double* g_ao, const double* C, int N, int M, double* T2,
-                                  int batch, oovqe_stream_t stream, int sym = SYM_FULL, bool rs = false,
-                                  double* Vk_tri = nullptr, const double* g_tiles = nullptr);
+// ---- the stage-1 kernel that serves a shape -----------------------------------------------------------------
+// LAUNCH(KCH, NRB, NPC, further arguments) for the Stage1Variant v / LAUNCH(KS) for its q -> x depth: the rows of stage1_variant
+#define OOVQE_STAGE1_DISPATCH(v, LAUNCH, ...)                                                     \
+    switch ((v).kch) {                                                                            \
+    case 4: LAUNCH(4, 1, 2, ##__VA_ARGS__); break;                                                \
+    case 8: LAUNCH(8, 2, 5, ##__VA_ARGS__); break;                                                \
+    case 11: LAUNCH(11, 3, 8, ##__VA_ARGS__); break;                                              \
+    default: LAUNCH(12, 3, 10, ##__VA_ARGS__); break;                                             \
+    }
+#define OOVQE_KS_DISPATCH(v, LAUNCH)                                                              \
+    switch ((v).ks) {                                                                             \
+    case 4: LAUNCH(4); break;                                                                     \
+    case 8: LAUNCH(8); break;                                                                     \
+    default: LAUNCH(12); break;                                                                   \
+    }
 
-extern "C" int oovqe_cas_half_transform(const double* g_ao, const double* C, int N, int M, double* T2,
-                                        oovqe_stream_t stream)
+static int stage1_variant(int N, Stage1Variant* v)
 {
-    return half_transform_batched(g_ao, C, N, M, T2, 1, stream);
+    // whole-slab preload: the slab is one k-chunk deep and <= 48 loads per lane; packed slabs in pieces of 1 KB
+    // for the largest N of each row: N <= 16 / 32 / 44 / 48
+    static const Stage1Variant rows[] = {{4, 1, 2, 4}, {8, 2, 5, 8}, {11, 3, 8, 12}, {12, 3, 10, 12}};
+    for (const Stage1Variant& r : rows)
+        if (N >= 1 && (N + 3) / 4 <= r.kch) {
+            *v = r;
+            return 0;
+        }
+    oovqe_set_error("cas_eval: no stage-1 kernel variant for N=%d", N);
+    return OOVQE_ERR_ARG;
 }
 
-static int half_transform_batched(const double* g_ao, const double* C, int N, int M, double* T2,
-                                  int batch, oovqe_stream_t stream, int sym, bool rs, double* Vk_tri,
-                                  const double* g_tiles)
+// LDS of the T2 kernels: the padded copy of C[:, :M] (see half_stream_kernel)
+static size_t half_lds_bytes(int N, int M)
 {
-    // g_tiles: the tile-packed copy of g_ao (oovqe_eri_pack, N > 48; both symmetry flags) or null
+    const int ZT = (M + 15) / 16, nrb = (N + 15) / 16, LDM = 16 * (ZT | 1);
+    return (((size_t)nrb * 16 * LDM + 511) / 512) * 512 * sizeof(double);
+}
+// r <-> s symmetric slabs: upper tile triangle only (needs a 16 x 17 patch per wave in LDS)
+static size_t half_lds_bytes_rs(int N, int M) { return half_lds_bytes(N, M) + (size_t)HALF_WAVES * 16 * 17 * sizeof(double); }
+
+// T2 [N][N][M][M] (sym SYM_FULL / SYM_MIRROR) or the row-major packed triangle (SYM_PACKED).  rs: the r <-> s flag;
+// tiles: a tile-packed copy of the integrals (oovqe_eri_pack, N > 48) is at hand
+static int stage1_half(int N, int M, int sym, bool rs, bool tiles, Stage1* s)
+{
+    memset(s, 0, sizeof(*s));
+    OOVQE_REQUIRE(N >= 1 && M >= 1 && M <= N, "cas_half_transform: bad N=%d M=%d", N, M);
+    const int ZT = (M + 15) / 16, nrb = (N + 15) / 16, ksteps = (N + 3) / 4;
+    OOVQE_REQUIRE(ZT <= 3, "cas_half_transform: n_occ+ncas = %d > 48 not supported", M);
+    OOVQE_REQUIRE(half_lds_bytes(N, M) <= 160 * 1024, "cas_half_transform: N=%d M=%d needs %zu B of LDS", N, M,
+                  half_lds_bytes(N, M));
+    s->zt = ZT;
+    s->sym = sym;
+    if (nrb <= 3) {
+        s->kernel = S1_HALF;
+        if (int rc = stage1_variant(N, &s->v)) return rc;
+        snprintf(s->name, sizeof(s->name), "half_transform_kernel<%d,%d,%d>%s", ZT, s->v.kch, s->v.nrb,
+                 sym ? " (slabs p <= q)" : "");
+        return 0;
+    }
+    // N > 48: persistent streaming kernel.  k-chunk depth with the least padding (ties: deeper)
+    int waste = 1 << 30;
+    for (int k = 16; k >= 10; --k) {
+        const int w = (ksteps + k - 1) / k * k - ksteps;
+        if (w < waste) { waste = w; s->skch = k; }
+    }
+    s->rs = rs && half_lds_bytes_rs(N, M) <= 160 * 1024;
+    if (tiles && s->rs && sym == SYM_MIRROR) {
+        // both flags and a resident tile-packed copy: half_tiles_kernel streams that instead
+        s->kernel = S1_TILES;
+        snprintf(s->name, sizeof(s->name), "half_tiles_kernel<%d,%d>", ZT, tiles_depth(ZT));
+    } else {
+        s->kernel = S1_STREAM;
+        snprintf(s->name, sizeof(s->name), "half_stream_kernel<%d,%d,%d,%s>", ZT, s->skch, stream_depth(ZT), s->rs ? "true" : "false");
+    }
+    return 0;
+}
+
+// g_tiles: the tile-packed copy of g_ao (S1_TILES) or null
+static int half_transform_batched(const double* g_ao, const double* C, int N, int M, double* T2, int batch,
+                                  oovqe_stream_t stream, const Stage1& s, double* Vk_tri = nullptr,
+                                  const double* g_tiles = nullptr)
+{
     OOVQE_REQUIRE(g_ao && C && T2, "cas_half_transform: null pointer");
-    OOVQE_REQUIRE(!Vk_tri || (sym == SYM_MIRROR && N <= 48),
+    OOVQE_REQUIRE(!Vk_tri || (s.sym == SYM_MIRROR && N <= 48),
                   "cas_half_transform: the quarter-transformed output needs p<->q symmetric integrals and N <= 48");
     OOVQE_REQUIRE(batch >= 1 && batch <= 65535, "cas_half_transform: batch=%d", batch);
-    OOVQE_REQUIRE(N >= 1 && M >= 1 && M <= N, "cas_half_transform: bad N=%d M=%d", N, M);
+    OOVQE_REQUIRE(s.kernel != S1_TILES || g_tiles, "cas_half_transform: no tile-packed integrals");
     hipStream_t st = (hipStream_t)stream;
-    const int ZT = (M + 15) / 16;
+    const int ZT = s.zt, sym = s.sym;
     const int nrb = (N + 15) / 16;
-    const int ksteps = (N + 3) / 4;
-    const int LDM = 16 * (ZT | 1);
-    const size_t lds_elems = (((size_t)nrb * 16 * LDM + 511) / 512) * 512;   // padded, see kernel
-    const size_t lds_bytes = lds_elems * sizeof(double);
-    OOVQE_REQUIRE(ZT <= 3, "cas_half_transform: n_occ+ncas = %d > 48 not supported", M);
-    OOVQE_REQUIRE(lds_bytes <= 160 * 1024, "cas_half_transform: N=%d M=%d needs %zu B of LDS", N, M,
-                  lds_bytes);
     const long nslabs = sym == SYM_FULL ? (long)N * N : (long)N * (N + 1) / 2;
-    // k-steps per register chunk: the whole row when it fits (<= 16 k-steps), else chunks of 16
-    int kch = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : ksteps <= 11 ? 11 : ksteps <= 12 ? 12 : 16;
-#define OOVQE_LAUNCH_HALF(Z, KC_, NS_)                                                            \
+    const long want = (nslabs + HALF_WAVES - 1) / HALF_WAVES;
+    oovqe_note_stage1("%s", s.name);
+    oovqe_profile_mark_start(st);
+    if (s.kernel == S1_HALF) {
+#define OOVQE_LAUNCH_HALF(KC_, NS_, NPC_, Z)                                                      \
     do {                                                                                          \
-        oovqe_note_stage1("half_transform_kernel<%d,%d,%d>%s", Z, KC_, NS_, sym ? " (slabs p <= q)" : ""); \
         const unsigned wpg = 4u;                                          /* waves per workgroup */      \
         hipLaunchKernelGGL((half_transform_kernel<Z, KC_, NS_>),                                  \
                            dim3((unsigned)((nslabs + wpg - 1) / wpg), batch), dim3(wpg * 64),     \
                            0, st, g_ao, C, T2, N, M, nslabs, sym, Vk_tri);                        \
     } while (0)
-#define OOVQE_DISPATCH_KCH(Z)                                                                     \
-    do {                                                                                          \
-        /* whole-slab preload when the slab is one k-chunk deep and <= 48 loads per lane */      \
-        if (kch == 4 && nrb == 1) OOVQE_LAUNCH_HALF(Z, 4, 1);                                     \
-        else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_HALF(Z, 8, 2);                                \
-        else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_HALF(Z, 11, 3);                              \
-        else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_HALF(Z, 12, 3);                              \
-        else {                                                                                    \
-            oovqe_set_error("cas_half_transform: no half_transform variant for N=%d", N);         \
-            return OOVQE_ERR_ARG;                                                                 \
-        }                                                                                         \
-    } while (0)
-    // N > 48: persistent streaming kernel.  k-chunk depth with the least padding (ties: deeper)
-    if (nrb > 3) {
-        int skch = 16, waste = 1 << 30;
-        for (int k = 16; k >= 10; --k) {
-            const int w = (ksteps + k - 1) / k * k - ksteps;
-            if (w < waste) { waste = w; skch = k; }
-        }
-        const int snkc = (ksteps + skch - 1) / skch;
-        const long want = (nslabs + HALF_WAVES - 1) / HALF_WAVES;
-        // r <-> s symmetric slabs: upper tile triangle only (needs a 16 x 17 patch per wave in LDS)
-        const size_t lds_rs = lds_bytes + (size_t)HALF_WAVES * 16 * 17 * sizeof(double);
-        const bool use_rs = rs && lds_rs <= 160 * 1024;
-        if (g_tiles && use_rs && sym == SYM_MIRROR) {
-            // both flags and a resident tile-packed copy: half_tiles_kernel streams that instead
-            const long slab_doubles = (long)nrb * (nrb + 1) / 2 * 256;
+        if (ZT == 1) OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_HALF, 1)
+        else if (ZT == 2) OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_HALF, 2)
+        else OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_HALF, 3)
+#undef OOVQE_LAUNCH_HALF
+    } else if (s.kernel == S1_TILES) {
+        const long slab_doubles = (long)nrb * (nrb + 1) / 2 * 256;
+        const size_t lds_rs = half_lds_bytes_rs(N, M);
 #define OOVQE_LAUNCH_TILES(Z, D_, A_)                                                             \
     do {                                                                                          \
         const void* fn = (const void*)half_tiles_kernel<Z, D_, A_>;                               \
@@ -3271,42 +3310,38 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
         long per = (long)oovqe_cu_count() / batch;      /* one workgroup per CU (LDS) */         \
         if (per < 1) per = 1;                                                                     \
         if (per > want) per = want;                                                               \
-        oovqe_note_stage1("half_tiles_kernel<%d,%d>", Z, D_);                                     \
         hipLaunchKernelGGL((half_tiles_kernel<Z, D_, A_>), dim3((unsigned)per, batch),            \
                            dim3(HALF_WAVES * 64), lds_rs, st, g_tiles, C, T2, N, M, nrb, nslabs,  \
                            nslabs * slab_doubles);                                                \
     } while (0)
-            oovqe_profile_mark_start(st);
-            if (ZT == 1) OOVQE_LAUNCH_TILES(1, 8, AUX_NT);
-            else if (ZT == 3) OOVQE_LAUNCH_TILES(3, 4, AUX_NT);
-            else OOVQE_LAUNCH_TILES(2, 8, AUX_NT);   // (N = 200, M = 26: 833 us per evaluation; ring of 6: 860-920, of 4: 858; default cache policy: 900)
-            oovqe_profile_mark_stop(st);
+        if (ZT == 1) OOVQE_LAUNCH_TILES(1, tiles_depth(1), AUX_NT);
+        else if (ZT == 3) OOVQE_LAUNCH_TILES(3, tiles_depth(3), AUX_NT);
+        else OOVQE_LAUNCH_TILES(2, tiles_depth(2), AUX_NT);
 #undef OOVQE_LAUNCH_TILES
-            OOVQE_CHECK_LAUNCH("cas_half_transform/tiles");
-            return 0;
-        }
+    } else {
+        const int snkc = ((N + 3) / 4 + s.skch - 1) / s.skch;
 #define OOVQE_LAUNCH_STREAM(Z, KC_, D_)                                                           \
     do {                                                                                          \
-        if (use_rs) OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, true, lds_rs);                             \
-        else OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, false, lds_bytes);                                \
+        if (s.rs) OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, true, half_lds_bytes_rs(N, M));              \
+        else OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, false, half_lds_bytes(N, M));                     \
     } while (0)
-#define OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, RS_, lds_bytes)                                        \
+#define OOVQE_LAUNCH_STREAM_RS(Z, KC_, D_, RS_, lds_bytes_)                                       \
     do {                                                                                          \
         const void* fn = (const void*)half_stream_kernel<Z, KC_, D_, RS_>;                        \
+        const size_t lds_bytes = lds_bytes_;                                                      \
         if (int rc_ = oovqe_ensure_dynamic_lds(fn, 160 * 1024)) return rc_;                       \
         const int occ = oovqe_blocks_per_cu(fn, HALF_WAVES * 64, lds_bytes);                      \
         if (occ < 0) return occ;                                                                  \
         long per = ((long)occ * oovqe_cu_count()) / batch;                                        \
         if (per < 1) per = 1;                                                                     \
         if (per > want) per = want;                                                               \
-        oovqe_note_stage1("half_stream_kernel<%d,%d,%d,%s>", Z, KC_, D_, RS_ ? "true" : "false"); \
         hipLaunchKernelGGL((half_stream_kernel<Z, KC_, D_, RS_>), dim3((unsigned)per, batch),     \
                            dim3(HALF_WAVES * 64), lds_bytes, st, g_ao, C, T2, N, M, nrb, snkc,    \
                            nslabs, sym);                                                          \
     } while (0)
 #define OOVQE_DISPATCH_STREAM(Z, D_)                                                              \
     do {                                                                                          \
-        switch (skch) {                                                                           \
+        switch (s.skch) {                                                                         \
         case 10: OOVQE_LAUNCH_STREAM(Z, 10, D_); break;                                           \
         case 11: OOVQE_LAUNCH_STREAM(Z, 11, D_); break;                                           \
         case 12: OOVQE_LAUNCH_STREAM(Z, 12, D_); break;                                           \
@@ -3316,26 +3351,24 @@ static int half_transform_batched(const double* g_ao, const double* C, int N, in
         default: OOVQE_LAUNCH_STREAM(Z, 16, D_); break;                                           \
         }                                                                                         \
     } while (0)
-        oovqe_profile_mark_start(st);
-        if (ZT == 1) OOVQE_DISPATCH_STREAM(1, 3);
-        else if (ZT == 2) OOVQE_DISPATCH_STREAM(2, 3);
-        else OOVQE_DISPATCH_STREAM(3, 2);
-        oovqe_profile_mark_stop(st);
+        if (ZT == 1) OOVQE_DISPATCH_STREAM(1, stream_depth(1));
+        else if (ZT == 2) OOVQE_DISPATCH_STREAM(2, stream_depth(2));
+        else OOVQE_DISPATCH_STREAM(3, stream_depth(3));
 #undef OOVQE_DISPATCH_STREAM
 #undef OOVQE_LAUNCH_STREAM
 #undef OOVQE_LAUNCH_STREAM_RS
-        OOVQE_CHECK_LAUNCH("cas_half_transform");
-        return 0;
     }
-    oovqe_profile_mark_start(st);
-    if (ZT == 1) OOVQE_DISPATCH_KCH(1);
-    else if (ZT == 2) OOVQE_DISPATCH_KCH(2);
-    else OOVQE_DISPATCH_KCH(3);
     oovqe_profile_mark_stop(st);
-#undef OOVQE_DISPATCH_KCH
-#undef OOVQE_LAUNCH_HALF
-    OOVQE_CHECK_LAUNCH("cas_half_transform");
+    OOVQE_CHECK_LAUNCH(s.kernel == S1_TILES ? "cas_half_transform/tiles" : "cas_half_transform");
     return 0;
+}
+
+extern "C" int oovqe_cas_half_transform(const double* g_ao, const double* C, int N, int M, double* T2,
+                                        oovqe_stream_t stream)
+{
+    Stage1 s;
+    if (int rc = stage1_half(N, M, SYM_FULL, false, false, &s)) return rc;
+    return half_transform_batched(g_ao, C, N, M, T2, 1, stream, s);
 }
 
 extern "C" int oovqe_eri_symmetry_flags(const double* g_ao, int N, int batch, unsigned* eri_flags,
@@ -3403,15 +3436,14 @@ static int sym_q_contract_batched(const double* J, const double* C, double* T3, 
                                   hipStream_t st)
 {
     OOVQE_REQUIRE(M >= 1 && M <= 16 && N >= 1 && N <= 48, "sym_q_contract: N=%d M=%d", N, M);
+    Stage1Variant v;
+    if (int rc = stage1_variant(N, &v)) return rc;
     const unsigned threads = (unsigned)((M * M + 15) / 16 * 64);
-    const int ksteps = (N + 3) / 4;
-    oovqe_profile_mark_start_l(st, 5);
-    if (ksteps <= 4)
-        hipLaunchKernelGGL(sym_q_contract_kernel<4>, dim3(N, batch), dim3(threads), 0, st, J, C, T3, N, M);
-    else if (ksteps <= 8)
-        hipLaunchKernelGGL(sym_q_contract_kernel<8>, dim3(N, batch), dim3(threads), 0, st, J, C, T3, N, M);
-    else
-        hipLaunchKernelGGL(sym_q_contract_kernel<12>, dim3(N, batch), dim3(threads), 0, st, J, C, T3, N, M);
+    oovqe_profile_mark_start_l(st, LABEL_Q_TO_X);
+#define OOVQE_LAUNCH_Q(KS_) \
+    hipLaunchKernelGGL(sym_q_contract_kernel<KS_>, dim3(N, batch), dim3(threads), 0, st, J, C, T3, N, M)
+    OOVQE_KS_DISPATCH(v, OOVQE_LAUNCH_Q)
+#undef OOVQE_LAUNCH_Q
     oovqe_profile_mark_stop(st);
     OOVQE_CHECK_LAUNCH("cas_eval/sym_q_contract");
     return 0;
@@ -3422,9 +3454,9 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
                           hipStream_t st, const oovqe_circuit_job_t* cj, bool packed)
 {
     OOVQE_REQUIRE(M >= 1 && M <= 16 && N >= 1 && N <= 48, "sym_gm: N=%d M=%d", N, M);
-    const int ksteps = (N + 3) / 4;
-    const int KSr = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : 12;
-    size_t lds_bytes = (size_t)4 * KSr * (M * 16 + 8) * sizeof(double);
+    Stage1Variant v;
+    if (int rc = stage1_variant(N, &v)) return rc;
+    size_t lds_bytes = (size_t)4 * v.ks * (M * 16 + 8) * sizeof(double);
     if (cj && cj->lds_bytes > lds_bytes) lds_bytes = cj->lds_bytes;
     const unsigned nty = (unsigned)(((packed ? M * (M + 1) / 2 : M * M) + 15) / 16);
     oovqe_circuit_job_t job;
@@ -3441,17 +3473,15 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
     } while (0)
     // (measurement hooks: OOVQE_GM_TWO_PER_CU / OOVQE_GM_ONE_PER_CU force a build; 128 geometries:
     // 45 -> 38 us with two per CU, 64 geometries: no difference)
-    const bool multi_round = ((long)(nty + (cj ? 1 : 0)) * batch > (long)oovqe_cu_count() || oovqe_opt(OOVQE_OPT_GM_TWO_PER_CU)) &&
+    const bool multi_round = ((long)nx * batch > (long)oovqe_cu_count() || oovqe_opt(OOVQE_OPT_GM_TWO_PER_CU)) &&
                              2 * lds_bytes <= 160 * 1024 && oovqe_opt(OOVQE_OPT_GM_ONE_PER_CU) == 0;
 #define OOVQE_LAUNCH_GM(KS_)                                                                      \
     do {                                                                                          \
         if (multi_round) OOVQE_LAUNCH_GM2(KS_, 4);                                                \
         else OOVQE_LAUNCH_GM2(KS_, 2);                                                            \
     } while (0)
-    oovqe_profile_mark_start_l(st, 2);
-    if (KSr == 4) OOVQE_LAUNCH_GM(4);
-    else if (KSr == 8) OOVQE_LAUNCH_GM(8);
-    else OOVQE_LAUNCH_GM(12);
+    oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
+    OOVQE_KS_DISPATCH(v, OOVQE_LAUNCH_GM)
     oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_GM
 #undef OOVQE_LAUNCH_GM2
@@ -3463,16 +3493,16 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
 static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* NC)
 {
     const int M = no + na, M3 = M * M * M;
-    if (N > 48 || M > 16) return 0;
+    Stage1Variant v;
+    if (N > 48 || M > 16 || stage1_variant(N, &v)) return 0;
     int nc = 0;
     for (int x = 0; x < M; ++x)
         for (int y = 0; y < M; ++y)
             for (int z = y; z < M; ++z) nc += tail_needed(x, y, z, no) ? 1 : 0;
     *NC = nc;
-    const int ksteps = (N + 3) / 4, KSr = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : 12;
     const size_t na2 = (size_t)na * na, na4 = na2 * na2;
     size_t scr = (size_t)N * N;                                           // W
-    const size_t t3 = (size_t)4 * KSr * (M * 16 + 8);                     // T3s
+    const size_t t3 = (size_t)4 * v.ks * (M * 16 + 8);                    // T3s
     const size_t fe = (size_t)nrdm * M * N + (size_t)nrdm * N +           // Fcol + Epart + Ga + Dc
                       (size_t)N * na * na * na + (size_t)N * no * na2;
     if (t3 > scr) scr = t3;
@@ -3484,55 +3514,40 @@ static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* 
 }
 
 // the tail of the packed-triangle path in one launch, one workgroup per geometry (cas_tail_kernel)
-static int cas_tail_batched(const double* J, const double* C, const double* Wpre, const double* gamma,
-                            const double* Gamma, int nrdm, double nuc, const double* nuc_arr, int N, int n_occ,
-                            int ncas, const int32_t* kap_row, const int32_t* kap_col, int n_kappa, double* c0,
-                            double* c1, double* c2, double* E, double* gvec, double* dE, int batch,
-                            size_t out_stride, hipStream_t st)
+static int cas_tail_batched(const CasEvalArgs& a, const EvalPlan& p, const double* J, const double* Wpre, hipStream_t st)
 {
-    int NC = 0;
-    const size_t lds_bytes = tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &NC);
-    OOVQE_REQUIRE(lds_bytes > 0, "cas_eval/tail: N=%d M=%d nrdm=%d does not fit", N, n_occ + ncas, nrdm);
-    const int ksteps = (N + 3) / 4;
+    Stage1Variant v;
+    if (int rc = stage1_variant(a.N, &v)) return rc;
 #define OOVQE_LAUNCH_TAIL(KS_)                                                                    \
     do {                                                                                          \
-        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)cas_tail_kernel<KS_>, lds_bytes)) return rc_; \
-        hipLaunchKernelGGL((cas_tail_kernel<KS_>), dim3(batch), dim3(TAIL_THREADS), lds_bytes, st, J, C, Wpre, \
-                           gamma, Gamma, nrdm, N, n_occ, ncas, NC, nuc, nuc_arr, kap_row, kap_col, n_kappa, c0, \
-                           E, gvec, dE, c1, c2, out_stride);                                      \
+        if (int rc_ = oovqe_ensure_dynamic_lds((const void*)cas_tail_kernel<KS_>, p.tail_lds)) return rc_; \
+        hipLaunchKernelGGL((cas_tail_kernel<KS_>), dim3(a.batch), dim3(TAIL_THREADS), p.tail_lds, st, J, a.C, Wpre, \
+                           a.gamma, a.Gamma, a.nrdm, a.N, a.n_occ, a.ncas, p.tail_nc, a.nuc, a.nuc_arr, a.kap_row, \
+                           a.kap_col, a.n_kappa, a.out.c0, a.out.E, a.out.gvec, a.out.dE, a.out.c1, a.out.c2,       \
+                           a.out_stride);                                                         \
     } while (0)
-    oovqe_profile_mark_start_l(st, 2);
-    if (ksteps <= 4) OOVQE_LAUNCH_TAIL(4);
-    else if (ksteps <= 8) OOVQE_LAUNCH_TAIL(8);
-    else OOVQE_LAUNCH_TAIL(12);
+    oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
+    OOVQE_KS_DISPATCH(v, OOVQE_LAUNCH_TAIL)
     oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_TAIL
     OOVQE_CHECK_LAUNCH("cas_eval/tail");
     return 0;
 }
 
-// Plan of the fused stage-1 + q->x kernel for `batch` geometries: number of q chunks, slots per
-// chunk, LDS ring.  Returns false when the shape is outside the kernel (M > 16, N > 48, no room
-// for two ring blocks, workspace) -- the caller then takes the T2 path.
-struct FusedPlan {
-    int nchunk, qc, nbuf, ldb, wpg;
-    size_t lds_bytes;
-};
-
-static bool fused_plan(int N, int M, int batch, FusedPlan* fp)
+// Plan of the fused stage-1 + q -> x kernel for `batch` geometries on n_cu CUs.  Returns false when the shape is
+// outside the kernel (M > 16, N > 48, no room for two ring blocks, workspace) or the sweep too small to pay off.
+// chunks_opt: option fused_chunks = n forces n chunks of the q range (and the fused path)
+static bool fused_plan(int N, int M, int batch, int n_cu, long chunks_opt, FusedPlan* fp)
 {
     if (M > 16 || N > 48 || N < 1) return false;
-    // test hook: option fused_chunks = n forces n chunks of the q range (and the fused path)
-    const long chunks_env = oovqe_opt(OOVQE_OPT_FUSED_CHUNKS);
     const long m2 = (long)M * M, m3 = m2 * M;
-    const int n_cu = oovqe_cu_count();
     // The persistent kernel pays off once the sweep is bandwidth-bound (>= ~6 slabs per wave on
     // every CU); below that the one-slab-per-wave T2 kernels have the shorter latency
     // (measured crossover at N = 43: 7-8 geometries).
-    if (chunks_env <= 0 && (long)batch * N * N < 48L * n_cu) return false;
+    if (chunks_opt <= 0 && (long)batch * N * N < 48L * n_cu) return false;
     // tasks (chunk, p) per geometry: about one workgroup's worth per CU when geometries are few
     long target = n_cu / batch;
-    long nchunk0 = chunks_env > 0 ? chunks_env : target / N;
+    long nchunk0 = chunks_opt > 0 ? chunks_opt : target / N;
     if (nchunk0 < 1) nchunk0 = 1;
     // T3 [nchunk][N][M^3] + Gm [N][M^3] + Cdup [nchunk][N][N] share the 2 N^2 M^2 workspace
     const long cap = (2L * N * m2 - m3) / (m3 + N);
@@ -3571,27 +3586,18 @@ static bool fused_plan(int N, int M, int batch, FusedPlan* fp)
 }
 
 static int half_transform_fused_batched(const double* g_ao, const double* C, int N, int M, double* T3,
-                                        double* Cdup, const FusedPlan& fp, int batch, hipStream_t st)
+                                        double* Cdup, const FusedPlan& fp, const Stage1& s, int batch, hipStream_t st)
 {
-    const int ksteps = (N + 3) / 4, nrb = (N + 15) / 16;
-    const int kch = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : ksteps <= 11 ? 11 : 12;
-#define OOVQE_LAUNCH_FUSED(KC_, NS_)                                                              \
+#define OOVQE_LAUNCH_FUSED(KC_, NS_, NPC_)                                                        \
     do {                                                                                          \
         if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)half_transform_fused_kernel<KC_, NS_>, 160 * 1024)) return rc_lds; \
-        oovqe_note_stage1("half_transform_fused_kernel<%d,%d>", KC_, NS_);                        \
         hipLaunchKernelGGL((half_transform_fused_kernel<KC_, NS_>), dim3(fp.wpg, batch),          \
                            dim3(HALF_WAVES * 64), fp.lds_bytes, st, g_ao, C, T3, Cdup, N, M,      \
                            fp.nchunk, fp.qc, fp.nbuf, fp.ldb);                                    \
     } while (0)
+    oovqe_note_stage1("%s", s.name);
     oovqe_profile_mark_start(st);
-    if (kch == 4 && nrb == 1) OOVQE_LAUNCH_FUSED(4, 1);
-    else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_FUSED(8, 2);
-    else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_FUSED(11, 3);
-    else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_FUSED(12, 3);
-    else {
-        oovqe_set_error("cas_eval: no fused half-transform variant for N=%d", N);
-        return OOVQE_ERR_ARG;
-    }
+    OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_FUSED)
     oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_FUSED
     OOVQE_CHECK_LAUNCH("cas_eval/half_transform_fused");
@@ -3630,13 +3636,13 @@ extern "C" int oovqe_eri_pack(const double* g_ao, int N, int batch, double* pack
 
 // Packed-triangle stage 1 (p <-> q symmetric integrals, M <= 16, N <= 48): J [G][N(N+1)/2][M^2].
 static int half_tri_batched(const double* g_ao, const double* C, int N, int M, double* J, int batch,
-                            hipStream_t st, int tiled = 0, bool packed_src = false)
+                            hipStream_t st, const Stage1& s)
 {
-    // packed_src: g_ao is the copy made by oovqe_eri_pack (tiled == 2 only)
+    // S1_TRI_REG: g_ao is the copy made by oovqe_eri_pack (tiled == 2 only)
+    const int tiled = s.tiled;
+    const bool packed_src = s.kernel == S1_TRI_REG;
     OOVQE_REQUIRE(!packed_src || tiled == 2, "cas_eval: packed integrals need both symmetry flags");
     OOVQE_REQUIRE(M >= 1 && M <= 16 && N >= M && N <= 48, "cas_eval: half_tri N=%d M=%d", N, M);
-    const int ksteps = (N + 3) / 4, nrb = (N + 15) / 16;
-    const int kch = ksteps <= 4 ? 4 : ksteps <= 8 ? 8 : ksteps <= 11 ? 11 : 12;
     const long tri = (long)N * (N + 1) / 2;
     // Workgroups per geometry (one 8-wave workgroup is resident per CU).  When the batch divides
     // the CU count, W = n_cu / batch fills the chip in one resident round.  Otherwise a larger W
@@ -3660,12 +3666,11 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
     const size_t round_bytes = (size_t)HALF_WAVES * M * M * sizeof(double);
     const size_t fixed_bytes = (64 + 128) * sizeof(double);   // dump + column table
     if (packed_src) {
-        // the packed copy: contiguous register loads, R = 3 slabs per wave in flight; pieces of 1 KB per
-        // slab for the largest N of each variant: N <= 16 / 32 / 44 / 48
-        const int npc = kch == 4 ? 2 : kch == 8 ? 5 : kch == 11 ? 8 : 10;
+        // the packed copy: contiguous register loads, R = 3 slabs per wave in flight
+        const int npc = s.v.npc;
         OOVQE_REQUIRE((size_t)npc * 1024 >= eri_slab_packed_elems(N) * sizeof(double),
                       "cas_eval: half_tri_reg slab of N=%d exceeds %d KB", N, npc);
-        constexpr int R = 3;
+        constexpr int R = TRI_REG_R;
         const size_t slot_bytes = (size_t)HALF_WAVES * npc * 1024;
         long ph = (long)((160 * 1024 - fixed_bytes - slot_bytes) / round_bytes) / R * R;
         OOVQE_REQUIRE(ph >= R, "cas_eval: half_tri_reg staging does not fit LDS (M=%d)", M);
@@ -3675,20 +3680,13 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
 #define OOVQE_LAUNCH_TRI_REG(KC_, NS_, NPC_)                                                      \
     do {                                                                                          \
         if (int rc_ = oovqe_ensure_dynamic_lds((const void*)half_tri_reg_kernel<KC_, NS_, NPC_, R>, 160 * 1024)) return rc_; \
-        oovqe_note_stage1("half_tri_reg_kernel<%d,%d,%d,%d>", KC_, NS_, NPC_, R);                 \
         hipLaunchKernelGGL((half_tri_reg_kernel<KC_, NS_, NPC_, R>), dim3((unsigned)W, batch),    \
                            dim3(HALF_WAVES * 64), lds_reg, st, g_ao, C, J, N, M, (int)ph);        \
     } while (0)
         if (int rc_s1 = oovqe_stage1_enter(st)) return rc_s1;
+        oovqe_note_stage1("%s", s.name);
         oovqe_profile_mark_start(st);
-        if (kch == 4 && nrb == 1) OOVQE_LAUNCH_TRI_REG(4, 1, 2);
-        else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_TRI_REG(8, 2, 5);
-        else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_TRI_REG(11, 3, 8);
-        else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_TRI_REG(12, 3, 10);
-        else {
-            oovqe_set_error("cas_eval: no half_tri_reg variant for N=%d", N);
-            return OOVQE_ERR_ARG;
-        }
+        OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_TRI_REG)
         oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_TRI_REG
         OOVQE_CHECK_LAUNCH("cas_eval/half_tri_reg");
@@ -3701,25 +3699,18 @@ static int half_tri_batched(const double* g_ao, const double* C, int N, int M, d
 #define OOVQE_LAUNCH_TRI2(KC_, NS_, RS_)                                                          \
     do {                                                                                          \
         if (int rc_ = oovqe_ensure_dynamic_lds((const void*)half_tri_kernel<KC_, NS_, RS_>, 160 * 1024)) return rc_; \
-        oovqe_note_stage1("half_tri_kernel<%d,%d,%d>", KC_, NS_, RS_);                            \
         hipLaunchKernelGGL((half_tri_kernel<KC_, NS_, RS_>), dim3((unsigned)W, batch),            \
                            dim3(HALF_WAVES * 64), lds_bytes, st, g_ao, C, J, N, M, (int)phase,    \
                            tiled);                                                                \
     } while (0)
-#define OOVQE_LAUNCH_TRI(KC_, NS_)                                                                \
+#define OOVQE_LAUNCH_TRI(KC_, NS_, NPC_)                                                          \
     do {                                                                                          \
         if (tiled == 2) OOVQE_LAUNCH_TRI2(KC_, NS_, 1);                                           \
         else OOVQE_LAUNCH_TRI2(KC_, NS_, 0);                                                      \
     } while (0)
+    oovqe_note_stage1("%s", s.name);
     oovqe_profile_mark_start(st);
-    if (kch == 4 && nrb == 1) OOVQE_LAUNCH_TRI(4, 1);
-    else if (kch == 8 && nrb == 2) OOVQE_LAUNCH_TRI(8, 2);
-    else if (kch == 11 && nrb == 3) OOVQE_LAUNCH_TRI(11, 3);
-    else if (kch == 12 && nrb == 3) OOVQE_LAUNCH_TRI(12, 3);
-    else {
-        oovqe_set_error("cas_eval: no half_tri variant for N=%d", N);
-        return OOVQE_ERR_ARG;
-    }
+    OOVQE_STAGE1_DISPATCH(s.v, OOVQE_LAUNCH_TRI)
     oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_TRI
 #undef OOVQE_LAUNCH_TRI2
@@ -3858,308 +3849,401 @@ static bool column_fits(int N, int M, int ncas)
     return column_base_bytes(N, M) + (na2 + na2 * na2) * sizeof(double) <= 160 * 1024;
 }
 
-// Batched CAS path: `batch` geometries of identical shape, every per-geometry array stacked.
-// Outputs c0/c1/c2/E/gvec/dE of geometry g live at pointer + g * out_stride (doubles).
-// Where the circuit launch of an evaluation may leave W = C^T h_ao [G][N][N] for the panel kernel: the T3 block of
-// the packed-triangle path's workspace, which its one-launch q -> x / p -> n kernel does not use.  False when the
-// call will not take that path (the decision tree of cas_eval_batched below).
-extern "C" int64_t oovqe_oo_eval_out_size(int n_theta, int n_kappa, int ncas, int derivatives);
-
-static bool cas_w_block(int N, int M, int batch, unsigned eri_flags, double* work, double** W)
+// the kernels for N <= 48 that do not write T2: T3 of the fused path (S1_FUSED) or the packed triangle J, tiled 0 =
+// row-major [tri][M^2], 1 = tile-major, 2 = tile-major with the columns y <= z only (r <-> s symmetric integrals);
+// S1_TRI_REG: from the packed copy of the integrals (tiled == 2)
+static Stage1 stage1_small(Stage1Kernel kernel, const Stage1Variant& v, int tiled)
 {
-    if (N > 48 || oovqe_opt(OOVQE_OPT_CAS_UNFUSED) != 0 || oovqe_opt(OOVQE_OPT_SYM_MIRROR) != 0 ||
-        oovqe_opt(OOVQE_OPT_SYM_SIMPLE) != 0 || oovqe_opt(OOVQE_OPT_SYM_TWO_STEP) != 0 ||
-        oovqe_opt(OOVQE_OPT_PANEL_NO_W) != 0 || (eri_flags & OOVQE_ERI_PQ_SYMMETRIC) == 0)
-        return false;
-    FusedPlan fp;
-    if (!fused_plan(N, M, batch, &fp)) return false;
-    const long m2 = (long)M * M, m3 = m2 * M;
-    const long tri = (long)N * (N + 1) / 2;
-    const long nty16 = (m2 + 15) / 16 * 16;
-    if (tri * nty16 + 2 * (long)N * m3 > 2 * (long)N * N * m2) return false;
-    *W = work + (size_t)batch * tri * nty16;
-    return true;
+    Stage1 s{};
+    s.kernel = kernel;
+    s.v = v;
+    s.tiled = tiled;
+    if (kernel == S1_FUSED) snprintf(s.name, sizeof(s.name), "half_transform_fused_kernel<%d,%d>", v.kch, v.nrb);
+    else if (kernel == S1_TRI_REG) snprintf(s.name, sizeof(s.name), "half_tri_reg_kernel<%d,%d,%d,%d>", v.kch, v.nrb, v.npc, TRI_REG_R);
+    else snprintf(s.name, sizeof(s.name), "half_tri_kernel<%d,%d,%d>", v.kch, v.nrb, tiled == 2 ? 1 : 0);
+    return s;
 }
 
-static int cas_eval_batched(const double* g_ao, const double* h_ao, const double* C,
-                            const double* gamma, const double* Gamma, int nrdm, double nuc,
-                            const double* nuc_arr, int N, int n_occ, int ncas, const int32_t* kap_row,
-                            const int32_t* kap_col, int n_kappa, double* work, double* c0, double* c1,
-                            double* c2, double* E, double* gvec, double* dE, double* fock,
-                            double* gmat, double* Gm, double* hmo, int batch, size_t out_stride,
-                            oovqe_stream_t stream, const oovqe_circuit_job_t* cj = nullptr,
-                            unsigned eri_flags = 0, const double* g_packed = nullptr,
-                            const double* T2_ready = nullptr, bool w_ready = false, hipEvent_t rdm_event = nullptr)
+EvalOpts oovqe_eval_opts()
 {
-    // rdm_event: recorded on the stream where gamma / Gamma are complete when the circuit rides along (cj): behind the
-    // q -> x / p -> n launch -- another stream of the caller (the orbital Hessian's assembly) waits for the RDMs, not
-    // for the end of this call
-    // w_ready: the caller's circuit launch has left W = C^T h_ao [G][N][N] in this workspace's T3 block
-    // (cas_w_block: packed-triangle path, one-launch q -> x / p -> n kernel)
-    // T2_ready [G][N][N][M][M]: the caller has stage 1's result in memory (the Hessian call); the
-    // packed-triangle path then builds its J from it instead of reading the integrals again
-    // cj: circuit + RDM evaluations that produce gamma / Gamma; they ride along the p -> n
-    // contraction launch (the caller has checked oovqe_contract_hosts_circuit for this shape)
-    OOVQE_REQUIRE(g_ao && h_ao && C && gamma && Gamma && work && c0 && c1 && c2 && E && gvec,
-                  "cas_eval: null pointer");
-    OOVQE_REQUIRE(nrdm >= 1 && N >= 1 && n_occ >= 0 && ncas >= 1 && n_occ + ncas <= N,
+    return EvalOpts{.fused_chunks = oovqe_opt(OOVQE_OPT_FUSED_CHUNKS), .no_ride = oovqe_opt(OOVQE_OPT_NO_RIDE),
+                    .cas_unfused = oovqe_opt(OOVQE_OPT_CAS_UNFUSED) != 0, .sym_no_rs = oovqe_opt(OOVQE_OPT_SYM_NO_RS) != 0,
+                    .sym_mirror = oovqe_opt(OOVQE_OPT_SYM_MIRROR) != 0, .sym_simple = oovqe_opt(OOVQE_OPT_SYM_SIMPLE) != 0,
+                    .sym_two_step = oovqe_opt(OOVQE_OPT_SYM_TWO_STEP) != 0, .panel_no_w = oovqe_opt(OOVQE_OPT_PANEL_NO_W) != 0,
+                    .tail_split = oovqe_opt(OOVQE_OPT_TAIL_SPLIT) != 0, .k1 = oovqe_contract_opts()};
+}
+
+int oovqe_eval_plan(const EvalShape& s, EvalPlan* plan)
+{
+    EvalPlan& p = *plan;
+    memset(&p, 0, sizeof(p));
+    OOVQE_REQUIRE(s.nrdm >= 1 && s.N >= 1 && s.n_occ >= 0 && s.ncas >= 1 && s.n_occ + s.ncas <= s.N,
                   "cas_eval: bad sizes");
-    OOVQE_REQUIRE(n_kappa == 0 || (kap_row && kap_col), "cas_eval: null index table");
-    OOVQE_REQUIRE(nrdm == 1 || dE, "cas_eval: dE required when nrdm > 1");
-    OOVQE_REQUIRE(batch >= 1 && batch <= 65535, "cas_eval: batch=%d", batch);
-    hipStream_t st = (hipStream_t)stream;
-    const int M = n_occ + ncas;
+    OOVQE_REQUIRE(s.batch >= 1 && s.batch <= 65535, "cas_eval: batch=%d", s.batch);
+    OOVQE_REQUIRE(s.n_cu >= 1, "cas_eval: n_cu=%d", s.n_cu);
+    const EvalOpts& o = s.opt;
+    const int N = s.N, M = s.n_occ + s.ncas, batch = s.batch, nrdm = s.nrdm;
     const long m2 = (long)M * M, m3 = m2 * M;
-    // workspace layout (each block stacked over the batch)
-    const size_t nb = (size_t)batch;
-    double* T2 = work;                                   // [G][N][N][M][M]
-    double* U = T2 + nb * N * N * m2;                    // [G][N][N][M][M]
-    double* Fcol = U + nb * N * N * m2;                  // [G][nrdm][M][N]
-    double* Epart = Fcol + nb * nrdm * M * N;            // [G][nrdm][N]
-    double* Cpart = Epart + nb * nrdm * N;               // [G][N]
-    int rc;
-    // fused path: T3 = stage 1 + q -> x in one kernel, then the small p -> n contraction gives
-    // g_mo[n,x,y,z] directly; T2 path (M > 16 or N > 48): T2, U = C^T T2, q -> x in the column kernel
-    const bool unfused_env = oovqe_opt(OOVQE_OPT_CAS_UNFUSED) != 0;   // test hook, read per call
-    FusedPlan fp;
-    const bool fused = !unfused_env && fused_plan(N, M, batch, &fp);
-    const double* Gm_in = nullptr;
-    const double* Wpre = nullptr;
-    // p <-> q symmetric integrals (verified by the caller): only the slabs p <= q are read
-    const bool pq_sym = (eri_flags & OOVQE_ERI_PQ_SYMMETRIC) != 0;
-    // r <-> s symmetric as well: J[p,q,y,z] == J[p,q,z,y], the packed path keeps the columns y <= z
-    const bool rs_sym = (eri_flags & OOVQE_ERI_RS_SYMMETRIC) != 0 && oovqe_opt(OOVQE_OPT_SYM_NO_RS) == 0;
-    const int half_sym = pq_sym ? SYM_MIRROR : SYM_FULL;
     const long tri = (long)N * (N + 1) / 2;
     const long nty16 = (m2 + 15) / 16 * 16;               // tile-major J rows are padded to 16
-    const bool sym_packed = fused && pq_sym && oovqe_opt(OOVQE_OPT_SYM_MIRROR) == 0 &&
-                            tri * nty16 + 2 * (long)N * m3 <= 2 * (long)N * N * m2;
-    if (sym_packed) {
-        // packed triangle J (instead of the fused kernel: its q -> x contraction needs whole rows
-        // of slabs), then the small q -> x kernel; from T3 on the same launches as the fused path
-        double* Jp = work;                                       // [G][tri][M^2] or [G][nty][tri][16]
-        double* T3 = Jp + nb * tri * nty16;                      // [G][N][M^3]
-        double* Gmw = T3 + nb * N * m3;                          // [G][N][M^3]
-        // test hooks: OOVQE_SYM_SIMPLE = the one-slab-per-wave kernel (direct stores) instead of the
-        // persistent one; OOVQE_SYM_TWO_STEP = q -> x kernel, then K1, instead of the one-launch
-        // kernel (both on the row-major J)
-        const bool simple = oovqe_opt(OOVQE_OPT_SYM_SIMPLE) != 0;
-        const bool two_step = simple || oovqe_opt(OOVQE_OPT_SYM_TWO_STEP) != 0;
-        if (simple) {
-            if ((rc = half_transform_batched(g_ao, C, N, M, Jp, batch, stream, SYM_PACKED))) return rc;
-        } else {
-            // the packed copy of the integrals (oovqe_eri_pack) is streamed when the caller holds one
-            const bool use_pk = !two_step && rs_sym && g_packed != nullptr;
-            if (T2_ready && !two_step) {
-                const unsigned nbk = (unsigned)((tri + 15) / 16);       // 16 rows of the triangle per workgroup
-                oovqe_profile_mark_start_l(st, 0);
-                hipLaunchKernelGGL(j_from_t2_kernel, dim3(nbk, batch), dim3(256), 0, st, T2_ready, Jp, N, M,
-                                   rs_sym ? 1 : 0);
-                oovqe_profile_mark_stop(st);
-                OOVQE_CHECK_LAUNCH("cas_eval/j_from_t2");
-            } else if ((rc = half_tri_batched(use_pk ? g_packed : g_ao, C, N, M, Jp, batch, st,
-                                              two_step ? 0 : rs_sym ? 2 : 1, use_pk)))
-                return rc;
-        }
-        // the whole tail in one launch of one workgroup per geometry (cas_tail_kernel) when the batch fills at
-        // least half the chip with it, the circuit has run in its own launch (RDMs and W = C^T h in memory) and
-        // nothing beyond the packed outputs is asked for; otherwise sym_gm, panel and final launches
-        int tail_nc = 0;
-        const bool tail = !two_step && rs_sym && g_packed != nullptr && !T2_ready && !cj && w_ready && !fock && !gmat && !Gm && !hmo &&
-                          2L * batch > (long)oovqe_cu_count() && tail_lds_bytes(N, n_occ, ncas, nrdm, n_kappa, &tail_nc) > 0 &&
-                          oovqe_opt(OOVQE_OPT_TAIL_SPLIT) == 0;
-        if (tail) {
-            double* wchk = nullptr;
-            OOVQE_REQUIRE(cas_w_block(N, M, batch, eri_flags, work, &wchk) && wchk == T3,
-                          "cas_eval: W = C^T h was promised for another path");
-            if ((rc = cas_tail_batched(Jp, C, T3, gamma, Gamma, nrdm, nuc, nuc_arr, N, n_occ, ncas, kap_row, kap_col,
-                                       n_kappa, c0, c1, c2, E, gvec, dE, batch, out_stride, st)))
-                return rc;
-            if (rdm_event) OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");
-            return 0;
-        }
-        if (!two_step) {
-            if ((rc = sym_gm_batched(Jp, C, Gmw, N, M, batch, st, cj, rs_sym))) return rc;
-            if (rdm_event && cj) {
-                OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");
-                rdm_event = nullptr;
+    // p <-> q symmetric integrals (verified by the caller): only the slabs p <= q are read
+    const bool pq = (s.eri_flags & OOVQE_ERI_PQ_SYMMETRIC) != 0;
+    // r <-> s symmetric as well: J[p,q,y,z] == J[p,q,z,y], the packed path keeps the columns y <= z
+    p.rs = (s.eri_flags & OOVQE_ERI_RS_SYMMETRIC) != 0 && !o.sym_no_rs;
+
+    // ---- the path ------------------------------------------------------------------------------------------
+    // fused: T3 = stage 1 + q -> x in one kernel, then the small p -> n contraction gives g_mo[n,x,y,z] directly.
+    // With p <-> q symmetric integrals the packed triangle J takes the fused kernel's place (its q -> x contraction
+    // needs whole rows of slabs) when J, T3 and g_mo fit the 2 N^2 M^2 workspace; from g_mo on the same launches.
+    const bool fused = !o.cas_unfused && fused_plan(N, M, batch, s.n_cu, o.fused_chunks, &p.fused);
+    const bool packed = fused && pq && !o.sym_mirror && tri * nty16 + 2 * (long)N * m3 <= 2 * (long)N * N * m2;
+    // test hooks: sym_simple = the one-slab-per-wave kernel (direct stores) instead of the persistent one;
+    // sym_two_step = q -> x kernel, then K1, instead of the one-launch kernel (both on the row-major J)
+    const bool two_step = o.sym_simple || o.sym_two_step;
+
+    // ---- the circuit ---------------------------------------------------------------------------------------
+    // The circuit + RDM step is independent of the integral transform until the Fock stage.  When it is the
+    // one-workgroup kind and the p -> n contraction of this shape is a single-chunk K1 launch, its workgroups ride
+    // along that launch (one launch and ~12 us of latency less per evaluation); otherwise it has a launch of its
+    // own.  Option no_ride = 1 forces the separate launch.
+    if (s.n_qubits > 0) {
+        p.circuit = CIRCUIT_OWN;
+        p.circuit_small = oovqe_circuit_rdms_is_small(s.n_qubits, s.ncas, nrdm, s.n_gates) != 0;
+        if (p.circuit_small && o.no_ride != 1) {
+            const long K = fused ? (long)p.fused.nchunk * N : N, B = fused ? m3 : (long)N * m2;
+            bool ride = oovqe_small_circuit_lds_bytes(s.n_qubits, s.ncas, nrdm, s.n_gates) <= 64 * 1024 &&
+                        K <= 0x7fffffffL && oovqe_contract_hosts_circuit(1, (int)K, N, B, 0, batch, o.k1);
+            // With p <-> q symmetric integrals the host launch is sym_gm_kernel, two workgroups per CU: the circuit
+            // workgroups are its longest (a latency chain through the gates and the RDM products, slowed further by the
+            // matrix-core workgroups they share a CU with), and once the grid is beyond 1.5 resident rounds they end
+            // the launch alone.  Measured per call (tools/ride_probe.py, riding / own launch): 192 geometries 363.9 /
+            // 370.2 us, 224: 427.8 / 420.6, 256: 471.4 / 464.5, 384: 734.6 / 705.0, 512: 983.4 / 946.9.
+            if (ride && fused && pq && !o.sym_mirror && o.no_ride != 2) {
+                const long ntile = ((p.rs ? (long)M * (M + 1) / 2 : m2) + 15) / 16;
+                if ((ntile + 1) * batch > 3L * s.n_cu) ride = false;
             }
-            if (w_ready) {                                       // (the block this path leaves unused)
-                double* wchk = nullptr;
-                OOVQE_REQUIRE(cas_w_block(N, M, batch, eri_flags, work, &wchk) && wchk == T3,
-                              "cas_eval: W = C^T h was promised for another path");
-                Wpre = T3;
-            }
-        } else {
-            if ((rc = sym_q_contract_batched(Jp, C, T3, N, M, batch, st))) return rc;
-            oovqe_profile_mark_start_l(st, 2);
-            if ((rc = oovqe_mode_contract_batched_circ(T3, C, Gmw, 1, N, N, m3, N, 0, batch, (long)N * m3,
-                                                       (long)N * N, (long)N * m3, st, cj)))
-                return rc;
-            oovqe_profile_mark_stop(st);
+            if (ride) p.circuit = CIRCUIT_RIDES;
         }
-        Gm_in = Gmw;
+    }
+    // the circuit's own launch forms W = C^T h_ao of every geometry with extra workgroups when the panel kernel will
+    // take it: the T3 block, which the one-launch q -> x / p -> n kernels of the packed-triangle path leave unused
+    p.w = packed && !two_step && !o.panel_no_w && p.circuit == CIRCUIT_OWN && p.circuit_small && batch <= 32767;
+    // the whole tail in one launch of one workgroup per geometry (cas_tail_kernel) when the batch fills at least half
+    // the chip with it, the circuit has run in its own launch (RDMs and W in memory) and nothing beyond the packed
+    // outputs is asked for
+    if (p.w && p.rs && s.packed && !s.t2_ready && !s.extras && 2L * batch > (long)s.n_cu && !o.tail_split)
+        p.tail_lds = tail_lds_bytes(N, s.n_occ, s.ncas, nrdm, s.n_kappa, &p.tail_nc);
+    // (behind the T3 block lies g_mo, which only the one-launch tail does not form: W [N][N] must not reach into it)
+    if (p.tail_lds == 0 && N > m3) p.w = false;
+    if (packed)
+        p.path = p.tail_lds > 0 ? PATH_PACKED_TAIL : two_step ? PATH_PACKED_TWO_STEP : PATH_PACKED_SPLIT;
+    else if (fused)
+        p.path = PATH_FUSED;
+    else
+        p.path = column_fits(N, M, s.ncas) ? PATH_COLUMN : PATH_STAGED;
+    OOVQE_REQUIRE(p.path != PATH_STAGED || M < N,
+                  "cas_eval: the staged path needs at least one virtual orbital (N=%d M=%d)", N, M);
+    // (the circuit workgroups cannot ride along the per-geometry launches of the staged path)
+    if (p.path == PATH_STAGED && p.circuit == CIRCUIT_RIDES) p.circuit = CIRCUIT_OWN;
+
+    // ---- stage 1 -------------------------------------------------------------------------------------------
+    Stage1Variant v;
+    if (packed || fused)
+        if (int rc = stage1_variant(N, &v)) return rc;
+    if (!packed && fused) {
+        p.stage1 = stage1_small(S1_FUSED, v, 0);
+    } else if (!packed) {
+        if (int rc = stage1_half(N, M, pq ? SYM_MIRROR : SYM_FULL, p.rs, N > 48 && s.packed, &p.stage1)) return rc;
+    } else if (o.sym_simple) {
+        if (int rc = stage1_half(N, M, SYM_PACKED, false, false, &p.stage1)) return rc;
+    } else if (s.t2_ready && !two_step) {
+        // J from the T2 the caller holds (the Hessian call) instead of reading the integrals again
+        p.stage1.kernel = S1_FROM_T2;
+    } else {
+        // the packed copy of the integrals (oovqe_eri_pack) is streamed when the caller holds one
+        p.stage1 = stage1_small(!two_step && p.rs && s.packed ? S1_TRI_REG : S1_TRI, v, two_step ? 0 : p.rs ? 2 : 1);
+    }
+
+    // ---- the workspace (each block stacked over the batch) -------------------------------------------------
+    const size_t nb = (size_t)batch;
+    size_t at = 0;
+    auto block = [&](WorkBlock b, size_t doubles) { p.off[b] = at; p.len[b] = nb * doubles; at += nb * doubles; };
+    if (packed) {
+        block(WB_JP, (size_t)(tri * nty16));              // [G][tri][M^2] or [G][nty][tri][16]
+        block(WB_T3, (size_t)N * m3);                     // [G][N][M^3] (two-step), W [G][N][N] (p.w), else unused
+        block(WB_GMW, (size_t)N * m3);                    // [G][N][M^3]
+        if (!two_step) p.len[WB_T3] = p.w ? nb * N * N : 0;
     } else if (fused) {
-        double* T3 = work;                                       // [G][nchunk][N][M^3]
-        double* Gmw = T3 + nb * fp.nchunk * N * m3;              // [G][N][M^3]
-        double* Cdup = Gmw + nb * N * m3;                        // [G][nchunk][N][N]  (nchunk > 1)
-        if ((rc = half_transform_fused_batched(g_ao, C, N, M, T3, Cdup, fp, batch, st))) return rc;
-        // Gm[n,(x y z)] = sum_{c,p} C[p,n] T3[c,p,(x y z)]
-        oovqe_profile_mark_start_l(st, 2);
-        const long K = (long)fp.nchunk * N;
-        if ((rc = oovqe_mode_contract_batched_circ(T3, fp.nchunk > 1 ? Cdup : C, Gmw, 1, (int)K, N, m3, N, 0,
-                                                   batch, K * m3, fp.nchunk > 1 ? K * N : (long)N * N,
-                                                   (long)N * m3, st, cj)))
+        block(WB_T3, (size_t)p.fused.nchunk * N * m3);    // [G][nchunk][N][M^3]
+        block(WB_GMW, (size_t)N * m3);                    // [G][N][M^3]
+        if (p.fused.nchunk > 1) block(WB_CDUP, (size_t)p.fused.nchunk * N * N);   // [G][nchunk][N][N]
+        else p.off[WB_CDUP] = at;
+    } else {
+        block(WB_T2, (size_t)N * N * m2);                 // [G][N][N][M][M]
+        block(WB_U, (size_t)N * N * m2);                  // [G][N][N][M][M]
+    }
+    at = 2 * nb * N * N * m2;
+    block(WB_FCOL, (size_t)nrdm * M * N);                 // [G][nrdm][M][N]
+    block(WB_EPART, (size_t)nrdm * N);                    // [G][nrdm][N]
+    block(WB_CPART, (size_t)N);                           // [G][N]
+    if (p.path == PATH_PACKED_TAIL) p.len[WB_GMW] = p.len[WB_FCOL] = p.len[WB_EPART] = p.len[WB_CPART] = 0;
+    if (p.path == PATH_STAGED) {
+        // per geometry: g_mo takes the place of T2, T3 + Y + the Fock scratch live in the U block, h_mo in Fcol
+        p.len[WB_EPART] = p.len[WB_CPART] = 0;
+        p.staged_rows = (size_t)N * m3 + (size_t)N * M + (size_t)nrdm * (M + 1) * N + N <= (size_t)N * N * m2 &&
+                        M <= 64 && fock_rows_lds_elems(s.n_occ, s.ncas) * sizeof(double) <= FROW_LDS_MAX;
+    }
+
+    // ---- what will be launched -----------------------------------------------------------------------------
+    p.labels[LABEL_STAGE1] = 1;
+    p.labels[LABEL_CIRCUIT] = p.circuit == CIRCUIT_OWN ? 1 : 0;
+    p.labels[LABEL_Q_TO_X] = p.path == PATH_PACKED_TWO_STEP ? 1 : 0;
+    p.labels[LABEL_P_TO_N] = p.path == PATH_STAGED ? 0 : 1;
+    p.labels[LABEL_COLUMN] = p.labels[LABEL_FINAL] = p.path == PATH_STAGED || p.path == PATH_PACKED_TAIL ? 0 : 1;
+    // (the general circuit path is three launches inside one bracket; the staged path brackets stage 1 and the circuit only)
+    p.launches = (p.circuit == CIRCUIT_OWN && !p.circuit_small ? 2 : 0) +
+                 (p.path == PATH_STAGED ? (long)batch * (p.staged_rows ? 6 : 5) : 0);
+    for (int l = 0; l < LABEL_COUNT; ++l) p.launches += p.labels[l];
+    return 0;
+}
+
+// panel kernel: stage 3 on panels of npan general indices per workgroup, about one resident round of workgroups;
+// Wpre: W = C^T h_ao [G][N][N] from the circuit launch, or null (the kernel then stages h_ao and forms its rows itself)
+static int cas_panel_batched(const CasEvalArgs& a, const EvalPlan& p, const double* Wpre, hipStream_t st)
+{
+    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
+    const size_t m3 = (size_t)M * M * M, na2 = (size_t)a.ncas * a.ncas;
+    const size_t set_bytes = (na2 + na2 * na2) * sizeof(double);
+    const size_t lds_cap = 160 * 1024;
+    const size_t fixed_bytes = ((size_t)N * M + (Wpre ? 0 : (size_t)N * N)) * sizeof(double);
+    const size_t per_n = (m3 + (Wpre ? 1 : 2) * (size_t)N + 2 * (size_t)M) * sizeof(double);
+    OOVQE_REQUIRE(fixed_bytes + per_n + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS",
+                  N, M, fixed_bytes + per_n + set_bytes);
+    long npan = ((long)N * batch + 383) / 384;
+    const long npan_max = (long)((lds_cap - fixed_bytes - set_bytes) / per_n);
+    if (npan > npan_max) npan = npan_max;
+    if (npan > 8) npan = 8;   // (two workgroups per CU: 40 us against 47 us with panels of 16 at 256 geometries)
+    if (Wpre) {
+        // without h_ao in LDS a panel of this many general indices leaves room for THREE workgroups per CU
+        // (N = 43, M = 9: 7 indices, 51 KB; 39 -> 31 us at 256 geometries)
+        const long n3 = (long)((lds_cap / 3 - fixed_bytes - set_bytes) / per_n);
+        if (n3 >= 4 && n3 < npan) npan = n3;
+    }
+    if (oovqe_opt(OOVQE_OPT_PANEL_ROWS) > 0) npan = oovqe_opt(OOVQE_OPT_PANEL_ROWS);   // measurement hook
+    if (npan < 1) npan = 1;
+    int rdm_chunk = (int)((lds_cap - fixed_bytes - (size_t)npan * per_n) / set_bytes);
+    if (rdm_chunk > a.nrdm) rdm_chunk = a.nrdm;
+    const size_t lds_bytes = fixed_bytes + (size_t)npan * per_n + (size_t)rdm_chunk * set_bytes;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_panel_kernel, lds_cap)) return rc_lds;
+    oovqe_profile_mark_start_l(st, LABEL_COLUMN);
+    const unsigned npanels = (unsigned)((N + npan - 1) / npan);
+    const bool xcd_grid = batch > 1 && oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) == 0;
+    hipLaunchKernelGGL(cas_panel_kernel,
+                       xcd_grid ? dim3(npanels * (unsigned)((batch + 7) / 8 * 8)) : dim3(npanels, batch),
+                       dim3(PAN_THREADS), lds_bytes, st, a.work + p.off[WB_GMW], a.h_ao, a.C, a.gamma, a.Gamma, a.nrdm,
+                       N, a.n_occ, a.ncas, (int)npan, a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART],
+                       a.work + p.off[WB_CPART], a.out.c1, a.out.c2, a.Gm, a.hmo, a.out_stride, rdm_chunk,
+                       xcd_grid ? batch : 0, Wpre);
+    oovqe_profile_mark_stop(st);
+    OOVQE_CHECK_LAUNCH("cas_eval/panel");
+    return 0;
+}
+
+// column kernel: q -> x and stage 3 per general index on U = C^T T2
+static int cas_column_batched(const CasEvalArgs& a, const EvalPlan& p, hipStream_t st)
+{
+    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
+    const size_t na2 = (size_t)a.ncas * a.ncas;
+    const size_t set_bytes = (na2 + na2 * na2) * sizeof(double);
+    const size_t lds_cap = 160 * 1024;
+    const size_t base_bytes = column_base_bytes(N, M);
+    OOVQE_REQUIRE(base_bytes + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS", N, M,
+                  base_bytes + set_bytes);
+    int rdm_chunk = (int)((lds_cap - base_bytes) / set_bytes);
+    if (rdm_chunk > a.nrdm) rdm_chunk = a.nrdm;
+    const size_t lds_bytes = base_bytes + (size_t)rdm_chunk * set_bytes;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_column_kernel, lds_cap)) return rc_lds;
+    oovqe_profile_mark_start_l(st, LABEL_COLUMN);
+    // many large RDM sets (a derivative evaluation of a big active space): their chunks are dealt to
+    // zsplit workgroups per n, about one resident round of workgroups in all
+    int zsplit = 1;
+    if (a.ncas * a.ncas * a.ncas >= 128 && rdm_chunk > 0) {
+        const int nchunks = (a.nrdm + rdm_chunk - 1) / rdm_chunk;
+        zsplit = (int)((long)oovqe_cu_count() * 2 / ((long)N * batch));
+        if (zsplit > nchunks) zsplit = nchunks;
+        if (zsplit > 64) zsplit = 64;
+        if (zsplit < 1) zsplit = 1;
+    }
+    hipLaunchKernelGGL(cas_column_kernel, dim3(N, batch, zsplit), dim3(COL_THREADS), lds_bytes, st,
+                       a.work + p.off[WB_U], a.h_ao, a.C, a.gamma, a.Gamma, a.nrdm, N, a.n_occ, a.ncas,
+                       a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART], a.work + p.off[WB_CPART], a.out.c1, a.out.c2,
+                       a.Gm, a.hmo, a.out_stride, rdm_chunk);
+    oovqe_profile_mark_stop(st);
+    OOVQE_CHECK_LAUNCH("cas_eval/column");
+    return 0;
+}
+
+// Large N * M^2 (many occupied orbitals): neither U[n] nor the panel fits LDS.  Staged path per geometry:
+// T2 (batched) -> K1: q -> x, p -> n -> g_mo[n,x,y,z] and h_mo in memory -> fock_kernel (one workgroup per RDM set,
+// streaming g_mo from L2) or the rows kernels.  Same outputs.
+static int cas_eval_staged(const CasEvalArgs& a, const EvalPlan& p)
+{
+    const int N = a.N, M = a.n_occ + a.ncas, nrdm = a.nrdm;
+    const size_t m2 = (size_t)M * M, m3 = m2 * M;
+    int rc;
+    if ((rc = half_transform_batched(a.g_ao, a.C, N, M, a.work + p.off[WB_T2], a.batch, a.stream, p.stage1, nullptr,
+                                     a.g_packed)))
+        return rc;
+    const size_t na2s = (size_t)a.ncas * a.ncas, na4s = na2s * na2s;
+    for (int g = 0; g < a.batch; ++g) {
+        const size_t gi = (size_t)g;
+        double* T2g = a.work + p.off[WB_T2] + gi * N * N * m2;
+        double* wk = a.work + p.off[WB_U] + gi * N * N * m2;           // T3 [N][M^3] + Y [N][M]
+        double* Gmg = T2g;                                             // T2 of this geometry is dead after q -> x
+        double* hmog = a.work + p.off[WB_FCOL] + gi * nrdm * M * N;    // [N][M]
+        if ((rc = oovqe_cas_finish_transform(T2g, a.h_ao + gi * N * N, a.C + gi * N * N, N, M, Gmg, hmog, wk, a.stream)))
             return rc;
-        oovqe_profile_mark_stop(st);
-        Gm_in = Gmw;
-    } else if (!column_fits(N, M, ncas)) {
-        // Large N * M^2 (many occupied orbitals): neither U[n] nor the panel fits LDS.  Staged path
-        // per geometry: T2 (batched) -> K1: q -> x, p -> n -> g_mo[n,x,y,z] and h_mo in memory ->
-        // fock_kernel (one workgroup per RDM set, streaming g_mo from L2).  Same outputs.
-        OOVQE_REQUIRE(M < N, "cas_eval: the staged path needs at least one virtual orbital (N=%d M=%d)", N, M);
-        if (cj) {   // the circuit workgroups cannot ride along here: own launch
-            if ((rc = oovqe_circuit_rdms(cj->theta, cj->n_theta, cj->gates, cj->n_gates, cj->n_qubits,
-                                         cj->ncas, cj->init_index, cj->n_tan > 0, batch, nullptr, nullptr,
-                                         cj->gamma, cj->Gamma, nullptr, stream)))
-                return rc;
-        }
-        if ((rc = half_transform_batched(g_ao, C, N, M, T2, batch, stream, half_sym, rs_sym, nullptr,
-                                         N > 48 ? g_packed : nullptr)))
-            return rc;
-        const size_t na2s = (size_t)ncas * ncas, na4s = na2s * na2s;
-        for (int g = 0; g < batch; ++g) {
-            const size_t gi = (size_t)g;
-            double* T2g = T2 + gi * N * N * m2;
-            double* wk = U + gi * N * N * m2;                  // T3 [N][M^3] + Y [N][M]
-            double* Gmg = T2g;                                 // T2 of this geometry is dead after q -> x
-            double* hmog = Fcol + gi * nrdm * M * N;           // [N][M]
-            if ((rc = oovqe_cas_finish_transform(T2g, h_ao + gi * N * N, C + gi * N * N, N, M, Gmg, hmog,
-                                                 wk, stream)))
-                return rc;
+        const double* gam = a.gamma + gi * nrdm * na2s;
+        const double* Gam = a.Gamma + gi * nrdm * na4s;
+        const double* nuc_g = a.nuc_arr ? a.nuc_arr + g : nullptr;
+        const size_t og = gi * a.out_stride;
+        double* fock_g = a.fock ? a.fock + gi * N * N : nullptr;
+        double* gmat_g = a.gmat ? a.gmat + gi * N * N : nullptr;
+        double* dE_g = a.out.dE ? a.out.dE + og : nullptr;
+        if (p.staged_rows) {
             // scratch behind T3 and Y in this geometry's U block (N^2 M^2 >= N M^3 + N M + the three below)
             double* Fc = wk + (size_t)N * m3 + (size_t)N * M;
             double* Ep = Fc + (size_t)nrdm * M * N;
             double* Cp = Ep + (size_t)nrdm * N;
-            const bool rows_fit = (size_t)N * m3 + (size_t)N * M + (size_t)nrdm * (M + 1) * N + N <=
-                                  (size_t)N * N * m2 && M <= 64 &&
-                                  fock_rows_lds_elems(n_occ, ncas) * sizeof(double) <= FROW_LDS_MAX;
-            if (rows_fit)
-                rc = cas_energy_gradient_rows(
-                    Gmg, hmog, gamma + gi * nrdm * na2s, Gamma + gi * nrdm * na4s, nrdm, nuc,
-                    nuc_arr ? nuc_arr + g : nullptr, N, n_occ, ncas, kap_row, kap_col, n_kappa, Fc, Ep, Cp,
-                    c0 + gi * out_stride, c1 + gi * out_stride, c2 + gi * out_stride, E + gi * out_stride,
-                    fock ? fock + gi * N * N : nullptr, gmat ? gmat + gi * N * N : nullptr,
-                    gvec + gi * out_stride, dE ? dE + gi * out_stride : nullptr, stream);
-            else
-                rc = cas_energy_gradient_impl(
-                    Gmg, hmog, gamma + gi * nrdm * na2s, Gamma + gi * nrdm * na4s, nrdm, nuc,
-                    nuc_arr ? nuc_arr + g : nullptr, N, n_occ, ncas, kap_row, kap_col, n_kappa,
-                    c0 + gi * out_stride, c1 + gi * out_stride, c2 + gi * out_stride, E + gi * out_stride,
-                    fock ? fock + gi * N * N : nullptr, gmat ? gmat + gi * N * N : nullptr,
-                    gvec + gi * out_stride, dE ? dE + gi * out_stride : nullptr, stream);
-            if (rc) return rc;
-            if (Gm)
-                OOVQE_CHECK_HIP(hipMemcpyAsync(Gm + gi * N * m3, Gmg, (size_t)N * m3 * sizeof(double),
-                                               hipMemcpyDeviceToDevice, st), "cas_eval: copy g_mo");
-            if (hmo)
-                OOVQE_CHECK_HIP(hipMemcpyAsync(hmo + gi * N * M, hmog, (size_t)N * M * sizeof(double),
-                                               hipMemcpyDeviceToDevice, st), "cas_eval: copy h_mo");
+            rc = cas_energy_gradient_rows(Gmg, hmog, gam, Gam, nrdm, a.nuc, nuc_g, N, a.n_occ, a.ncas, a.kap_row,
+                                          a.kap_col, a.n_kappa, Fc, Ep, Cp, a.out.c0 + og, a.out.c1 + og, a.out.c2 + og,
+                                          a.out.E + og, fock_g, gmat_g, a.out.gvec + og, dE_g, a.stream);
+        } else {
+            rc = cas_energy_gradient_impl(Gmg, hmog, gam, Gam, nrdm, a.nuc, nuc_g, N, a.n_occ, a.ncas, a.kap_row,
+                                          a.kap_col, a.n_kappa, a.out.c0 + og, a.out.c1 + og, a.out.c2 + og,
+                                          a.out.E + og, fock_g, gmat_g, a.out.gvec + og, dE_g, a.stream);
         }
-        return 0;
-    } else {
-        if ((rc = half_transform_batched(g_ao, C, N, M, T2, batch, stream, half_sym, rs_sym, nullptr,
-                                         N > 48 ? g_packed : nullptr)))
+        if (rc) return rc;
+        if (a.Gm)
+            OOVQE_CHECK_HIP(hipMemcpyAsync(a.Gm + gi * N * m3, Gmg, (size_t)N * m3 * sizeof(double),
+                                           hipMemcpyDeviceToDevice, (hipStream_t)a.stream), "cas_eval: copy g_mo");
+        if (a.hmo)
+            OOVQE_CHECK_HIP(hipMemcpyAsync(a.hmo + gi * N * M, hmog, (size_t)N * M * sizeof(double),
+                                           hipMemcpyDeviceToDevice, (hipStream_t)a.stream), "cas_eval: copy h_mo");
+    }
+    return 0;
+}
+
+// Launches the evaluation the plan describes (same shape, flags and buffers the plan was made for).
+static int cas_eval_batched(const CasEvalArgs& a, const EvalPlan& p)
+{
+    OOVQE_REQUIRE(a.g_ao && a.h_ao && a.C && a.gamma && a.Gamma && a.work && a.out.c0 && a.out.c1 && a.out.c2 &&
+                  a.out.E && a.out.gvec, "cas_eval: null pointer");
+    OOVQE_REQUIRE(a.n_kappa == 0 || (a.kap_row && a.kap_col), "cas_eval: null index table");
+    OOVQE_REQUIRE(a.nrdm == 1 || a.out.dE, "cas_eval: dE required when nrdm > 1");
+    OOVQE_REQUIRE((p.circuit == CIRCUIT_RIDES) == (a.cj != nullptr), "cas_eval: circuit job and plan disagree");
+    hipStream_t st = (hipStream_t)a.stream;
+    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
+    const long m2 = (long)M * M, m3 = m2 * M;
+    double* const Jp = a.work + p.off[WB_JP];
+    double* const T3 = a.work + p.off[WB_T3];
+    double* const Gmw = a.work + p.off[WB_GMW];
+    hipEvent_t rdm_event = a.rdm_event;
+    int rc;
+    switch (p.path) {
+    case PATH_PACKED_TAIL:
+    case PATH_PACKED_SPLIT:
+    case PATH_PACKED_TWO_STEP:
+        if (p.stage1.kernel == S1_HALF) {
+            if ((rc = half_transform_batched(a.g_ao, a.C, N, M, Jp, batch, a.stream, p.stage1))) return rc;
+        } else if (p.stage1.kernel == S1_FROM_T2) {
+            const unsigned nbk = (unsigned)(((long)N * (N + 1) / 2 + 15) / 16);   // 16 rows of the triangle per workgroup
+            oovqe_profile_mark_start_l(st, LABEL_STAGE1);
+            hipLaunchKernelGGL(j_from_t2_kernel, dim3(nbk, batch), dim3(256), 0, st, a.T2_ready, Jp, N, M, p.rs ? 1 : 0);
+            oovqe_profile_mark_stop(st);
+            OOVQE_CHECK_LAUNCH("cas_eval/j_from_t2");
+        } else if ((rc = half_tri_batched(p.stage1.kernel == S1_TRI_REG ? a.g_packed : a.g_ao, a.C, N, M, Jp, batch, st,
+                                          p.stage1)))
+            return rc;
+        if (p.path == PATH_PACKED_TAIL) {
+            if ((rc = cas_tail_batched(a, p, Jp, T3, st))) return rc;
+            if (rdm_event) OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");
+            return 0;
+        }
+        if (p.path == PATH_PACKED_SPLIT) {
+            if ((rc = sym_gm_batched(Jp, a.C, Gmw, N, M, batch, st, a.cj, p.rs))) return rc;
+            if (rdm_event && a.cj) {
+                OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");
+                rdm_event = nullptr;
+            }
+        } else {
+            if ((rc = sym_q_contract_batched(Jp, a.C, T3, N, M, batch, st))) return rc;
+            oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
+            if ((rc = oovqe_mode_contract_batched(T3, a.C, Gmw, 1, N, N, m3, N, 0, batch, (long)N * m3,
+                                                  (long)N * N, (long)N * m3, st, a.cj)))
+                return rc;
+            oovqe_profile_mark_stop(st);
+        }
+        if ((rc = cas_panel_batched(a, p, p.w ? T3 : nullptr, st))) return rc;
+        break;
+    case PATH_FUSED: {
+        const FusedPlan& fp = p.fused;
+        double* Cdup = a.work + p.off[WB_CDUP];
+        if ((rc = half_transform_fused_batched(a.g_ao, a.C, N, M, T3, Cdup, fp, p.stage1, batch, st))) return rc;
+        // Gm[n,(x y z)] = sum_{c,p} C[p,n] T3[c,p,(x y z)]
+        oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
+        const long K = (long)fp.nchunk * N;
+        if ((rc = oovqe_mode_contract_batched(T3, fp.nchunk > 1 ? Cdup : a.C, Gmw, 1, (int)K, N, m3, N, 0,
+                                              batch, K * m3, fp.nchunk > 1 ? K * N : (long)N * N,
+                                              (long)N * m3, st, a.cj)))
+            return rc;
+        oovqe_profile_mark_stop(st);
+        if ((rc = cas_panel_batched(a, p, nullptr, st))) return rc;
+        break;
+    }
+    case PATH_COLUMN:
+        if ((rc = half_transform_batched(a.g_ao, a.C, N, M, a.work + p.off[WB_T2], batch, a.stream, p.stage1, nullptr,
+                                         a.g_packed)))
             return rc;
         // U[n,(q y z)] = sum_p C[p,n] T2[p,(q y z)]
-        oovqe_profile_mark_start_l(st, 2);
-        if ((rc = oovqe_mode_contract_batched_circ(T2, C, U, 1, N, N, (long)N * m2, N, 0, batch,
-                                                   (long)N * N * m2, (long)N * N, (long)N * N * m2, st,
-                                                   cj)))
+        oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
+        if ((rc = oovqe_mode_contract_batched(a.work + p.off[WB_T2], a.C, a.work + p.off[WB_U], 1, N, N,
+                                              (long)N * m2, N, 0, batch, (long)N * N * m2, (long)N * N,
+                                              (long)N * N * m2, st, a.cj)))
             return rc;
         oovqe_profile_mark_stop(st);
+        if ((rc = cas_column_batched(a, p, st))) return rc;
+        break;
+    case PATH_STAGED:
+        return cas_eval_staged(a, p);
     }
-    const size_t na2 = (size_t)ncas * ncas;
-    const size_t set_bytes = (na2 + na2 * na2) * sizeof(double);
-    const size_t lds_cap = 160 * 1024;
-    if (fused || sym_packed) {
-        // panel kernel: npan general indices per workgroup, about one resident round of workgroups
-        const size_t fixed_bytes = ((size_t)N * M + (Wpre ? 0 : (size_t)N * N)) * sizeof(double);
-        const size_t per_n = ((size_t)m3 + (Wpre ? 1 : 2) * (size_t)N + 2 * (size_t)M) * sizeof(double);
-        OOVQE_REQUIRE(fixed_bytes + per_n + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS",
-                      N, M, fixed_bytes + per_n + set_bytes);
-        long npan = ((long)N * batch + 383) / 384;
-        const long npan_max = (long)((lds_cap - fixed_bytes - set_bytes) / per_n);
-        if (npan > npan_max) npan = npan_max;
-        if (npan > 8) npan = 8;   // (two workgroups per CU: 40 us against 47 us with panels of 16 at 256 geometries)
-        if (Wpre) {
-            // without h_ao in LDS a panel of this many general indices leaves room for THREE workgroups per CU
-            // (N = 43, M = 9: 7 indices, 51 KB; 39 -> 31 us at 256 geometries)
-            const long n3 = (long)((lds_cap / 3 - fixed_bytes - set_bytes) / per_n);
-            if (n3 >= 4 && n3 < npan) npan = n3;
-        }
-        if (oovqe_opt(OOVQE_OPT_PANEL_ROWS) > 0) npan = oovqe_opt(OOVQE_OPT_PANEL_ROWS);   // measurement hook
-        if (npan < 1) npan = 1;
-        int rdm_chunk = (int)((lds_cap - fixed_bytes - (size_t)npan * per_n) / set_bytes);
-        if (rdm_chunk > nrdm) rdm_chunk = nrdm;
-        const size_t lds_bytes = fixed_bytes + (size_t)npan * per_n + (size_t)rdm_chunk * set_bytes;
-        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_panel_kernel, lds_cap)) return rc_lds;
-        oovqe_profile_mark_start_l(st, 3);
-        const unsigned npanels = (unsigned)((N + npan - 1) / npan);
-        const bool xcd_grid = batch > 1 && oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) == 0;
-        hipLaunchKernelGGL(cas_panel_kernel,
-                           xcd_grid ? dim3(npanels * (unsigned)((batch + 7) / 8 * 8)) : dim3(npanels, batch),
-                           dim3(PAN_THREADS), lds_bytes, st, Gm_in, h_ao, C, gamma, Gamma, nrdm, N, n_occ,
-                           ncas, (int)npan, Fcol, Epart, Cpart, c1, c2, Gm, hmo, out_stride, rdm_chunk,
-                           xcd_grid ? batch : 0, Wpre);
-        oovqe_profile_mark_stop(st);
-        OOVQE_CHECK_LAUNCH("cas_eval/panel");
-    } else {
-        const size_t base_bytes = ((size_t)N * m2 + (size_t)N * M + m3 + N + M + M + N + (size_t)4 * N) *
-                                  sizeof(double);
-        OOVQE_REQUIRE(base_bytes + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS", N, M,
-                      base_bytes + set_bytes);
-        int rdm_chunk = (int)((lds_cap - base_bytes) / set_bytes);
-        if (rdm_chunk > nrdm) rdm_chunk = nrdm;
-        const size_t lds_bytes = base_bytes + (size_t)rdm_chunk * set_bytes;
-        if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_column_kernel, lds_cap)) return rc_lds;
-        oovqe_profile_mark_start_l(st, 3);
-        // many large RDM sets (a derivative evaluation of a big active space): their chunks are dealt to
-        // zsplit workgroups per n, about one resident round of workgroups in all
-        int zsplit = 1;
-        if (ncas * ncas * ncas >= 128 && rdm_chunk > 0) {
-            const int nchunks = (nrdm + rdm_chunk - 1) / rdm_chunk;
-            zsplit = (int)((long)oovqe_cu_count() * 2 / ((long)N * batch));
-            if (zsplit > nchunks) zsplit = nchunks;
-            if (zsplit > 64) zsplit = 64;
-            if (zsplit < 1) zsplit = 1;
-        }
-        hipLaunchKernelGGL(cas_column_kernel, dim3(N, batch, zsplit), dim3(COL_THREADS), lds_bytes, st, U, h_ao, C,
-                           gamma, Gamma, nrdm, N, n_occ, ncas, Fcol, Epart, Cpart, c1, c2, Gm, hmo,
-                           out_stride, rdm_chunk);
-        oovqe_profile_mark_stop(st);
-        OOVQE_CHECK_LAUNCH("cas_eval/column");
-    }
-    oovqe_profile_mark_start_l(st, 4);
-    hipLaunchKernelGGL(cas_final_kernel, dim3(batch), dim3(512), 0, st, Fcol, Epart, Cpart, nuc, nrdm,
-                       N, M, kap_row, kap_col, n_kappa, c0, E, gvec, dE, fock, gmat, nuc_arr,
-                       out_stride);
+    oovqe_profile_mark_start_l(st, LABEL_FINAL);
+    hipLaunchKernelGGL(cas_final_kernel, dim3(batch), dim3(512), 0, st, a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART],
+                       a.work + p.off[WB_CPART], a.nuc, a.nrdm, N, M, a.kap_row, a.kap_col, a.n_kappa, a.out.c0, a.out.E,
+                       a.out.gvec, a.out.dE, a.fock, a.gmat, a.nuc_arr, a.out_stride);
     oovqe_profile_mark_stop(st);
     OOVQE_CHECK_LAUNCH("cas_eval/final");
     if (rdm_event) OOVQE_CHECK_HIP(hipEventRecord(rdm_event, st), "cas_eval: hipEventRecord");   // (no earlier point on this path)
     return 0;
 }
 
-extern "C" int oovqe_cas_eval(const double* g_ao, const double* h_ao, const double* C,
-                              const double* gamma, const double* Gamma, int nrdm, double nuc, int N,
-                              int n_occ, int ncas, const int32_t* kap_row, const int32_t* kap_col,
-                              int n_kappa, double* work, double* c0, double* c1, double* c2,
-                              double* E, double* gvec, double* dE, double* fock, double* gmat,
-                              double* Gm, double* hmo, unsigned eri_flags, oovqe_stream_t stream)
+// n_qubits == 0: the RDM sets are given
+static EvalShape eval_shape(const CasEvalArgs& a, int n_qubits, int n_gates)
 {
-    return cas_eval_batched(g_ao, h_ao, C, gamma, Gamma, nrdm, nuc, nullptr, N, n_occ, ncas, kap_row,
-                            kap_col, n_kappa, work, c0, c1, c2, E, gvec, dE, fock, gmat, Gm, hmo, 1, 0,
-                            stream, nullptr, eri_flags);
+    return EvalShape{.N = a.N, .n_occ = a.n_occ, .ncas = a.ncas, .nrdm = a.nrdm, .n_kappa = a.n_kappa, .batch = a.batch,
+                     .eri_flags = a.eri_flags, .packed = a.g_packed != nullptr, .t2_ready = a.T2_ready != nullptr,
+                     .extras = a.fock || a.gmat || a.Gm || a.hmo, .n_qubits = n_qubits, .n_gates = n_gates,
+                     .n_cu = oovqe_cu_count(), .opt = oovqe_eval_opts()};
+}
+
+// the RDM sets are given: plan without a circuit, launch
+static int cas_eval_given_rdms(const CasEvalArgs& a)
+{
+    OOVQE_REQUIRE(!a.g_packed || a.eri_flags == (OOVQE_ERI_PQ_SYMMETRIC | OOVQE_ERI_RS_SYMMETRIC),
+                  "cas_eval: a packed copy needs both symmetry flags");
+    EvalPlan p;
+    if (int rc = oovqe_eval_plan(eval_shape(a, 0, 0), &p)) return rc;
+    return cas_eval_batched(a, p);
 }
 
 extern "C" int oovqe_cas_eval_packed(const double* g_ao, const double* h_ao, const double* C,
@@ -4170,11 +4254,22 @@ extern "C" int oovqe_cas_eval_packed(const double* g_ao, const double* h_ao, con
                                      double* Gm, double* hmo, unsigned eri_flags, const double* g_packed,
                                      oovqe_stream_t stream)
 {
-    OOVQE_REQUIRE(!g_packed || eri_flags == (OOVQE_ERI_PQ_SYMMETRIC | OOVQE_ERI_RS_SYMMETRIC),
-                  "cas_eval: a packed copy needs both symmetry flags");
-    return cas_eval_batched(g_ao, h_ao, C, gamma, Gamma, nrdm, nuc, nullptr, N, n_occ, ncas, kap_row,
-                            kap_col, n_kappa, work, c0, c1, c2, E, gvec, dE, fock, gmat, Gm, hmo, 1, 0,
-                            stream, nullptr, eri_flags, g_packed);
+    const CasEvalArgs a{.g_ao = g_ao, .h_ao = h_ao, .C = C, .gamma = gamma, .Gamma = Gamma, .nrdm = nrdm, .nuc = nuc, .N = N,
+                        .n_occ = n_occ, .ncas = ncas, .kap_row = kap_row, .kap_col = kap_col, .n_kappa = n_kappa,
+                        .work = work, .out = OutSlab{c0, E, dE, gvec, c1, c2}, .fock = fock, .gmat = gmat, .Gm = Gm,
+                        .hmo = hmo, .batch = 1, .stream = stream, .eri_flags = eri_flags, .g_packed = g_packed};
+    return cas_eval_given_rdms(a);
+}
+
+extern "C" int oovqe_cas_eval(const double* g_ao, const double* h_ao, const double* C,
+                              const double* gamma, const double* Gamma, int nrdm, double nuc, int N,
+                              int n_occ, int ncas, const int32_t* kap_row, const int32_t* kap_col,
+                              int n_kappa, double* work, double* c0, double* c1, double* c2,
+                              double* E, double* gvec, double* dE, double* fock, double* gmat,
+                              double* Gm, double* hmo, unsigned eri_flags, oovqe_stream_t stream)
+{
+    return oovqe_cas_eval_packed(g_ao, h_ao, C, gamma, Gamma, nrdm, nuc, N, n_occ, ncas, kap_row, kap_col, n_kappa,
+                                 work, c0, c1, c2, E, gvec, dE, fock, gmat, Gm, hmo, eri_flags, nullptr, stream);
 }
 
 // The CAS path for a STACK of geometries from given RDM sets (the circuit lives elsewhere: the sector engine of large
@@ -4188,20 +4283,12 @@ extern "C" int oovqe_cas_eval_batch(const double* g_ao, const double* h_ao, cons
 {
     OOVQE_REQUIRE(nuc && out, "cas_eval_batch: null pointer");
     OOVQE_REQUIRE(nrdm >= 1 && batch >= 1, "cas_eval_batch: nrdm = %d, batch = %d", nrdm, batch);
-    OOVQE_REQUIRE(!g_packed || eri_flags == (OOVQE_ERI_PQ_SYMMETRIC | OOVQE_ERI_RS_SYMMETRIC),
-                  "cas_eval_batch: a packed copy needs both symmetry flags");
-    const size_t na2 = (size_t)ncas * ncas;
-    const size_t out_stride = (size_t)oovqe_oo_eval_out_size(nrdm - 1, n_kappa, ncas, nrdm > 1);
-    const int n_t = nrdm > 1 ? nrdm - 1 : 1;
-    double* c0 = out;
-    double* E = out + 1;
-    double* dE = out + 2;
-    double* gvec = dE + n_t;
-    double* c1 = gvec + (size_t)nrdm * n_kappa;
-    double* c2 = c1 + na2;
-    return cas_eval_batched(g_ao, h_ao, C, gamma, Gamma, nrdm, 0.0, nuc, N, n_occ, ncas, kap_row, kap_col, n_kappa,
-                            work, c0, c1, c2, E, gvec, dE, fock, nullptr, nullptr, nullptr, batch, out_stride, stream,
-                            nullptr, eri_flags, g_packed);
+    const CasEvalArgs a{.g_ao = g_ao, .h_ao = h_ao, .C = C, .gamma = gamma, .Gamma = Gamma, .nrdm = nrdm, .nuc_arr = nuc,
+                        .N = N, .n_occ = n_occ, .ncas = ncas, .kap_row = kap_row, .kap_col = kap_col, .n_kappa = n_kappa,
+                        .work = work, .out = out_layout(out, nrdm, n_kappa, ncas),
+                        .out_stride = (size_t)oovqe_oo_eval_out_size(nrdm - 1, n_kappa, ncas, nrdm > 1), .fock = fock,
+                        .batch = batch, .stream = stream, .eri_flags = eri_flags, .g_packed = g_packed};
+    return cas_eval_given_rdms(a);
 }
 
 extern "C" int64_t oovqe_cas_eval_work_size(int N, int n_occ, int ncas, int nrdm)
@@ -4233,142 +4320,70 @@ extern "C" int64_t oovqe_oo_eval_out_size(int n_theta, int n_kappa, int ncas, in
     return 2 + n_t + nvec * n_kappa + (int64_t)ncas * ncas + (int64_t)ncas * ncas * ncas * ncas;
 }
 
-// One call = one OO-VQE evaluation for each of `batch` geometries (same circuit, same shapes):
-// circuit (+tangents) -> RDM sets -> CAS path; 5 launches in total, whatever the batch size.
-static int oo_eval_batched(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
-                           int n_qubits, uint32_t init_index, const double* g_ao, const double* h_ao,
-                           const double* C, double nuc, const double* nuc_arr, int N, int n_occ,
-                           int ncas, const int32_t* kap_row, const int32_t* kap_col, int n_kappa,
-                           int derivatives, int batch, double* work, double* out,
-                           unsigned eri_flags, oovqe_stream_t stream, const double* g_packed = nullptr,
-                           double* fock = nullptr, const double* T2_ready = nullptr, hipEvent_t rdm_event = nullptr)
+// 5 launches in total (3 with the one-launch tail), whatever the batch size
+int oovqe_oo_eval_batched_impl(const OoEvalArgs& a)
 {
-    OOVQE_REQUIRE(theta && gates && g_ao && h_ao && C && work && out, "oo_eval: null pointer");
-    OOVQE_REQUIRE(n_qubits == 2 * ncas, "oo_eval: n_qubits != 2*ncas");
-    OOVQE_REQUIRE(batch >= 1, "oo_eval: batch=%d", batch);
-    const int nvec = derivatives ? 1 + n_theta : 1;
-    const size_t nb = (size_t)batch;
-    const size_t D = (size_t)1 << n_qubits;
-    const size_t na2 = (size_t)ncas * ncas, na4 = na2 * na2;
-    double* gamma = work;                                  // [G][nvec][a^2]
-    double* Gamma = gamma + nb * nvec * na2;               // [G][nvec][a^4]
-    double* cas_work = Gamma + nb * nvec * na4;
-    double* rest = cas_work + nb * oovqe_cas_eval_work_size(N, n_occ, ncas, nvec);
-    double *psi = nullptr, *dpsi = nullptr, *rwork = nullptr;
-    if (!oovqe_circuit_rdms_is_small(n_qubits, ncas, nvec, n_gates)) {
-        psi = rest;                                        // [G][D]
-        dpsi = psi + nb * D;                               // [G][n_theta][D]
-        rwork = psi + nb * nvec * D;
-    }
-    // The circuit + RDM step is independent of the integral transform until the Fock stage.  When
-    // it is the one-workgroup kind and the p -> n contraction of this shape is a single-chunk K1
-    // launch, its workgroups ride along that launch (one launch and ~12 us of latency less per
-    // evaluation); otherwise it is launched here.  OOVQE_NO_RIDE=1 forces the separate launch.
+    OOVQE_REQUIRE(a.theta && a.gates && a.cas.g_ao && a.cas.h_ao && a.cas.C && a.work && a.out, "oo_eval: null pointer");
+    OOVQE_REQUIRE(a.n_qubits == 2 * a.cas.ncas, "oo_eval: n_qubits != 2*ncas");
+    OOVQE_REQUIRE(a.cas.batch >= 1, "oo_eval: batch=%d", a.cas.batch);
+    const int nvec = a.derivatives ? 1 + a.n_theta : 1;
+    const size_t nb = (size_t)a.cas.batch;
+    const size_t D = (size_t)1 << a.n_qubits;
+    const size_t na2 = (size_t)a.cas.ncas * a.cas.ncas, na4 = na2 * na2;
+    hipStream_t st = (hipStream_t)a.cas.stream;
+
+    CasEvalArgs c = a.cas;
+    c.gamma = a.work;                                        // [G][nvec][a^2]
+    c.Gamma = c.gamma + nb * nvec * na2;                     // [G][nvec][a^4]
+    c.nrdm = nvec;
+    c.work = a.work + nb * nvec * (na2 + na4);
+    c.out = out_layout(a.out, nvec, c.n_kappa, c.ncas);
+    c.out_stride = (size_t)oovqe_oo_eval_out_size(a.n_theta, c.n_kappa, c.ncas, a.derivatives);
+
+    EvalPlan p;
+    if (int rc = oovqe_eval_plan(eval_shape(c, a.n_qubits, a.n_gates), &p)) return rc;
+
     oovqe_circuit_job_t cj;
-    bool ride = false;
-    if (oovqe_circuit_rdms_is_small(n_qubits, ncas, nvec, n_gates) && oovqe_opt(OOVQE_OPT_NO_RIDE) != 1) {
-        const int M = n_occ + ncas;
-        const long m2 = (long)M * M, m3 = m2 * M;
-        cj.theta = theta;
-        cj.gates = gates;
-        cj.gamma = gamma;
-        cj.Gamma = Gamma;
-        cj.n_theta = n_theta;
-        cj.n_gates = n_gates;
-        cj.n_qubits = n_qubits;
-        cj.ncas = ncas;
-        cj.n_tan = nvec - 1;
-        cj.count = batch;
-        cj.init_index = init_index;
-        cj.lds_bytes = oovqe_small_circuit_lds_bytes(n_qubits, ncas, nvec, n_gates);
-        FusedPlan fp;
-        const bool fused = oovqe_opt(OOVQE_OPT_CAS_UNFUSED) == 0 && fused_plan(N, M, batch, &fp);
-        const long K = fused ? (long)fp.nchunk * N : N, B = fused ? m3 : (long)N * m2;
-        ride = cj.lds_bytes <= 64 * 1024 && K <= 0x7fffffffL &&
-               oovqe_contract_hosts_circuit(1, (int)K, N, B, 0, batch);
-        // On the packed-triangle path the host launch is sym_gm_kernel, two workgroups per CU: the circuit
-        // workgroups are its longest (a latency chain through the gates and the RDM products, slowed further by the
-        // matrix-core workgroups they share a CU with), and once the grid is beyond 1.5 resident rounds they end
-        // the launch alone.  Measured per call (tools/ride_probe.py, riding / own launch): 192 geometries 363.9 /
-        // 370.2 us, 224: 427.8 / 420.6, 256: 471.4 / 464.5, 384: 734.6 / 705.0, 512: 983.4 / 946.9.
-        if (ride && fused && (eri_flags & OOVQE_ERI_PQ_SYMMETRIC) != 0 && oovqe_opt(OOVQE_OPT_SYM_MIRROR) == 0 &&
-            oovqe_opt(OOVQE_OPT_NO_RIDE) != 2) {
-            const bool rs = (eri_flags & OOVQE_ERI_RS_SYMMETRIC) != 0 && oovqe_opt(OOVQE_OPT_SYM_NO_RS) == 0;
-            const long ntile = ((rs ? (long)M * (M + 1) / 2 : m2) + 15) / 16;
-            if ((ntile + 1) * batch > 3L * oovqe_cu_count()) ride = false;
+    if (p.circuit == CIRCUIT_RIDES) {
+        cj = oovqe_circuit_job_t{.theta = a.theta, .gates = a.gates, .gamma = const_cast<double*>(c.gamma),
+                                 .Gamma = const_cast<double*>(c.Gamma), .n_theta = a.n_theta, .n_gates = a.n_gates,
+                                 .n_qubits = a.n_qubits, .ncas = a.cas.ncas, .n_tan = nvec - 1, .count = a.cas.batch,
+                                 .init_index = a.init_index,
+                                 .lds_bytes = oovqe_small_circuit_lds_bytes(a.n_qubits, a.cas.ncas, nvec, a.n_gates)};
+        c.cj = &cj;
+    } else {
+        // the circuit as a launch of its own (with W = C^T h_ao of every geometry from extra workgroups, p.w)
+        double *psi = nullptr, *dpsi = nullptr, *rwork = nullptr;
+        if (!p.circuit_small) {
+            psi = c.work + nb * oovqe_cas_eval_work_size(a.cas.N, a.cas.n_occ, a.cas.ncas, nvec);   // [G][D]
+            dpsi = psi + nb * D;                                                         // [G][n_theta][D]
+            rwork = psi + nb * nvec * D;
         }
-    }
-    bool w_ready = false;
-    if (!ride) {
-        // the circuit as a launch of its own: W = C^T h_ao of every geometry comes from extra workgroups of that
-        // launch when the panel kernel will take it (packed-triangle path, small circuit, T2 not from a caller)
-        double* Wpre = nullptr;
-        if (oovqe_circuit_rdms_is_small(n_qubits, ncas, nvec, n_gates) && batch <= 32767)
-            w_ready = cas_w_block(N, n_occ + ncas, batch, eri_flags, cas_work, &Wpre);
-        oovqe_profile_mark_start_l((hipStream_t)stream, 1);
-        int rc = oovqe_circuit_rdms_w(theta, n_theta, gates, n_gates, n_qubits, ncas, init_index,
-                                      derivatives, batch, psi, derivatives ? dpsi : nullptr, gamma, Gamma,
-                                      rwork, w_ready ? h_ao : nullptr, w_ready ? C : nullptr, N,
-                                      w_ready ? Wpre : nullptr, stream);
+        oovqe_profile_mark_start_l(st, LABEL_CIRCUIT);
+        int rc = oovqe_circuit_rdms_w(a.theta, a.n_theta, a.gates, a.n_gates, a.n_qubits, a.cas.ncas, a.init_index,
+                                      a.derivatives, a.cas.batch, psi, a.derivatives ? dpsi : nullptr,
+                                      const_cast<double*>(c.gamma), const_cast<double*>(c.Gamma), rwork,
+                                      p.w ? a.cas.h_ao : nullptr, p.w ? a.cas.C : nullptr, a.cas.N,
+                                      p.w ? c.work + p.off[WB_T3] : nullptr, a.cas.stream);
         if (rc) return rc;
-        oovqe_profile_mark_stop((hipStream_t)stream);
-        if (rdm_event) {                                  // the RDMs are complete behind the circuit's own launch
-            OOVQE_CHECK_HIP(hipEventRecord(rdm_event, (hipStream_t)stream), "oo_eval: hipEventRecord");
-            rdm_event = nullptr;
+        oovqe_profile_mark_stop(st);
+        if (c.rdm_event) {                                // the RDMs are complete behind the circuit's own launch
+            OOVQE_CHECK_HIP(hipEventRecord(c.rdm_event, st), "oo_eval: hipEventRecord");
+            c.rdm_event = nullptr;
         }
     }
-    // packed output per geometry: [c0 | E | dE (max(nvec-1,1)) | gvec (nvec x n_kappa) | c1 | c2]
-    const size_t out_stride = (size_t)oovqe_oo_eval_out_size(n_theta, n_kappa, ncas, derivatives);
-    const int n_t = nvec > 1 ? nvec - 1 : 1;
-    double* c0 = out;
-    double* E = out + 1;
-    double* dE = out + 2;
-    double* gvec = dE + n_t;
-    double* c1 = gvec + (size_t)nvec * n_kappa;
-    double* c2 = c1 + na2;
-    return cas_eval_batched(g_ao, h_ao, C, gamma, Gamma, nvec, nuc, nuc_arr, N, n_occ, ncas, kap_row,
-                            kap_col, n_kappa, cas_work, c0, c1, c2, E, gvec, dE, fock, nullptr,
-                            nullptr, nullptr, batch, out_stride, stream, ride ? &cj : nullptr, eri_flags,
-                            g_packed, T2_ready, w_ready, rdm_event);
+    return cas_eval_batched(c, p);
 }
 
-// hessian.hip (oovqe_oo_hessian_batch): the batched evaluation with the generalized Fock matrices
-// [G][N][N] as an extra output; the RDM sets stay at the head of `work` (gamma [G][nvec][a^2], then
-// Gamma [G][nvec][a^4]) for the orbital-Hessian stage that follows.
-int oovqe_oo_eval_batched_impl(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
-                               int n_qubits, uint32_t init_index, const double* g_ao, const double* h_ao,
-                               const double* C, const double* nuc_arr, int N, int n_occ, int ncas,
-                               const int32_t* kap_row, const int32_t* kap_col, int n_kappa, int derivatives,
-                               int batch, double* work, double* out, unsigned eri_flags,
-                               oovqe_stream_t stream, const double* g_packed, double* fock,
-                               const double* T2_ready, hipEvent_t rdm_event)
-{
-    return oo_eval_batched(theta, n_theta, gates, n_gates, n_qubits, init_index, g_ao, h_ao, C, 0.0, nuc_arr,
-                           N, n_occ, ncas, kap_row, kap_col, n_kappa, derivatives, batch, work, out,
-                           eri_flags, stream, g_packed, fock, T2_ready, rdm_event);
-}
-
-// hessian.hip: stage 1 (T2[p,q,y,z]) for a stack of geometries, reading only the slabs p <= q when the
-// caller vouches for the p<->q symmetry
+// hessian.hip: stage 1 (T2[p,q,y,z]) for a stack of geometries
 int oovqe_half_transform_batched_impl(const double* g_ao, const double* C, int N, int M, double* T2,
                                       int batch, unsigned eri_flags, oovqe_stream_t stream, double* Vk_tri)
 {
-    // Vk_tri [G][N(N+1)/2][N][M] (optional; p <-> q symmetric integrals, N <= 48): see half_transform_kernel
     const bool pq = (eri_flags & OOVQE_ERI_PQ_SYMMETRIC) != 0;
     const bool rs = (eri_flags & OOVQE_ERI_RS_SYMMETRIC) != 0 && oovqe_opt(OOVQE_OPT_SYM_NO_RS) == 0;
-    return half_transform_batched(g_ao, C, N, M, T2, batch, stream, pq ? SYM_MIRROR : SYM_FULL, rs, Vk_tri);
-}
-
-extern "C" int oovqe_oo_eval(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
-                             int n_qubits, uint32_t init_index, const double* g_ao,
-                             const double* h_ao, const double* C, double nuc, int N, int n_occ,
-                             int ncas, const int32_t* kap_row, const int32_t* kap_col, int n_kappa,
-                             int derivatives, double* work, double* out, unsigned eri_flags,
-                             oovqe_stream_t stream)
-{
-    return oo_eval_batched(theta, n_theta, gates, n_gates, n_qubits, init_index, g_ao, h_ao, C, nuc,
-                           nullptr, N, n_occ, ncas, kap_row, kap_col, n_kappa, derivatives, 1, work,
-                           out, eri_flags, stream);
+    Stage1 s;
+    if (int rc = stage1_half(N, M, pq ? SYM_MIRROR : SYM_FULL, rs, false, &s)) return rc;
+    return half_transform_batched(g_ao, C, N, M, T2, batch, stream, s, Vk_tri);
 }
 
 extern "C" int oovqe_oo_eval_batch(const double* theta, int n_theta, const oovqe_gate_t* gates,
@@ -4379,9 +4394,66 @@ extern "C" int oovqe_oo_eval_batch(const double* theta, int n_theta, const oovqe
                                    unsigned eri_flags, const double* g_packed, oovqe_stream_t stream)
 {
     OOVQE_REQUIRE(nuc, "oo_eval_batch: null nuc");
-    return oo_eval_batched(theta, n_theta, gates, n_gates, n_qubits, init_index, g_ao, h_ao, C, 0.0,
-                           nuc, N, n_occ, ncas, kap_row, kap_col, n_kappa, derivatives, batch, work,
-                           out, eri_flags, stream, g_packed);
+    return oovqe_oo_eval_batched_impl(OoEvalArgs{
+        .theta = theta, .n_theta = n_theta, .gates = gates, .n_gates = n_gates, .n_qubits = n_qubits,
+        .init_index = init_index, .derivatives = derivatives, .work = work, .out = out,
+        .cas = {.g_ao = g_ao, .h_ao = h_ao, .C = C, .nuc_arr = nuc, .N = N, .n_occ = n_occ, .ncas = ncas,
+                .kap_row = kap_row, .kap_col = kap_col, .n_kappa = n_kappa, .batch = batch, .stream = stream,
+                .eri_flags = eri_flags, .g_packed = g_packed}});
+}
+
+extern "C" int oovqe_oo_eval(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
+                             int n_qubits, uint32_t init_index, const double* g_ao,
+                             const double* h_ao, const double* C, double nuc, int N, int n_occ,
+                             int ncas, const int32_t* kap_row, const int32_t* kap_col, int n_kappa,
+                             int derivatives, double* work, double* out, unsigned eri_flags,
+                             oovqe_stream_t stream)
+{
+    return oovqe_oo_eval_batched_impl(OoEvalArgs{
+        .theta = theta, .n_theta = n_theta, .gates = gates, .n_gates = n_gates, .n_qubits = n_qubits,
+        .init_index = init_index, .derivatives = derivatives, .work = work, .out = out,
+        .cas = {.g_ao = g_ao, .h_ao = h_ao, .C = C, .nuc = nuc, .N = N, .n_occ = n_occ, .ncas = ncas,
+                .kap_row = kap_row, .kap_col = kap_col, .n_kappa = n_kappa, .batch = 1, .stream = stream,
+                .eri_flags = eri_flags}});
+}
+
+// The plan of a call as one line, without launching anything (include/oovqe.h has the format).
+extern "C" const char* oovqe_oo_eval_plan_describe(int n_theta, int n_gates, int n_qubits, int N, int n_occ,
+                                                   int ncas, int n_kappa, int derivatives, int batch,
+                                                   unsigned eri_flags, int have_packed)
+{
+    static thread_local char line[512];
+    static const char* const path_names[] = {"packed_tail", "packed_split", "packed_two_step", "fused", "column", "staged"};
+    static const char* const circuit_names[] = {"none", "rides", "own"};
+    static const char* const block_names[WB_COUNT] = {"Jp", "T3", "Gmw", "Cdup", "T2", "U", "Fcol", "Epart", "Cpart"};
+    const EvalShape s{.N = N, .n_occ = n_occ, .ncas = ncas, .nrdm = derivatives ? 1 + n_theta : 1, .n_kappa = n_kappa,
+                      .batch = batch, .eri_flags = eri_flags, .packed = have_packed != 0, .n_qubits = n_qubits,
+                      .n_gates = n_gates, .n_cu = oovqe_cu_count(), .opt = oovqe_eval_opts()};
+    EvalPlan p;
+    if (n_qubits != 0 && n_qubits != 2 * ncas) {
+        oovqe_set_error("oo_eval: n_qubits != 2*ncas");
+        return nullptr;
+    }
+    if (oovqe_eval_plan(s, &p)) return nullptr;
+    // k1_hosts: what the contraction dispatcher itself answers for the batched K1 launch of this path (p -> n; the
+    // packed one-step and staged paths have none) -- the tests hold a riding circuit against it
+    const bool k1 = p.path == PATH_PACKED_TWO_STEP || p.path == PATH_FUSED || p.path == PATH_COLUMN;
+    const long M = n_occ + ncas, K = p.path == PATH_FUSED ? (long)p.fused.nchunk * N : N;
+    const int hosts = k1 && oovqe_contract_hosts_circuit(1, (int)K, N, p.path == PATH_COLUMN ? N * M * M : M * M * M, 0, batch, s.opt.k1);
+    size_t n = 0;
+    auto add = [&](const char* fmt, auto... args) {
+        if (n < sizeof(line)) n += (size_t)snprintf(line + n, sizeof(line) - n, fmt, args...);
+    };
+    add("path=%s; stage1=%s; circuit=%s; w=%d; launches=%ld; k1_hosts=%d; labels=", path_names[p.path], p.stage1.name,
+        circuit_names[p.circuit], p.w ? 1 : 0, p.launches, hosts);
+    for (int l = 0; l < LABEL_COUNT; ++l) add("%s%d", l ? "," : "", p.labels[l]);
+    add("%s", "; blocks=");
+    for (int b = 0, first = 1; b < WB_COUNT; ++b)
+        if (p.len[b]) {
+            add("%s%s@%zu+%zu", first ? "" : ",", block_names[b], p.off[b], p.len[b]);
+            first = 0;
+        }
+    return line;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 // over the 2^n real amplitudes (closed form: include/oovqe.h, oovqe_gate_t); the state never
 // becomes complex.  Tangent states d psi / d theta_k come from the same pass with the k-th gate
 // replaced by its derivative (forward mode).
-#include "common.h"
+#include "internal.h"
 #include "circuit_small.h"
 
 namespace {
@@ -645,13 +645,6 @@ extern "C" int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int
     return n_qubits <= 10 && small_lds_bytes(n_qubits, ncas, nvec, n_gates) <= 150 * 1024;
 }
 
-// cas.hip: the same with W = C^T h_ao [batch][N][N] of every geometry formed by extra workgroups of the launch
-// (small circuits only: the caller has checked oovqe_circuit_rdms_is_small; N <= 48)
-int oovqe_circuit_rdms_w(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates, int n_qubits,
-                         int ncas, uint32_t init_index, int want_tangents, int batch, double* psi, double* dpsi,
-                         double* gamma, double* Gamma, double* work, const double* h_ao, const double* C, int N,
-                         double* Wpre, oovqe_stream_t stream);
-
 extern "C" int oovqe_circuit_rdms(const double* theta, int n_theta, const oovqe_gate_t* gates,
                                   int n_gates, int n_qubits, int ncas, uint32_t init_index,
                                   int want_tangents, int batch, double* psi, double* dpsi,
@@ -734,8 +727,6 @@ extern "C" int64_t oovqe_circuit_hessian_work_size(int n_theta, int n_qubits, in
            4 * n_pairs * 2 * na2 * D;
 }
 
-// batch elements stacked: theta [batch][n_theta]; c1 / c2 of element b at c1 + b * c1_bs, c2 + b * c2_bs;
-// H element (j,k) of b at H[b * h_bs + j * ldh + k]; work: batch * oovqe_circuit_hessian_work_size()
 int oovqe_circuit_hessian_batched_impl(const double* theta, int n_theta, const oovqe_gate_t* gates,
                                        int n_gates, int n_qubits, int ncas, uint32_t init_index,
                                        const double* c1, const double* c2, long c1_bs, long c2_bs,

@@ -29,7 +29,7 @@
 //     buffer stores) behind the next tile's MFMAs; every wait for a prefetched load pinned inside
 //     the straight-line code that issued it, where it is counted exactly.
 //   INNER contractions with even B and many strips run on contract_pair.hip (two strips per wave).
-#include "common.h"
+#include "internal.h"
 
 // cache policy of the result stores / the T loads (buffer aux bits; 2 = nt: streaming)
 #ifndef K1_AUX_ST
@@ -620,33 +620,51 @@ int launch_short(int nt, const double* T, const double* Cm, double* out, long A,
 
 }  // namespace
 
-int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st);
-
 int oovqe_mode_contract_impl(const double* T, const double* Cm, double* out, long A, int K, int J,
                              long B, int ldc, int last, hipStream_t st)
 {
     return oovqe_mode_contract_batched(T, Cm, out, A, K, J, B, ldc, last, 1, 0, 0, 0, st);
 }
 
-// Can the launch for this shape host circuit workgroups (single-chunk kernels, K <= 48, <= 4 tiles)?
-// Mirrors the dispatch of oovqe_mode_contract_batched_circ below.
-static int contract_plan(long A, int K, int J, long B, int last, int batch, int* nt_out, int* ngroups_out,
-                         long* n_items_out, int* nbt_out)
+ContractOpts oovqe_contract_opts()
 {
-    const int JT = (J + 15) / 16;
+    return ContractOpts{oovqe_opt(OOVQE_OPT_K1_FORCE_NT), oovqe_opt(OOVQE_OPT_K1_FORCE_WIDE) != 0,
+                        oovqe_opt(OOVQE_OPT_K1_NO_PAIR) != 0};
+}
+
+// The launch that serves a contraction: kernel family, tiles per wave, j-groups (grid.y of ONE launch), items.
+enum ContractFamily {
+    CONTRACT_SHORT,      // K <= 48, <= 4 tiles: single-chunk kernels (launch_short); the only family that hosts circuit workgroups
+    CONTRACT_PAIR,       // INNER, two 16-wide strips per wave (contract_pair.hip)
+    CONTRACT_WIDE,       // INNER, strides of T too long for scalar step offsets
+    CONTRACT_DEEP,       // 20-row chunks
+    CONTRACT_SHALLOW     // 12-row chunks
+};
+struct ContractPlan {
+    ContractFamily family;
+    bool deep;           // chunk depth of the pair family
+    int nt, ngroups, nbt;
     long n_items;
-    int nbt = 1;
+};
+
+// T / out / their batch strides decide only whether the pair kernels may serve (alignment); null: do not ask
+static ContractPlan contract_plan(long A, int K, int J, long B, int last, int batch, const ContractOpts& o,
+                                  const double* T = nullptr, const double* out = nullptr, long t_bs = 0, long o_bs = 0)
+{
+    ContractPlan p;
+    const int JT = (J + 15) / 16;
+    p.nbt = 1;
     if (last) {
-        n_items = (A + 15) / 16;
+        p.n_items = (A + 15) / 16;
     } else {
         const long nb = (B + 15) / 16;
-        nbt = (int)nb;
-        n_items = A * nb;
+        p.nbt = (int)nb;
+        p.n_items = A * nb;
     }
+    // tiles per wave: as many as fit (T is then streamed once), fewer when the problem is too
+    // small to fill 256 CUs with 8-wave workgroups
     int nt = JT < 13 ? JT : 13;
-    const long wgs = (n_items + NWAVES - 1) / NWAVES;
+    const long wgs = (p.n_items + NWAVES - 1) / NWAVES;
     // (never past one resident round of workgroups, ~2 per CU: a second round doubles the latency of
     // these short launches -- 17 -> 9 us for the p -> n step of a 64-geometry evaluation)
     while (nt > 1 && wgs * ((JT + nt - 1) / nt) * batch < 512) {
@@ -654,44 +672,33 @@ static int contract_plan(long A, int K, int J, long B, int last, int batch, int*
         if (wgs * ((JT + nt2 - 1) / nt2) * batch > 512) break;
         nt = nt2;
     }
-    if (oovqe_opt(OOVQE_OPT_K1_FORCE_NT) > 0 && oovqe_opt(OOVQE_OPT_K1_FORCE_NT) < nt) nt = oovqe_opt(OOVQE_OPT_K1_FORCE_NT);
-    const int ngroups = (JT + nt - 1) / nt;
-    nt = (JT + ngroups - 1) / ngroups;   // even split
-    *nt_out = nt;
-    *ngroups_out = ngroups;
-    *n_items_out = n_items;
-    *nbt_out = nbt;
-    return 0;
+    if (o.force_nt > 0 && o.force_nt < nt) nt = o.force_nt;
+    p.ngroups = (JT + nt - 1) / nt;
+    p.nt = nt = (JT + p.ngroups - 1) / p.ngroups;   // even split
+    // chunk depth: 20 rows when that wastes <= 5 % of the MFMAs on zero padding, else 12 rows
+    const int pad20 = ((K + 19) / 20) * 20, pad12 = ((K + 11) / 12) * 12;
+    p.deep = (pad20 <= pad12 || pad20 * 100 <= K * 105) && (last || step_offsets_fit(5, B));
+    const bool few = K <= 48 && nt <= 4;
+    if (!last && !few && step_offsets_fit(p.deep ? 5 : 3, B) && !o.no_pair && !o.force_wide && T &&
+        oovqe_contract_pair_ok(T, out, A, B, nt, p.ngroups, batch, t_bs, o_bs))
+        p.family = CONTRACT_PAIR;
+    else if (!last && (!step_offsets_fit(3, B) || o.force_wide))
+        p.family = CONTRACT_WIDE;
+    else if (few && (last || step_offsets_fit(12, B)))
+        p.family = CONTRACT_SHORT;
+    else
+        p.family = p.deep ? CONTRACT_DEEP : CONTRACT_SHALLOW;
+    return p;
 }
 
-int oovqe_contract_hosts_circuit(long A, int K, int J, long B, int last, int batch)
+int oovqe_contract_hosts_circuit(long A, int K, int J, long B, int last, int batch, const ContractOpts& o)
 {
-    int nt, ngroups, nbt;
-    long n_items;
-    contract_plan(A, K, J, B, last, batch, &nt, &ngroups, &n_items, &nbt);
-    return K <= 48 && nt <= 4 && (last || step_offsets_fit(12, B));
+    return contract_plan(A, K, J, B, last, batch, o).family == CONTRACT_SHORT;
 }
-
-int oovqe_mode_contract_batched_circ(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                     long B, int ldc, int last, int batch, long t_bs, long c_bs,
-                                     long o_bs, hipStream_t st, const oovqe_circuit_job_t* cj);
-int oovqe_contract_pair_ok(const double* T, const double* out, long A, long B, int nt, int ngroups, int batch,
-                           long t_bs, long o_bs);
-int oovqe_contract_pair_launch(const double* T, const double* Cm, double* out, long A, int K, int J, long B,
-                               int ldc, int nt, int ngroups, int deep, int batch, long t_bs, long c_bs,
-                               long o_bs, hipStream_t st);
 
 int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
                                 long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st)
-{
-    return oovqe_mode_contract_batched_circ(T, Cm, out, A, K, J, B, ldc, last, batch, t_bs, c_bs, o_bs, st,
-                                            nullptr);
-}
-
-int oovqe_mode_contract_batched_circ(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                     long B, int ldc, int last, int batch, long t_bs, long c_bs,
-                                     long o_bs, hipStream_t st, const oovqe_circuit_job_t* cj)
+                                hipStream_t st, const oovqe_circuit_job_t* cj)
 {
     OOVQE_REQUIRE(batch >= 1 && batch <= 65535, "mode_contract: batch=%d", batch);
     OOVQE_REQUIRE((double)A * (double)((B + 15) / 16) < 2.0e9, "mode_contract: too many strips");
@@ -700,43 +707,32 @@ int oovqe_mode_contract_batched_circ(const double* T, const double* Cm, double* 
                   "mode_contract: bad dims A=%ld K=%d J=%d B=%ld ldc=%d", A, K, J, B, ldc);
     OOVQE_REQUIRE(!last || B == 1, "mode_contract: last-mode needs B == 1");
     OOVQE_REQUIRE(last || (B + 15) / 16 <= 0x7fffffffL, "mode_contract: B too large");
-    // tiles per wave: as many as fit (T is then streamed once), fewer when the problem is too
-    // small to fill 256 CUs with 8-wave workgroups.  The j-groups are grid.y of ONE launch.
-    int nt, ngroups, nbt;
-    long n_items;
-    contract_plan(A, K, J, B, last, batch, &nt, &ngroups, &n_items, &nbt);
-    OOVQE_REQUIRE(ngroups <= 65535, "mode_contract: J too large");
-    // chunk depth: 20 rows when that wastes <= 5 % of the MFMAs on zero padding, else 12 rows
-    const int pad20 = ((K + 19) / 20) * 20, pad12 = ((K + 11) / 12) * 12;
-    const bool deep = (pad20 <= pad12 || pad20 * 100 <= K * 105) && (last || step_offsets_fit(5, B));
-    int rc;
-    OOVQE_REQUIRE(!cj || (K <= 48 && nt <= 4 && (last || step_offsets_fit(12, B))),
-                  "mode_contract: this shape cannot host circuit workgroups");
-    if (!last && !cj && !(K <= 48 && nt <= 4) && step_offsets_fit(deep ? 5 : 3, B) && !oovqe_opt(OOVQE_OPT_K1_NO_PAIR) &&
-        !oovqe_opt(OOVQE_OPT_K1_FORCE_WIDE) &&
-        oovqe_contract_pair_ok(T, out, A, B, nt, ngroups, batch, t_bs, o_bs))
-        // two 16-wide strips per wave (contract_pair.hip)
-        rc = oovqe_contract_pair_launch(T, Cm, out, A, K, J, B, ldc, nt, ngroups, deep ? 1 : 0, batch, t_bs, c_bs,
-                                        o_bs, st);
-    else if (!last && (!step_offsets_fit(3, B) || oovqe_opt(OOVQE_OPT_K1_FORCE_WIDE)))
-        rc = launch_wide(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch, t_bs, c_bs, o_bs, st);
-    else if (K <= 48 && nt <= 4 && (last || step_offsets_fit(12, B)))
-        rc = last ? launch_short<true>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch, t_bs,
-                                       c_bs, o_bs, st, cj)
-                  : launch_short<false>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch, t_bs,
-                                        c_bs, o_bs, st, cj);
-    else if (deep)
-        rc = last ? launch_group<true, 5>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch,
-                                     t_bs, c_bs, o_bs, st)
-                  : launch_group<false, 5>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch,
-                                     t_bs, c_bs, o_bs, st);
-    else
-        rc = last ? launch_group<true, 3>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch,
-                                     t_bs, c_bs, o_bs, st)
-                  : launch_group<false, 3>(nt, T, Cm, out, A, K, J, B, ldc, ngroups, n_items, nbt, batch,
-                                     t_bs, c_bs, o_bs, st);
-    if (rc) return rc;
-    return 0;
+    const ContractPlan p = contract_plan(A, K, J, B, last, batch, oovqe_contract_opts(), T, out, t_bs, o_bs);
+    OOVQE_REQUIRE(p.ngroups <= 65535, "mode_contract: J too large");
+    OOVQE_REQUIRE(!cj || p.family == CONTRACT_SHORT, "mode_contract: this shape cannot host circuit workgroups");
+    switch (p.family) {
+    case CONTRACT_PAIR:
+        return oovqe_contract_pair_launch(T, Cm, out, A, K, J, B, ldc, p.nt, p.ngroups, p.deep ? 1 : 0, batch, t_bs,
+                                          c_bs, o_bs, st);
+    case CONTRACT_WIDE:
+        return launch_wide(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch, t_bs, c_bs, o_bs, st);
+    case CONTRACT_SHORT:
+        return last ? launch_short<true>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch, t_bs,
+                                         c_bs, o_bs, st, cj)
+                    : launch_short<false>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch, t_bs,
+                                          c_bs, o_bs, st, cj);
+    case CONTRACT_DEEP:
+        return last ? launch_group<true, 5>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch,
+                                            t_bs, c_bs, o_bs, st)
+                    : launch_group<false, 5>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch,
+                                             t_bs, c_bs, o_bs, st);
+    case CONTRACT_SHALLOW:
+        return last ? launch_group<true, 3>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch,
+                                            t_bs, c_bs, o_bs, st)
+                    : launch_group<false, 3>(p.nt, T, Cm, out, A, K, J, B, ldc, p.ngroups, p.n_items, p.nbt, batch,
+                                             t_bs, c_bs, o_bs, st);
+    }
+    return OOVQE_ERR_ARG;
 }
 
 extern "C" int oovqe_mode_contract(const double* T, const double* Cm, double* out, int64_t A, int K,

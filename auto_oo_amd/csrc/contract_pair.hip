@@ -20,7 +20,7 @@
 // Everything else follows contract.hip: Cm staged through LDS in K-chunks (double buffered), one
 // buffer descriptor per chunk with the k-step as scalar offset, fragment reads and prefetch parts
 // between groups of MFMAs, the last chunk of a strip tile-outer with its stores between the MFMAs.
-#include "common.h"
+#include "internal.h"
 
 // cache policy of the result stores / the T loads (buffer aux bits; 2 = nt: streaming)
 #ifndef K1_AUX_ST

@@ -12,10 +12,7 @@
 //             of squarings decided on the device - a single launch, no host round trip.
 //   N  > 48 : matrices in HBM/L2, products through the K1 contraction kernel; the 1-norm is read
 //             back once (8 bytes) to choose s on the host.
-#include "common.h"
-
-int oovqe_mode_contract_impl(const double* T, const double* Cm, double* out, long A, int K, int J,
-                             long B, int ldc, int last, hipStream_t st);
+#include "internal.h"
 
 namespace {
 
@@ -365,10 +362,6 @@ extern "C" int oovqe_expm_skew(const double* kappa, const int32_t* kap_row, cons
 // src/auto_oo/oo_energy.py:213-236, per geometry): C_out[b] = C[b] expm(-K(kappa[b])).
 // kappa [batch][n_kappa], C / C_out [batch][N][N] (C_out may alias C), U [batch][N][N] or NULL.
 // N <= 48: one workgroup per geometry, everything in LDS.
-int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st);
-
 extern "C" int oovqe_rotate_orbitals_batch(const double* kappa, const int32_t* kap_row,
                                            const int32_t* kap_col, int n_kappa, int N, int batch,
                                            const double* C, double* C_out, double* U, double* work,

@@ -12,10 +12,7 @@
 // Both are produced from g_ao with partial transforms on the K1 contraction kernel
 // (O(N^4 M) flop), Y is two small GEMMs (O(N^2 M^4)), and an assembly kernel applies the
 // antisymmetrisers directly on the non-redundant (tril) pairs.
-#include "common.h"
-
-int oovqe_mode_contract_impl(const double* T, const double* Cm, double* out, long A, int K, int J,
-                             long B, int ldc, int last, hipStream_t st);
+#include "internal.h"
 
 namespace {
 
@@ -210,14 +207,6 @@ extern "C" int64_t oovqe_orbital_hessian_work_size(int N, int n_occ, int ncas)
     return 8 * n * n * M * M + n * n * n * M + 2 * n * n + 2 * M * M * M * M;
 }
 
-// cas.hip: stage 1 for a stack of geometries (slabs p <= q only when the flags allow it)
-int oovqe_half_transform_batched_impl(const double* g_ao, const double* C, int N, int M, double* T2,
-                                      int batch, unsigned eri_flags, oovqe_stream_t stream,
-                                      double* Vk_tri = nullptr);
-int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st);
-
 // The orbital-orbital Hessian for `batch` geometries of identical shape: every input stacked along a
 // leading batch axis with the given strides (doubles), every intermediate stacked in `work`
 // (batch * oovqe_orbital_hessian_work_size() doubles); the geometry index is a grid dimension of
@@ -382,19 +371,6 @@ extern "C" int oovqe_orbital_hessian_batch(const double* g_ao, const double* h_a
 // (n_theta + n_kappa)^2 Hessian of every geometry (OO_pqc.full_gradient + full_hessian,
 // oo_pqc.py:132-148), the geometry index being a grid dimension of every launch.
 // ------------------------------------------------------------------------------------------------------
-int oovqe_oo_eval_batched_impl(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
-                               int n_qubits, uint32_t init_index, const double* g_ao, const double* h_ao,
-                               const double* C, const double* nuc_arr, int N, int n_occ, int ncas,
-                               const int32_t* kap_row, const int32_t* kap_col, int n_kappa, int derivatives,
-                               int batch, double* work, double* out, unsigned eri_flags,
-                               oovqe_stream_t stream, const double* g_packed, double* fock,
-                               const double* T2_ready = nullptr, hipEvent_t rdm_event = nullptr);
-int oovqe_circuit_hessian_batched_impl(const double* theta, int n_theta, const oovqe_gate_t* gates,
-                                       int n_gates, int n_qubits, int ncas, uint32_t init_index,
-                                       const double* c1, const double* c2, long c1_bs, long c2_bs,
-                                       const int32_t* pairs, int n_pairs, int batch, double* work, double* H,
-                                       long ldh, long h_bs, oovqe_stream_t stream);
-
 static bool hess_circuit_own_block(int n_qubits) { return n_qubits <= 10; }
 
 extern "C" int64_t oovqe_oo_hessian_work_size(int n_theta, int n_gates, int n_qubits, int N, int n_occ,
@@ -466,16 +442,17 @@ extern "C" int oovqe_oo_hessian_batch(const double* theta, int n_theta, const oo
         }
     }
     // 1. circuit + tangents -> RDM sets -> CAS path: E, dE/dtheta, dE/dkappa, d^2E/dkappa dtheta, c1, c2, F
-    if ((rc = oovqe_oo_eval_batched_impl(theta, n_theta, gates, n_gates, n_qubits, init_index, g_ao, h_ao, C, nuc,
-                                         N, n_occ, ncas, kap_row, kap_col, n_kappa, 1, batch, ev_work, out,
-                                         eri_flags, stream, g_packed, fock, share ? hs_work : nullptr,
-                                         forked ? fork.rdm_ready : nullptr)))
-        return rc;
+    const OoEvalArgs ev_args{
+        .theta = theta, .n_theta = n_theta, .gates = gates, .n_gates = n_gates, .n_qubits = n_qubits,
+        .init_index = init_index, .derivatives = 1, .work = ev_work, .out = out,
+        .cas = {.g_ao = g_ao, .h_ao = h_ao, .C = C, .nuc_arr = nuc, .N = N, .n_occ = n_occ, .ncas = ncas,
+                .kap_row = kap_row, .kap_col = kap_col, .n_kappa = n_kappa, .fock = fock, .batch = batch, .stream = stream,
+                .eri_flags = eri_flags, .g_packed = g_packed, .T2_ready = share ? hs_work : nullptr,
+                .rdm_event = forked ? fork.rdm_ready : nullptr}};
+    if ((rc = oovqe_oo_eval_batched_impl(ev_args))) return rc;
     const long out_stride = (long)oovqe_oo_eval_out_size(n_theta, n_kappa, ncas, 1);
     const long n = (long)n_theta + n_kappa;
-    const double* gvec = out + 2 + n_theta;
-    const double* c1 = gvec + (size_t)nvec * n_kappa;
-    const double* c2 = c1 + na2;
+    const OutSlab o = out_layout(out, nvec, n_kappa, ncas);
     // 2. kappa-kappa block (bottom right) from RDM set 0 of every geometry and its Fock matrix (before the
     //    circuit Hessian: that one reuses the scratch in which T2 / Vk of step 0 live)
     const double* gamma = ev_work;
@@ -492,15 +469,15 @@ extern "C" int oovqe_oo_hessian_batch(const double* theta, int n_theta, const oo
         const int64_t oh = oovqe_orbital_hessian_work_size(N, n_occ, ncas);
         ch_work = hs_work + nb * (size_t)(ch > oh ? ch : oh);
     }
-    if ((rc = oovqe_circuit_hessian_batched_impl(theta, n_theta, gates, n_gates, n_qubits, ncas, init_index, c1,
-                                                 c2, out_stride, out_stride, pairs, n_pairs, batch, ch_work,
+    if ((rc = oovqe_circuit_hessian_batched_impl(theta, n_theta, gates, n_gates, n_qubits, ncas, init_index, o.c1,
+                                                 o.c2, out_stride, out_stride, pairs, n_pairs, batch, ch_work,
                                                  hessian, n, n * n, stream)))
         return rc;
     // 4. kappa-theta blocks
     {
         const long total = (long)n_theta * n_kappa;
         const unsigned nbk = (unsigned)((total + 255) / 256);
-        hess_cross_block_kernel<<<dim3(nbk, batch), 256, 0, (hipStream_t)stream>>>(gvec, out_stride, n_theta,
+        hess_cross_block_kernel<<<dim3(nbk, batch), 256, 0, (hipStream_t)stream>>>(o.gvec, out_stride, n_theta,
                                                                                   n_kappa, hessian, n, n * n);
         OOVQE_CHECK_LAUNCH("oo_hessian_batch/cross");
     }

@@ -14,7 +14,7 @@
 //      partial pivoting.
 // The whole problem lives in one workgroup (LDS: the panel's V and W, vectors; global: a working
 // copy of H and the stored reflectors), so a batch of G problems is G independent workgroups.
-#include "common.h"
+#include "internal.h"
 #include <math.h>
 
 #ifdef OOVQE_NEWTON_TIMING
@@ -1984,11 +1984,6 @@ static int n2_cu_count()
     }
     return cus;
 }
-
-int oovqe_newton_chol_launch(const double* hessian, const double* gradient, int n, int batch, double lambda_min,
-                             double* work, double* dp, double* shift, double* info, hipStream_t st);
-size_t oovqe_newton_chol_work(int n, int batch);
-int oovqe_newton_chol_max_n(void);
 
 // which kernel serves (n, aug): the two-stage multi-workgroup one whenever the level shift is on (then the
 // system it solves is positive definite by construction); without the shift (aug == 0: the reference then

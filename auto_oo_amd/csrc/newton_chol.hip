@@ -39,14 +39,9 @@
 // (c_pi) the lane holds four ADJACENT columns of one row: 16-byte accesses everywhere.
 // Back substitution: column-oriented (thread c owns y[c], no reductions), the 16 x 16 transposed solves are
 // mat-vecs with the stored inverses, y of a block by readlane.
-#include "common.h"
+#include "internal.h"
 #include <math.h>
 #include <type_traits>
-
-int oovqe_newton_chol_launch(const double* hessian, const double* gradient, int n, int batch, double lambda_min,
-                             double* work, double* dp, double* shift, double* info, hipStream_t st);
-size_t oovqe_newton_chol_work(int n, int batch);
-int oovqe_newton_chol_max_n(void);
 
 #ifdef OOVQE_CHOL_TIMING
 // tools/newton_chol_probe.hip: cycles per phase, thread 0 of workgroup 0

@@ -19,11 +19,7 @@
 //   walking the gates backwards:  dE/dtheta_k = (sign_k/2) lambda^T A_k psi,
 //                                 psi <- U_k^T psi, lambda <- U_k^T lambda   (sector_adjoint_kernel)
 // i.e. 2 vectors and 2*n_gates Givens passes instead of n_theta tangent states.
-#include "common.h"
-
-int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, long A, int K, int J,
-                                long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
-                                hipStream_t st);
+#include "internal.h"
 
 namespace {
 

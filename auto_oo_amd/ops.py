@@ -37,6 +37,29 @@ def profile_end():
     return ms[0], cnt[0], by
 
 
+def eval_plan(N, n_occ, ncas, n_kappa, batch, eri_flags, have_packed, n_theta=0, n_gates=0, derivatives=True,
+              circuit=True):
+    """What one batched evaluation of this shape will launch (oovqe_oo_eval_plan_describe; no device needed), as a
+    dict: path, stage1, circuit, w (bool), launches (int), k1_hosts (bool: the K1 launch of the path, if it makes one, can
+    host circuit workgroups), labels {PROFILE_LABELS name: bracketed launches},
+    blocks {name: (offset, doubles)}.  ``circuit=False``: the evaluation from given RDM sets."""
+    lib = _lib.load()
+    line = lib.oovqe_oo_eval_plan_describe(n_theta, n_gates, 2 * ncas if circuit else 0, N, n_occ, ncas, n_kappa,
+                                           int(bool(derivatives)), batch, eri_flags, int(bool(have_packed)))
+    if line is None:
+        raise _lib.OovqeError(lib.oovqe_last_error().decode())
+    plan = dict(field.split("=", 1) for field in line.decode().split("; "))
+    plan["w"], plan["k1_hosts"] = plan["w"] == "1", plan["k1_hosts"] == "1"
+    plan["launches"] = int(plan["launches"])
+    plan["labels"] = dict(zip(PROFILE_LABELS, (int(x) for x in plan["labels"].split(","))))
+    blocks = {}
+    for item in filter(None, plan["blocks"].split(",")):
+        name, span = item.split("@")
+        blocks[name] = tuple(int(x) for x in span.split("+"))
+    plan["blocks"] = blocks
+    return plan
+
+
 def _dev(t):
     if not t.is_cuda:
         raise _lib.OovqeError("auto_oo_amd ops need CUDA(HIP) tensors; no CPU fallback exists")

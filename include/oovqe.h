@@ -45,6 +45,19 @@ int         oovqe_profile_end_labels(double* ms_by_label, int* count_by_label, i
 /* name and template arguments of the stage-1 (N^4 pass) kernel the last evaluation dispatched, e.g.
  * "half_tri_reg_kernel<11,3,8,3>" ("" before the first evaluation); bench.py's roofline quotes it */
 const char* oovqe_last_stage1_kernel(void);
+/* The plan of an evaluation as one line, without launching anything (needs no device; a test / debug aid):
+ *   "path=<packed_tail|packed_split|packed_two_step|fused|column|staged>; stage1=<kernel, spelled as
+ *    oovqe_last_stage1_kernel reports it>; circuit=<none|rides|own>; w=<0|1>; launches=<kernel launches>;
+ *    k1_hosts=<0|1: the batched contraction launch of the path, if it makes one, can host circuit workgroups>;
+ *    labels=<bracketed launches by profile label, comma separated>; blocks=<name>@<offset>+<doubles>,..."
+ * for an oovqe_oo_eval_batch call of this shape (n_qubits == 0: an oovqe_cas_eval_batch call with
+ * nrdm = derivatives ? 1 + n_theta : 1) under the debug options set now and the CU count of the current device
+ * (256 without one).  w: the circuit's own launch leaves W = C^T h_ao for the Fock stage; blocks: the parts of the
+ * CAS workspace the path uses.  NULL (see oovqe_last_error) for a shape no kernel serves.  The string belongs to the
+ * calling thread and is overwritten by its next call. */
+const char* oovqe_oo_eval_plan_describe(int n_theta, int n_gates, int n_qubits, int N, int n_occ, int ncas,
+                                        int n_kappa, int derivatives, int batch, unsigned eri_flags,
+                                        int have_packed);
 
 /* ---- gate table for the statevector kernels ----------------------------------------------- *
  * One entry per excitation gate (qml.FermionicDoubleExcitation / FermionicSingleExcitation /

@@ -22,7 +22,9 @@ int main()
     float tot = 0, best = 1e30f;
     for (int r = 0; r < reps + 5; ++r) {
         (void)hipEventRecord(e0, 0);
-        int rc = half_transform_batched(g, C, N, M, T2, G, nullptr);
+        Stage1 s1;
+        int rc = stage1_half(N, M, SYM_FULL, false, false, &s1);
+        if (!rc) rc = half_transform_batched(g, C, N, M, T2, G, nullptr, s1);
         (void)hipEventRecord(e1, 0);
         (void)hipEventSynchronize(e1);
         if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }
@@ -32,13 +34,16 @@ int main()
     }
     {
         FusedPlan fp;
-        if (!fused_plan(N, M, G, &fp)) { printf("no fused plan\n"); return 1; }
+        if (!fused_plan(N, M, G, oovqe_cu_count(), 0, &fp)) { printf("no fused plan\n"); return 1; }
+        Stage1Variant v;
+        if (stage1_variant(N, &v)) return 1;
+        const Stage1 sf = stage1_small(S1_FUSED, v, 0);
         double* Cdup;
         (void)hipMalloc(&Cdup, (size_t)G * fp.nchunk * N * N * 8 + 8);
         float tot2 = 0, best2 = 1e30f;
         for (int r = 0; r < reps + 5; ++r) {
             (void)hipEventRecord(e0, 0);
-            int rc = half_transform_fused_batched(g, C, N, M, T2, Cdup, fp, G, nullptr);
+            int rc = half_transform_fused_batched(g, C, N, M, T2, Cdup, fp, sf, G, nullptr);
             (void)hipEventRecord(e1, 0);
             (void)hipEventSynchronize(e1);
             if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }
@@ -55,7 +60,12 @@ int main()
         float tot3 = 0, best3 = 1e30f, totq = 0;
         for (int r = 0; r < reps + 5; ++r) {
             (void)hipEventRecord(e0, 0);
-            int rc = mode == 5 ? half_tri_batched(g, C, N, M, T2, G, nullptr, 2, true) : mode == 4 ? half_tri_batched(g, C, N, M, T2, G, nullptr, 2, false) : mode == 3 ? half_tri_batched(g, C, N, M, T2, G, nullptr) : half_transform_batched(g, C, N, M, T2, G, nullptr, mode);
+            Stage1Variant v;
+            Stage1 s1;
+            int rc = stage1_variant(N, &v);
+            if (!rc && mode >= 3) s1 = stage1_small(mode == 5 ? S1_TRI_REG : S1_TRI, v, mode == 3 ? 0 : 2);
+            else if (!rc) rc = stage1_half(N, M, mode, false, false, &s1);
+            if (!rc) rc = mode >= 3 ? half_tri_batched(g, C, N, M, T2, G, nullptr, s1) : half_transform_batched(g, C, N, M, T2, G, nullptr, s1);
             (void)hipEventRecord(e1, 0);
             (void)hipEventSynchronize(e1);
             if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }

@@ -26,7 +26,9 @@ int main()
         long long zero[16] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_cyc), zero, sizeof(zero));
         (void)hipEventRecord(e0, 0);
-        int rc = half_transform_batched(g, C, N, M, T2, 1, nullptr, SYM_MIRROR, true);
+        Stage1 s1;
+        int rc = stage1_half(N, M, SYM_MIRROR, true, false, &s1);
+        if (!rc) rc = half_transform_batched(g, C, N, M, T2, 1, nullptr, s1);
         (void)hipEventRecord(e1, 0);
         (void)hipEventSynchronize(e1);
         if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }

@@ -28,7 +28,9 @@ int main()
         float tot = 0, best = 1e30f;
         for (int r = 0; r < reps + 5; ++r) {
             (void)hipEventRecord(e0, 0);
-            int rc = half_transform_batched(g, C, N, M, T2, G, nullptr);
+            Stage1 s1;
+            int rc = stage1_half(N, M, SYM_FULL, false, false, &s1);
+            if (!rc) rc = half_transform_batched(g, C, N, M, T2, G, nullptr, s1);
             (void)hipEventRecord(e1, 0);
             (void)hipEventSynchronize(e1);
             if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }

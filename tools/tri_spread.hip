@@ -27,7 +27,9 @@ int main()
         long long zero[16] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tri_cyc), zero, sizeof(zero));
         (void)hipEventRecord(e0, 0);
-        int rc = half_tri_batched(gp, C, N, M, J, G, nullptr, 2, true);
+        Stage1Variant var;
+        int rc = stage1_variant(N, &var);
+        if (!rc) rc = half_tri_batched(gp, C, N, M, J, G, nullptr, stage1_small(S1_TRI_REG, var, 2));
         (void)hipEventRecord(e1, 0);
         (void)hipEventSynchronize(e1);
         if (rc) { printf("error: %s\n", oovqe_last_error()); return 1; }
