@@ -21,7 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _lib, excitations as X, gto as GTO, ops, scf
+from . import _lib, excitations as X, gto as GTO, nucgrad, ops, scf
 from ._lib import check, dptr, stream_ptr
 from .gaussian import rhf
 from .moldata import Moldata
@@ -102,6 +102,8 @@ class OO_pqc_batch:
         self._all_pd_last_step = False
         self.step_by_calls = False
         self.basis = None
+        self.coords_bohr = None
+        self._grad_dm2 = None
 
     # ---- integrals made on the device (auto_oo_amd/gto.py) ----------------------------------------------------------
     @classmethod
@@ -148,6 +150,13 @@ class OO_pqc_batch:
             raise ValueError(f"{int(xyz_bohr.shape[0])} geometries for {len(rows)} rows")
         if any(not 0 <= r < self.G for r in rows) or len(set(rows)) != len(rows):
             raise ValueError(f"index must hold distinct rows in 0..{self.G - 1}")
+        # the coordinates stay with the batch (Bohr): nuclear_gradient differentiates with respect to them
+        if self.coords_bohr is None:
+            self.coords_bohr = torch.empty((self.G, self.basis.natm, 3), dtype=F64, device=self.device)
+        if index is None:
+            self.coords_bohr.copy_(xyz_bohr)
+        else:
+            self.coords_bohr[torch.as_tensor(rows, device=self.device)] = xyz_bohr
         infos = []
         k = 0
         while k < len(rows):
@@ -208,6 +217,77 @@ class OO_pqc_batch:
         res = scf.rhf_batch(self.int1e_ao[sel], self.int2e_ao[sel], self.overlap[sel], self.nelectron // 2,
                             oao_coeff=self.oao_coeff[sel], **kw)
         return res._replace(e_tot=res.e_elec + self.nuc[sel])
+
+    # ---- forces (auto_oo_amd/nucgrad.py, csrc/gto_grad.hip) ----------------------------------------------------------
+    def _gradient_rows(self, index, who):
+        if self.basis is None or self.coords_bohr is None:
+            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries")
+        if index is None:
+            return list(range(self.G))
+        rows = [int(i) for i in np.atleast_1d(index)]
+        if any(not 0 <= r < self.G for r in rows):
+            raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+        return rows
+
+    def _dm2_buffer(self, n):
+        """[n, N, N, N, N] for the AO two-particle density of a chunk: the size of ``int2e_ao`` per geometry, so it is
+        made on first use and kept at the largest chunk asked for."""
+        if self._grad_dm2 is None or int(self._grad_dm2.shape[0]) < n:
+            self._grad_dm2 = torch.empty((n,) + (self.nao,) * 4, dtype=F64, device=self.device)
+        return self._grad_dm2
+
+    def nuclear_gradient(self, thetas, index=None, chunk=None):
+        """dE/dR of every geometry -> [G, natm, 3] (device, Hartree / Bohr): the derivative of each geometry's
+        ``energy_from_parameters(theta_g)`` with respect to its own nuclear coordinates at fixed ``theta_g`` and fixed
+        ``oao_mo_coeff`` -- what central differences over ``set_geometries(..., oao_mo_coeffs=None)`` measure, exact at
+        any parameters and orbitals, converged or not (the dependence of ``S^-1/2`` on the geometry is pulled back to
+        the overlap, ``nucgrad.overlap_pullback``).
+
+        Args:
+            thetas: [G, n_theta], one parameter set per geometry of the batch
+            index: rows of the batch to differentiate (default all); the result then has one entry per row asked for
+            chunk: geometries per pass of the two-electron part (default all at once): the AO two-particle density
+                is as large as ``int2e_ao`` and is kept for ``chunk`` geometries only
+
+        A geometry's gradient has the same bits whatever ``index`` and ``chunk``.  Needs a batch made by
+        ``from_geometries`` (RuntimeError otherwise).  Dense-register circuits only: a circuit in the sector engine
+        (more than 10 qubits) raises NotImplementedError -- its RDMs would serve, that path has not been tested."""
+        rows = self._gradient_rows(index, "nuclear_gradient")
+        if getattr(self.pqc, "_use_sector", False):
+            raise NotImplementedError("nuclear_gradient covers dense-register circuits; circuits in the sector engine "
+                                      "(more than 10 qubits) are not implemented")
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"nuclear_gradient covers ncas <= {nucgrad.MAX_NCAS}")
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        pqc = self.pqc
+        gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
+                                        pqc._init_index, tangents=False)
+        _, _, fock = self._cas_batch(gamma, Gamma, self.G, want_fock=True)
+        step = len(rows) if chunk is None else max(1, int(chunk))
+        out = torch.empty((len(rows), self.basis.natm, 3), dtype=F64, device=self.device)
+        for k in range(0, len(rows), step):
+            sel = torch.as_tensor(rows[k:k + step], device=self.device)
+            d1, d2 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel, 0],
+                                              Gamma[sel, 0], out=self._dm2_buffer(len(sel)))
+            wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
+            out[k:k + step] = GTO.gradient_into(self.basis, self.coords_bohr[sel], d1, wq, d2, True)
+        return out
+
+    def rhf_nuclear_gradient(self, result=None, index=None):
+        """Closed-shell Hartree-Fock gradient -> [G, natm, 3] (device, Hartree / Bohr) from a converged
+        ``scf.RHFResult`` of the rows ``index`` (default all; ``self.rhf(index=index)`` is run when none is given):
+        ``D = 2 C_o C_o^T`` and the energy-weighted density ``WQ = -2 C_o eps_o C_o^T``.  Exact for converged orbitals
+        only (the orbital gradient is taken as zero)."""
+        rows = self._gradient_rows(index, "rhf_nuclear_gradient")
+        if result is None:
+            result = self.rhf(index=index)
+            scf.raise_unless_converged(result.info, rows)
+        if int(result.mo_coeff.shape[0]) != len(rows):
+            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
+                             "for")
+        sel = torch.as_tensor(rows, device=self.device)
+        return nucgrad.rhf_gradient(self.basis, self.coords_bohr[sel], result.mo_coeff, result.mo_energy,
+                                    self.nelectron // 2)
 
     def _rhf_orbitals(self, how, rows):
         """``oao_mo_coeffs="rhf"``: the orbitals of the rows (None: all) from the device solver."""

@@ -14,156 +14,12 @@
 //                      primitive quartet; every unique value goes to its (up to 8) places from one register
 //   sym_invsqrt_kernel S^-1/2 by cyclic Jacobi (round-robin ordering), one wave per matrix, matrix and vectors in LDS
 //
+// The device helpers (Boys function, Hermite coefficients, R_tuv, the readers of the pair data) live in gto.h, shared
+// with the nuclear-derivative kernels of gto_grad.hip.
 // l is a template parameter everywhere; GTO_LMAX = 1 limits what is instantiated (and the component tables
 // gto_ncomp / gto_pow are written for l <= 1).  Every per-thread array is indexed by compile-time constants
 // (static_for / fully unrolled loops of constant trip count), so none of them lives in scratch.
-#include "common.h"
-#include "jacobi.h"
-#include <math.h>
-#include <utility>
-#include <vector>
-
-#define GTO_LMAX 1
-#define GTO_NCLS ((GTO_LMAX + 1) * (GTO_LMAX + 2) / 2)
-#define GTO_PW 8                 // doubles per primitive pair
-#define GTO_NT 64                // threads per workgroup of the integral kernels (one wave)
-#define GTO_SPLIT 8              // lanes that share one shell pair / quartet: each takes every 8th primitive pair of the
-                                 // bra, the partial sums are added by a butterfly (fixed order: the same bits whatever
-                                 // the batch).  A thread's chain of 81 primitive quartets is what a call waits for.
-#define GTO_BOYS_SWITCH 5.0      // T below: series for F_L and downward recursion; above: erf and upward recursion
-#define GTO_BOYS_TERMS 36        // terms of the series (last term below 1e-17 of the sum for T < 5, n >= 0)
-#define GTO_PI 3.14159265358979323846
-#define INVSQRT_NT JACOBI_NT
-
-template <class F, int... I>
-__host__ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F> __host__ __device__ __forceinline__ void static_for(F&& f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// sum over the SPLIT adjacent lanes of a group; every lane of the group receives the same bits
-template <int SPLIT> __host__ __device__ __forceinline__ double gto_group_sum(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-    for (int o = 1; o < SPLIT; o <<= 1) x += __shfl_xor(x, o, 64);
-#endif
-    return x;
-}
-
-__host__ __device__ constexpr int gto_ncomp(int l) { return l == 0 ? 1 : 3; }
-// power of coordinate d in Cartesian component c of a shell of angular momentum l (s; px, py, pz)
-__host__ __device__ constexpr int gto_pow(int l, int c, int d) { return (l == 1 && c == d) ? 1 : 0; }
-__host__ __device__ constexpr int gto_cls(int la, int lb) { return la * (la + 1) / 2 + lb; }
-
-// ---- Boys function -------------------------------------------------------------------------------------------
-// F_n(T) = int_0^1 t^2n exp(-T t^2) dt, n = 0 .. L.
-// T < 5: F_L = exp(-T) sum_k (2T)^k / ((2L+1)(2L+3)...(2L+2k+1)) (all terms positive), then downwards
-// F_{n-1} = (2T F_n + exp(-T)) / (2n - 1) (a sum of positive terms).  T >= 5: F_0 = sqrt(pi/T) erf(sqrt T) / 2, then
-// upwards F_{n+1} = ((2n+1) F_n - exp(-T)) / (2T): for T >= 5 and n <= 4 the subtraction loses less than a bit per
-// step.  Against 40-digit arithmetic this scheme in fp64 is within 6.4e-16 relative for n <= 4 on [0, 2000].
-template <int L> __host__ __device__ __forceinline__ void gto_boys(double T, double (&F)[L + 1])
-{
-    const double et = exp(-T);
-    if (T < GTO_BOYS_SWITCH) {
-        const double T2 = 2.0 * T;
-        double s = 0.0;
-#pragma unroll
-        for (int k = GTO_BOYS_TERMS; k > 0; --k) s = (s + 1.0) * T2 * (1.0 / (double)(2 * L + 2 * k + 1));
-        F[L] = et * (s + 1.0) * (1.0 / (double)(2 * L + 1));
-#pragma unroll
-        for (int n = L; n > 0; --n) F[n - 1] = (T2 * F[n] + et) * (1.0 / (double)(2 * n - 1));
-    } else {
-        const double st = sqrt(T);
-        F[0] = 0.88622692545275801365 / st * erf(st);        // sqrt(pi) / 2
-        const double o2t = 0.5 / T;
-#pragma unroll
-        for (int n = 0; n < L; ++n) F[n + 1] = ((double)(2 * n + 1) * F[n] - et) * o2t;
-    }
-}
-
-// ---- Hermite expansion coefficients of one dimension, without the exponential factor --------------------------
-// E[i][j][t] = E_t^{ij} / E_0^{00}, i <= LA, j <= LB: E^{i+1,j}_t = E^{ij}_{t-1} / 2p + XPA E^{ij}_t + (t+1) E^{ij}_{t+1}
-template <int LA, int LB>
-__host__ __device__ __forceinline__ void gto_herm(double (&E)[LA + 1][LB + 1][LA + LB + 1], double xpa, double xpb, double oo2p)
-{
-#pragma unroll
-    for (int i = 0; i <= LA; ++i) {
-#pragma unroll
-        for (int j = 0; j <= LB; ++j) {
-#pragma unroll
-            for (int t = 0; t <= LA + LB; ++t) {
-                double v = 0.0;
-                if (i == 0 && j == 0) {
-                    v = (t == 0) ? 1.0 : 0.0;
-                } else if (t <= i + j) {
-                    const int top = i + j - 1;             // highest t of the parent
-                    if (j == 0) {
-                        if (t >= 1) v += oo2p * E[i > 0 ? i - 1 : 0][0][t > 0 ? t - 1 : 0];
-                        if (t <= top) v += xpa * E[i > 0 ? i - 1 : 0][0][t];
-                        if (t + 1 <= top) v += (double)(t + 1) * E[i > 0 ? i - 1 : 0][0][t + 1 <= LA + LB ? t + 1 : 0];
-                    } else {
-                        if (t >= 1) v += oo2p * E[i][j > 0 ? j - 1 : 0][t > 0 ? t - 1 : 0];
-                        if (t <= top) v += xpb * E[i][j > 0 ? j - 1 : 0][t];
-                        if (t + 1 <= top) v += (double)(t + 1) * E[i][j > 0 ? j - 1 : 0][t + 1 <= LA + LB ? t + 1 : 0];
-                    }
-                }
-                E[i][j][t] = v;
-            }
-        }
-    }
-}
-
-// ---- Hermite Coulomb integrals R^n_tuv from Fs[n] = (-2 alpha)^n F_n(T) (times any common factor) -----------
-template <int T, int U, int V, int N, int NF>
-__host__ __device__ __forceinline__ double gto_R(const double (&Fs)[NF], double X, double Y, double Z)
-{
-    if constexpr (T < 0 || U < 0 || V < 0) {
-        return 0.0;
-    } else if constexpr (T == 0 && U == 0 && V == 0) {
-        return Fs[N];
-    } else if constexpr (T == 0 && U == 0) {
-        double v = Z * gto_R<0, 0, V - 1, N + 1>(Fs, X, Y, Z);
-        if constexpr (V > 1) v += (double)(V - 1) * gto_R<0, 0, V - 2, N + 1>(Fs, X, Y, Z);
-        return v;
-    } else if constexpr (T == 0) {
-        double v = Y * gto_R<0, U - 1, V, N + 1>(Fs, X, Y, Z);
-        if constexpr (U > 1) v += (double)(U - 1) * gto_R<0, U - 2, V, N + 1>(Fs, X, Y, Z);
-        return v;
-    } else {
-        double v = X * gto_R<T - 1, U, V, N + 1>(Fs, X, Y, Z);
-        if constexpr (T > 1) v += (double)(T - 1) * gto_R<T - 2, U, V, N + 1>(Fs, X, Y, Z);
-        return v;
-    }
-}
-
-template <int L>
-__host__ __device__ __forceinline__ void gto_R_fill(double (&R)[L + 1][L + 1][L + 1], const double (&Fs)[L + 1], double X,
-                                           double Y, double Z)
-{
-    static_for<L + 1>([&](auto tc) {
-        static_for<L + 1>([&](auto uc) {
-            static_for<L + 1>([&](auto vc) {
-                constexpr int t = decltype(tc)::value, u = decltype(uc)::value, v = decltype(vc)::value;
-                if constexpr (t + u + v <= L) R[t][u][v] = gto_R<t, u, v, 0>(Fs, X, Y, Z);
-            });
-        });
-    });
-}
-
-// ---- work buffer ------------------------------------------------------------------------------------------------
-// int32 part: ao_off[nshell] | lists[GTO_NCLS][npair][2] (shell of higher l, shell of lower l), padded to 16 bytes;
-// then pair data [batch][npair][kp][GTO_PW], pair index i (i + 1) / 2 + j (i >= j), slot ka * nprim_j + kb.
-__host__ __device__ inline long gto_int_doubles(int nshell)
-{
-    const long npair = (long)nshell * (nshell + 1) / 2;
-    const long ints = nshell + (long)GTO_NCLS * npair * 2;
-    return ((ints + 1) / 2 + 1) & ~1L;
-}
+#include "gto.h"
 
 __host__ __device__ inline void gto_setup_body(const int* __restrict__ shells, int nshell, int* __restrict__ iw)
 {
@@ -256,49 +112,6 @@ __global__ __launch_bounds__(256) void gto_pair_kernel(const int* __restrict__ s
 {
     gto_pair_body((long)blockIdx.x * blockDim.x + threadIdx.x, shells, nshell, exps, coefs, charges, natm, coords,
                   batch, kp, pairs, nuc);
-}
-
-// what a consumer keeps of one primitive pair, oriented to ITS order of the two shells (first = higher l)
-struct gto_prim_t {
-    double p, P[3], cck, oo2p, fa, fb;     // fa = (exponent of the first shell) / p, fb = (second) / p
-};
-__host__ __device__ __forceinline__ gto_prim_t gto_load_prim(const double* e, bool swapped)
-{
-    const d2* e2 = reinterpret_cast<const d2*>(e);
-    const d2 v0 = e2[0], v1 = e2[1], v2 = e2[2], v3 = e2[3];
-    gto_prim_t q;
-    q.p = v0.x; q.P[0] = v0.y; q.P[1] = v1.x; q.P[2] = v1.y; q.cck = v2.x; q.oo2p = v2.y;
-    q.fa = swapped ? v3.y : v3.x;
-    q.fb = swapped ? v3.x : v3.y;
-    return q;
-}
-
-struct gto_pair_ref_t {
-    int sa, sb;                 // shells (l of sa >= l of sb)
-    int oa, ob;                 // their AO offsets
-    int nprim;                  // primitive pairs
-    bool swapped;               // sa < sb: the stored orientation is (sb, sa)
-    double AB[3];               // A - B
-    const double* data;
-};
-__host__ __device__ __forceinline__ gto_pair_ref_t gto_pair_ref(const int* lists, int cls, int k, long npair, const int* iw,
-                                                       const int* shells, const double* xyz, const double* pairs_g,
-                                                       int kp)
-{
-    gto_pair_ref_t r;
-    r.sa = lists[((long)cls * npair + k) * 2];
-    r.sb = lists[((long)cls * npair + k) * 2 + 1];
-    r.oa = iw[r.sa];
-    r.ob = iw[r.sb];
-    r.nprim = shells[4 * r.sa + 2] * shells[4 * r.sb + 2];
-    r.swapped = r.sa < r.sb;
-    const int hi = r.swapped ? r.sb : r.sa, lo = r.swapped ? r.sa : r.sb;
-    r.data = pairs_g + ((size_t)hi * (hi + 1) / 2 + lo) * kp * GTO_PW;
-    const double* A = xyz + 3 * shells[4 * r.sa];
-    const double* B = xyz + 3 * shells[4 * r.sb];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) r.AB[d] = A[d] - B[d];
-    return r;
 }
 
 // ---- one-electron integrals ---------------------------------------------------------------------------------------
@@ -617,16 +430,6 @@ __global__ __launch_bounds__(INVSQRT_NT) void sym_invsqrt_kernel(const double* _
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-static int gto_check_sizes(const char* who, int nshell, int max_nprim, int batch)
-{
-    OOVQE_REQUIRE(nshell >= 1 && nshell <= OOVQE_GTO_MAX_SHELL, "%s: nshell = %d (1 .. %d)", who, nshell,
-                  OOVQE_GTO_MAX_SHELL);
-    OOVQE_REQUIRE(max_nprim >= 1 && max_nprim <= OOVQE_GTO_MAX_PRIM, "%s: %d primitives per shell (1 .. %d)", who,
-                  max_nprim, OOVQE_GTO_MAX_PRIM);
-    OOVQE_REQUIRE(batch >= 0, "%s: batch = %d", who, batch);
-    return 0;
-}
-
 extern "C" int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch)
 {
     if (gto_check_sizes("oovqe_gto_work_size", nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
@@ -668,25 +471,28 @@ template <int LA, int LB, int LC, int LD> int gto_launch_eri(const gto_launch_t&
 }
 }  // namespace
 
-extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
-                                         const double* coefs, int natm, const double* charges, int batch,
-                                         const double* coords, int nao, double* overlap, double* h_ao, double* g_ao,
-                                         double* nuc, double* work, oovqe_stream_t stream)
+// What every entry point that consumes pair data does first: the shell table is checked against the limits, the pair
+// classes counted, ao_off / class lists (gto_setup_kernel) and the pair data of every geometry (gto_pair_kernel; nuc
+// may be null) written into `work`.  batch = 0 leaves p->batch = 0 and launches nothing.
+int gto_prepare(const char* who, int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                const double* coefs, int natm, const double* charges, int batch, const double* coords, int nao,
+                double* nuc, double* work, hipStream_t st, gto_prep_t* p)
 {
-    const char* who = "oovqe_gto_integrals_batch";
     OOVQE_REQUIRE(nshell >= 1 && nshell <= OOVQE_GTO_MAX_SHELL, "%s: nshell = %d (1 .. %d)", who, nshell,
                   OOVQE_GTO_MAX_SHELL);
     OOVQE_REQUIRE(batch >= 0 && natm >= 1 && nprim_total >= 1, "%s: batch = %d, natm = %d, nprim_total = %d", who,
                   batch, natm, nprim_total);
+    p->batch = batch;
     if (batch == 0) return 0;
     OOVQE_REQUIRE(shells && exps && coefs && charges && coords && work, "%s: null pointer", who);
-    hipStream_t st = (hipStream_t)stream;
     // the shell table is read back once per call (16 bytes per shell): the limits below are enforced here, with a
     // return code, and the launches are sized from it
     std::vector<int32_t> tab((size_t)nshell * 4);
     OOVQE_CHECK_HIP(hipMemcpyAsync(tab.data(), shells, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st), who);
     OOVQE_CHECK_HIP(hipStreamSynchronize(st), who);
-    int cnt[GTO_NCLS] = {0}, ao = 0, kp = 0;
+    int* cnt = p->cnt;
+    for (int c = 0; c < GTO_NCLS; ++c) cnt[c] = 0;
+    int ao = 0, kp = 0;
     for (int s = 0; s < nshell; ++s) {
         const int atom = tab[4 * s], l = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
         OOVQE_REQUIRE(l >= 0 && l <= OOVQE_GTO_MAX_L, "%s: shell %d has l = %d (s and p shells only, l <= %d)", who,
@@ -707,8 +513,9 @@ extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int 
         }
     kp *= kp;
     const long npair = (long)nshell * (nshell + 1) / 2;
-    int* iw = reinterpret_cast<int*>(work);
-    double* pairs = work + gto_int_doubles(nshell);
+    int* iw = p->iw = reinterpret_cast<int*>(work);
+    double* pairs = p->pairs = work + gto_int_doubles(nshell);
+    p->kp = kp;
     hipLaunchKernelGGL(gto_setup_kernel, dim3(1), dim3(64), 0, st, shells, nshell, iw);
     OOVQE_CHECK_LAUNCH("gto_setup_kernel");
     const long pt = npair * kp * batch;
@@ -716,9 +523,25 @@ extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int 
     hipLaunchKernelGGL(gto_pair_kernel, dim3((unsigned)((pt + 255) / 256)), dim3(256), 0, st, shells, nshell, exps,
                        coefs, charges, natm, coords, batch, kp, pairs, nuc);
     OOVQE_CHECK_LAUNCH("gto_pair_kernel");
+    return 0;
+}
+
+extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                         const double* coefs, int natm, const double* charges, int batch,
+                                         const double* coords, int nao, double* overlap, double* h_ao, double* g_ao,
+                                         double* nuc, double* work, oovqe_stream_t stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    gto_prep_t p;
+    int rc = gto_prepare("oovqe_gto_integrals_batch", nshell, shells, nprim_total, exps, coefs, natm, charges, batch,
+                         coords, nao, nuc, work, st, &p);
+    if (rc != 0 || batch == 0) return rc;
+    const int* cnt = p.cnt;
+    const int* iw = p.iw;
+    const double* pairs = p.pairs;
+    const int kp = p.kp;
     const gto_launch_t a = {iw, shells, nshell, cnt, charges, natm, coords, batch, pairs, kp, nao, overlap, h_ao,
                             g_ao, st};
-    int rc = 0;
     if (overlap || h_ao) {
         if ((rc = gto_launch_one<0, 0>(a)) != 0) return rc;
         if ((rc = gto_launch_one<1, 0>(a)) != 0) return rc;

@@ -154,6 +154,17 @@ class GTOBasis:
             buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
         return buf
 
+    def gradient_work(self, device, G):
+        """Work buffer of ``oovqe_gto_gradient_batch`` for G geometries, one per (device, stream) like ``work``."""
+        key = ("gradient", str(device), torch.cuda.current_stream().cuda_stream)
+        buf = self._work.get(key)
+        size = int(_lib.load().oovqe_gto_gradient_work_size(self.nshell, self.max_nprim, self.natm, G))
+        if size < 0:
+            check(size, "oovqe_gto_gradient_work_size")
+        if buf is None or buf.numel() < size:
+            buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
+        return buf
+
 
 def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=None, nuc=None):
     """The integrals of the geometries ``coords_bohr`` ([G, natm, 3] device tensor, Bohr) written into the given
@@ -172,6 +183,60 @@ def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=Non
         basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
         dptr(t.charges), G, dptr(coords_bohr), N, dptr(overlap), dptr(int1e_ao), dptr(int2e_ao), dptr(nuc),
         dptr(work), stream_ptr()), "oovqe_gto_integrals_batch")
+
+
+def gradient_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True, work=None):
+    """``gradient_batch`` for geometries that are already a [G, natm, 3] device tensor in Bohr, on the current stream.
+    ``work``: a buffer of ``oovqe_gto_gradient_work_size`` doubles to use instead of the basis' own."""
+    lib = _lib.load()
+    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
+            basis.natm, 3):
+        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
+                         f"[G, {basis.natm}, 3]")
+    G, N = int(coords_bohr.shape[0]), basis.nao
+    dev = coords_bohr.device
+    t = basis.device_tables(dev)
+    ins = []
+    for name, x, shape in (("dm1", dm1, (G, N, N)), ("wq", wq, (G, N, N)), ("dm2", dm2, (G, N, N, N, N))):
+        if x is not None:
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != shape:
+                raise ValueError(f"{name} has shape {tuple(getattr(x, 'shape', ()))}, expected {shape}")
+            x = x.to(device=dev, dtype=F64).contiguous()
+        ins.append(x)
+    grad = torch.empty((G, basis.natm, 3), dtype=F64, device=dev)
+    if G == 0:
+        return grad
+    if work is None:
+        work = basis.gradient_work(dev, G)
+    xyz = coords_bohr.to(F64).contiguous()
+    check(lib.oovqe_gto_gradient_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(xyz), N, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), int(bool(nuc)), dptr(grad),
+        dptr(work), stream_ptr()), "oovqe_gto_gradient_batch")
+    return grad
+
+
+def gradient_batch(basis, coords, dm1=None, wq=None, dm2=None, nuc=True):
+    """Derivative integrals of G geometries contracted with densities on the device (``oovqe_gto_gradient_batch``,
+    csrc/gto_grad.hip; no derivative integral is stored):
+
+        grad[g, A, :] = dm1[g] . dh/dR_A + wq[g] . dS/dR_A + 1/2 dm2[g] . d(pq|rs)/dR_A + (nuc) dE_nuc/dR_A
+
+    Args:
+        basis: GTOBasis
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        dm1, wq: [G, N, N] device tensors, taken as symmetric -- symmetrising them is the caller's business (of the
+            two elements (p, q) and (q, p) only one is read, once per shell pair; a non-symmetric matrix is not an
+            error, it gives the gradient for the matrix mirrored from the elements read)
+        dm2: [G, N, N, N, N] with the 8-fold symmetry of ``int2e_ao`` (``nucgrad.cas_ao_densities`` makes one),
+            likewise the caller's business
+        nuc: add the derivative of the nuclear repulsion
+        (None skips a term)
+
+    Returns [G, natm, 3] on the device, in Hartree / Bohr.  A geometry's gradient has the same bits whatever stack it
+    is part of."""
+    device = _lib.require_device()
+    return gradient_into(basis, coords_to_device(basis, coords, device), dm1, wq, dm2, nuc)
 
 
 def sym_invsqrt_batch(S, out=None):

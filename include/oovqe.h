@@ -686,6 +686,34 @@ int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* i
  * integral kernels. */
 int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream);
 
+/* ---- nuclear gradients of a stack of geometries (gto_grad.hip): the derivatives of the integrals above with respect to
+ * the nuclear coordinates, contracted on the fly with densities (no derivative integral is stored).  Basis tables,
+ * limits and conventions are those of oovqe_gto_integrals_batch (coords in Bohr); for every geometry b and atom A
+ *   grad[b][A][:] = sum_pq d1[b][p][q] dh[p][q]/dR_A + sum_pq wq[b][p][q] dS[p][q]/dR_A
+ *                 + 1/2 sum_pqrs d2[b][p][q][r][s] d(pq|rs)/dR_A + (with_nuc != 0) dE_nuc/dR_A     (Hartree / Bohr)
+ * with h = kinetic + nuclear attraction (the derivative of the operator on every nucleus included).  d1, wq
+ * [batch][nao][nao] are taken as symmetric and d2 [batch][nao]^4 as carrying the 8-fold symmetry of the integrals (only
+ * the elements of shell pairs i >= j and of unique shell quartets are read): symmetrising them is the caller's
+ * business.  A null d1, wq or d2 skips that term.  No floating-point atomics: partial sums go to the work buffer and
+ * are added per geometry in a fixed order, so a geometry's gradient has the same bits whatever stack it is part of.
+ * work: oovqe_gto_gradient_work_size(nshell, largest number of primitives of a shell, natm, batch) doubles (answers
+ * without a device; a negative code beyond the limits); batch <= 65535. */
+int64_t oovqe_gto_gradient_work_size(int nshell, int max_nprim, int natm, int batch);
+int oovqe_gto_gradient_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                             const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                             int nao, const double* d1, const double* wq, const double* d2, int with_nuc, double* grad,
+                             double* work, oovqe_stream_t stream);
+/* AO densities of a CAS wave function for the call above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
+ * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
+ * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
+ *   d1 = Dc + Da, Dc = 2 C_c C_c^T, Da = C_a gamma C_a^T;
+ *   d2 = sym8[ Dc_pq Dc_rs - Dc_pr Dc_qs / 2 + 2 (Dc_pq Da_rs - Dc_pr Da_qs / 2) + sum_tuvw Gamma_tuvw C_pt C_qu C_rv C_sw ],
+ * sym8 the average over the 8 index permutations of (pq|rs), so that E = d1 . h + 1/2 d2 . g + nuc; each unique
+ * element is computed once and stored to its (up to 8) places.  ncas = 0 (gamma, Gamma null) is the closed-shell
+ * case.  Either output may be null.  n <= OOVQE_INVSQRT_MAX_N, ncas <= 8, batch <= 65535. */
+int oovqe_cas_ao_densities_batch(const double* mo_coeff, int n, int n_core, int ncas, const double* gamma,
+                                 const double* Gamma, int batch, double* d1, double* d2, oovqe_stream_t stream);
+
 /* ---- restricted Hartree-Fock for a stack of geometries (auto_oo_amd/csrc/scf.hip) -----------------------------------
  * j[b,p,q] = sum_rs g[b,p,q,r,s] d[b,r,s], k[b,p,q] = sum_rs g[b,p,r,q,s] d[b,r,s]   (g [batch][n]^4, d, j, k
  * [batch][n][n], 1 <= n <= OOVQE_INVSQRT_MAX_N).  One pass over g, no symmetry of g or d assumed, no floating-point
