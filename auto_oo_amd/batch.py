@@ -223,10 +223,12 @@ class OO_pqc_batch:
         if self.basis is None or self.coords_bohr is None:
             raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries")
         if index is None:
-            return list(range(self.G))
-        rows = [int(i) for i in np.atleast_1d(index)]
-        if any(not 0 <= r < self.G for r in rows):
-            raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+            rows = list(range(self.G))
+        else:
+            rows = [int(i) for i in np.atleast_1d(index)]
+            if any(not 0 <= r < self.G for r in rows):
+                raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+        GTO.refuse_d_gradient(self.basis)         # before anything is launched
         return rows
 
     def _dm2_buffer(self, n):

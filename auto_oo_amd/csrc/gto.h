@@ -9,7 +9,7 @@
 #include <utility>
 #include <vector>
 
-#define GTO_LMAX 1
+#define GTO_LMAX 2
 #define GTO_NCLS ((GTO_LMAX + 1) * (GTO_LMAX + 2) / 2)
 #define GTO_PW 8                 // doubles per primitive pair
 #define GTO_NT 64                // threads per workgroup of the integral kernels (one wave)
@@ -41,17 +41,31 @@ template <int SPLIT> __host__ __device__ __forceinline__ double gto_group_sum(do
     return x;
 }
 
-__host__ __device__ constexpr int gto_ncomp(int l) { return l == 0 ? 1 : 3; }
-// power of coordinate d in Cartesian component c of a shell of angular momentum l (s; px, py, pz)
-__host__ __device__ constexpr int gto_pow(int l, int c, int d) { return (l == 1 && c == d) ? 1 : 0; }
+// Cartesian components of a shell of angular momentum l
+__host__ __device__ constexpr int gto_ncomp(int l) { return l == 0 ? 1 : (l == 1 ? 3 : 6); }
+// power of coordinate d in Cartesian component c of a shell of angular momentum l (s; px, py, pz; dxx, dxy, dxz, dyy,
+// dyz, dzz: one hexadecimal digit per component, c = 0 the lowest)
+__host__ __device__ constexpr int gto_pow(int l, int c, int d)
+{
+    return l == 2 ? (((d == 0 ? 0x000112 : (d == 1 ? 0x012010 : 0x210100)) >> (4 * c)) & 15)
+                  : ((l == 1 && c == d) ? 1 : 0);
+}
 __host__ __device__ constexpr int gto_cls(int la, int lb) { return la * (la + 1) / 2 + lb; }
+// the l field of a row of the shell table: angular momentum in the low byte, OOVQE_GTO_CARTESIAN for a d shell of 6
+// Cartesian functions (without it: 5 real solid harmonics)
+__host__ __device__ constexpr int gto_l_of(int field) { return field & 255; }
+__host__ __device__ constexpr int gto_nfunc(int field)
+{
+    return gto_l_of(field) == 2 ? ((field & OOVQE_GTO_CARTESIAN) ? 6 : 5) : gto_ncomp(gto_l_of(field));
+}
 
 // ---- Boys function -------------------------------------------------------------------------------------------
 // F_n(T) = int_0^1 t^2n exp(-T t^2) dt, n = 0 .. L.
 // T < 5: F_L = exp(-T) sum_k (2T)^k / ((2L+1)(2L+3)...(2L+2k+1)) (all terms positive), then downwards
 // F_{n-1} = (2T F_n + exp(-T)) / (2n - 1) (a sum of positive terms).  T >= 5: F_0 = sqrt(pi/T) erf(sqrt T) / 2, then
 // upwards F_{n+1} = ((2n+1) F_n - exp(-T)) / (2T): for T >= 5 and n <= 4 the subtraction loses less than a bit per
-// step.  Against 40-digit arithmetic this scheme in fp64 is within 6.4e-16 relative for n <= 4 on [0, 2000].
+// step.  Against 40-digit arithmetic this scheme in fp64 is within 6.4e-16 relative for n <= 4 on [0, 2000]; for the
+// orders 5 .. 8 of the d classes see DESIGN.md ("d shells").
 template <int L> __host__ __device__ __forceinline__ void gto_boys(double T, double (&F)[L + 1])
 {
     const double et = exp(-T);
@@ -205,6 +219,15 @@ static inline int gto_check_sizes(const char* who, int nshell, int max_nprim, in
     return 0;
 }
 
+struct gto_launch_t {
+    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
+    const double* coords; int batch; const double* pairs; int kp; int nao; double* overlap; double* h_ao;
+    double* g_ao; hipStream_t st;
+};
+// the classes with a d shell (gto_d.hip)
+int gto_d_launch_one_electron(const gto_launch_t& a);
+int gto_d_launch_two_electron(const gto_launch_t& a);
+
 struct gto_prep_t {
     int cnt[GTO_NCLS];          // shell pairs per class
     int kp;                     // slots per shell pair of the pair data (largest primitive count squared)
@@ -212,6 +235,6 @@ struct gto_prep_t {
     int* iw;                    // ao_off | class lists
     double* pairs;              // pair data [batch][npair][kp][GTO_PW]
 };
-int gto_prepare(const char* who, int nshell, const int32_t* shells, int nprim_total, const double* exps,
+int gto_prepare(const char* who, int max_l, int nshell, const int32_t* shells, int nprim_total, const double* exps,
                 const double* coefs, int natm, const double* charges, int batch, const double* coords, int nao,
                 double* nuc, double* work, hipStream_t st, gto_prep_t* p);

@@ -1,8 +1,10 @@
-// Batched Gaussian integrals over a stack of geometries (gfx950): contracted Cartesian s and p shells,
-// McMurchie-Davidson.  One basis description (shell table, exponents, normalised contraction coefficients,
+// Batched Gaussian integrals over a stack of geometries (gfx950): contracted s, p and d shells (d as 5 real solid
+// harmonics or 6 Cartesian functions), McMurchie-Davidson.  The kernels of this file serve the classes of s and p
+// shells; every class with a d shell is served by the workgroup-per-quartet kernels of gto_d.hip.  One basis description (shell table, exponents, normalised contraction coefficients,
 // charges) is shared by all geometries; the geometry index is a grid dimension of every kernel.
 //
-//   gto_setup_kernel   AO offset of every shell and the shell pairs i >= j sorted into classes (la >= lb: ss, ps, pp)
+//   gto_setup_kernel   AO offset of every shell and the shell pairs i >= j sorted into classes (la >= lb: ss, ps, pp,
+//                      ds, dp, dd)
 //   gto_pair_kernel    per geometry and primitive pair: p, P, c_a c_b exp(-mu |AB|^2), 1/(2p), a/p, b/p
 //                      (8 doubles, in the work buffer) and the nuclear repulsion of the geometry.  The Hermite
 //                      coefficients E_t^{ij} per dimension are polynomials in (P - A, P - B, 1/2p) times the
@@ -16,8 +18,8 @@
 //
 // The device helpers (Boys function, Hermite coefficients, R_tuv, the readers of the pair data) live in gto.h, shared
 // with the nuclear-derivative kernels of gto_grad.hip.
-// l is a template parameter everywhere; GTO_LMAX = 1 limits what is instantiated (and the component tables
-// gto_ncomp / gto_pow are written for l <= 1).  Every per-thread array is indexed by compile-time constants
+// l is a template parameter everywhere; these kernels are instantiated for l <= 1 (the component tables gto_ncomp /
+// gto_pow are written for l <= GTO_LMAX = 2).  Every per-thread array is indexed by compile-time constants
 // (static_for / fully unrolled loops of constant trip count), so none of them lives in scratch.
 #include "gto.h"
 
@@ -27,7 +29,7 @@ __host__ __device__ inline void gto_setup_body(const int* __restrict__ shells, i
     int off = 0;
     for (int s = 0; s < nshell; ++s) {
         iw[s] = off;
-        off += gto_ncomp(shells[4 * s + 1]);
+        off += gto_nfunc(shells[4 * s + 1]);
     }
     int cnt[GTO_NCLS];
 #pragma unroll
@@ -35,7 +37,7 @@ __host__ __device__ inline void gto_setup_body(const int* __restrict__ shells, i
     int* lists = iw + nshell;
     for (int i = 0; i < nshell; ++i) {
         for (int j = 0; j <= i; ++j) {
-            const int li = shells[4 * i + 1], lj = shells[4 * j + 1];
+            const int li = gto_l_of(shells[4 * i + 1]), lj = gto_l_of(shells[4 * j + 1]);
             const int hi = (li >= lj) ? i : j, lo = (li >= lj) ? j : i;
             const int cls = gto_cls(li >= lj ? li : lj, li >= lj ? lj : li);
 #pragma unroll
@@ -438,12 +440,6 @@ extern "C" int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch)
 }
 
 namespace {
-struct gto_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
-    const double* coords; int batch; const double* pairs; int kp; int nao; double* overlap; double* h_ao;
-    double* g_ao; hipStream_t st;
-};
-
 template <int LA, int LB> int gto_launch_one(const gto_launch_t& a)
 {
     const int count = a.cnt[gto_cls(LA, LB)];
@@ -474,7 +470,7 @@ template <int LA, int LB, int LC, int LD> int gto_launch_eri(const gto_launch_t&
 // What every entry point that consumes pair data does first: the shell table is checked against the limits, the pair
 // classes counted, ao_off / class lists (gto_setup_kernel) and the pair data of every geometry (gto_pair_kernel; nuc
 // may be null) written into `work`.  batch = 0 leaves p->batch = 0 and launches nothing.
-int gto_prepare(const char* who, int nshell, const int32_t* shells, int nprim_total, const double* exps,
+int gto_prepare(const char* who, int max_l, int nshell, const int32_t* shells, int nprim_total, const double* exps,
                 const double* coefs, int natm, const double* charges, int batch, const double* coords, int nao,
                 double* nuc, double* work, hipStream_t st, gto_prep_t* p)
 {
@@ -494,21 +490,25 @@ int gto_prepare(const char* who, int nshell, const int32_t* shells, int nprim_to
     for (int c = 0; c < GTO_NCLS; ++c) cnt[c] = 0;
     int ao = 0, kp = 0;
     for (int s = 0; s < nshell; ++s) {
-        const int atom = tab[4 * s], l = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
-        OOVQE_REQUIRE(l >= 0 && l <= OOVQE_GTO_MAX_L, "%s: shell %d has l = %d (s and p shells only, l <= %d)", who,
-                      s, l, OOVQE_GTO_MAX_L);
+        const int atom = tab[4 * s], field = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
+        const int l = gto_l_of(field);
+        OOVQE_REQUIRE(field >= 0 && l <= OOVQE_GTO_MAX_L && (field == l || (l == 2 && field == (2 | OOVQE_GTO_CARTESIAN))),
+                      "%s: shell %d has the l field %d (l <= %d; OOVQE_GTO_CARTESIAN on a d shell only)", who, s, field,
+                      OOVQE_GTO_MAX_L);
+        OOVQE_REQUIRE(l <= max_l, "%s: shell %d has l = %d: this entry serves s and p shells only (l <= %d)", who, s, l,
+                      max_l);
         OOVQE_REQUIRE(np >= 1 && np <= OOVQE_GTO_MAX_PRIM, "%s: shell %d has %d primitives (1 .. %d)", who, s, np,
                       OOVQE_GTO_MAX_PRIM);
         OOVQE_REQUIRE(atom >= 0 && atom < natm, "%s: shell %d sits on atom %d of %d", who, s, atom, natm);
         OOVQE_REQUIRE(off >= 0 && off + np <= nprim_total, "%s: shell %d reads primitives %d .. %d of %d", who, s,
                       off, off + np - 1, nprim_total);
-        ao += gto_ncomp(l);
+        ao += gto_nfunc(field);
         kp = np > kp ? np : kp;
     }
     OOVQE_REQUIRE(ao == nao, "%s: the shell table has %d functions, nao = %d", who, ao, nao);
     for (int i = 0; i < nshell; ++i)
         for (int j = 0; j <= i; ++j) {
-            const int li = tab[4 * i + 1], lj = tab[4 * j + 1];
+            const int li = gto_l_of(tab[4 * i + 1]), lj = gto_l_of(tab[4 * j + 1]);
             cnt[gto_cls(li >= lj ? li : lj, li >= lj ? lj : li)] += 1;
         }
     kp *= kp;
@@ -533,7 +533,7 @@ extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int 
 {
     hipStream_t st = (hipStream_t)stream;
     gto_prep_t p;
-    int rc = gto_prepare("oovqe_gto_integrals_batch", nshell, shells, nprim_total, exps, coefs, natm, charges, batch,
+    int rc = gto_prepare("oovqe_gto_integrals_batch", OOVQE_GTO_MAX_L, nshell, shells, nprim_total, exps, coefs, natm, charges, batch,
                          coords, nao, nuc, work, st, &p);
     if (rc != 0 || batch == 0) return rc;
     const int* cnt = p.cnt;
@@ -543,12 +543,15 @@ extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int 
     const gto_launch_t a = {iw, shells, nshell, cnt, charges, natm, coords, batch, pairs, kp, nao, overlap, h_ao,
                             g_ao, st};
     if (overlap || h_ao) {
+        if ((rc = gto_d_launch_one_electron(a)) != 0) return rc;
         if ((rc = gto_launch_one<0, 0>(a)) != 0) return rc;
         if ((rc = gto_launch_one<1, 0>(a)) != 0) return rc;
         if ((rc = gto_launch_one<1, 1>(a)) != 0) return rc;
     }
     if (g_ao) {
-        // bra class >= ket class; the most numerous (and cheapest) classes last, behind the long threads of (pp|pp)
+        // bra class >= ket class; the most numerous (and cheapest) classes last, behind the classes with a d shell
+        // (gto_d.hip) and the long threads of (pp|pp)
+        if ((rc = gto_d_launch_two_electron(a)) != 0) return rc;
         if ((rc = gto_launch_eri<1, 1, 1, 1>(a)) != 0) return rc;
         if ((rc = gto_launch_eri<1, 1, 1, 0>(a)) != 0) return rc;
         if ((rc = gto_launch_eri<1, 1, 0, 0>(a)) != 0) return rc;
@@ -589,7 +592,11 @@ extern "C" int oovqe_boys(int nmax, const double* t, int64_t count, double* f, o
     case 1: hipLaunchKernelGGL(gto_boys_kernel<1>, grid, block, 0, st, t, (long)count, f); break;
     case 2: hipLaunchKernelGGL(gto_boys_kernel<2>, grid, block, 0, st, t, (long)count, f); break;
     case 3: hipLaunchKernelGGL(gto_boys_kernel<3>, grid, block, 0, st, t, (long)count, f); break;
-    default: hipLaunchKernelGGL(gto_boys_kernel<4>, grid, block, 0, st, t, (long)count, f); break;
+    case 4: hipLaunchKernelGGL(gto_boys_kernel<4>, grid, block, 0, st, t, (long)count, f); break;
+    case 5: hipLaunchKernelGGL(gto_boys_kernel<5>, grid, block, 0, st, t, (long)count, f); break;
+    case 6: hipLaunchKernelGGL(gto_boys_kernel<6>, grid, block, 0, st, t, (long)count, f); break;
+    case 7: hipLaunchKernelGGL(gto_boys_kernel<7>, grid, block, 0, st, t, (long)count, f); break;
+    default: hipLaunchKernelGGL(gto_boys_kernel<8>, grid, block, 0, st, t, (long)count, f); break;
     }
     OOVQE_CHECK_LAUNCH("gto_boys_kernel");
     return 0;

@@ -623,7 +623,8 @@ extern "C" int oovqe_gto_gradient_batch(int nshell, const int32_t* shells, int n
     hipStream_t st = (hipStream_t)stream;
     gto_prep_t p;
     OOVQE_REQUIRE(batch <= 65535, "%s: batch = %d (at most 65535 geometries per call)", who, batch);
-    int rc = gto_prepare(who, nshell, shells, nprim_total, exps, coefs, natm, charges, batch, coords, nao, nullptr, work,
+    // (derivatives of d shells need f-type intermediates: a table with l = 2 is refused, before any launch)
+    int rc = gto_prepare(who, 1, nshell, shells, nprim_total, exps, coefs, natm, charges, batch, coords, nao, nullptr, work,
                          st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(grad, "%s: null pointer", who);

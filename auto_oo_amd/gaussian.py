@@ -1,4 +1,5 @@
-"""AO integrals and RHF orbitals for s/p Gaussian basis sets (STO-3G), on the host.
+"""AO integrals and RHF orbitals for s/p Gaussian basis sets (STO-3G), on the host (and, as a test oracle for the device
+kernels only, of tables with d shells: ``integrals_from_table``).
 
 SURVEY.md section 8(f) rank 3: the reference's ``Moldata_pyscf`` (src/auto_oo/moldata_pyscf.py:19-61)
 gets its arrays from PySCF / libcint -- ``int1e_kin + int1e_nuc``, ``int2e``, ``int1e_ovlp``,
@@ -117,6 +118,91 @@ class _Shell:
         a, b = self.exps[:, None], self.exps[None, :]
         s = (np.pi / (a + b)) ** 1.5 / (2 * (a + b)) ** L
         self.coefs = self.coefs / np.sqrt(self.coefs @ s @ self.coefs)
+
+
+# ---- d shells (additions; nothing above or below calls them, and the device path never does) ------------------------
+# ``_Shell`` normalises the radial part for a product of first powers: of the components of a d shell xy, xz, yz come
+# out with norm 1 and xx, yy, zz with norm^2 = 3.  ``component_norm`` is the missing factor.
+CARTESIAN_D = ((2, 0, 0), (1, 1, 0), (1, 0, 1), (0, 2, 0), (0, 1, 1), (0, 0, 2))      # xx, xy, xz, yy, yz, zz
+_CARTESIAN = {0: ((0, 0, 0),), 1: ((1, 0, 0), (0, 1, 0), (0, 0, 1)), 2: CARTESIAN_D}
+# real solid harmonics m = -2 .. 2 (xy, yz, 3z^2 - r^2, xz, x^2 - y^2; PySCF's order and signs) in the six Cartesian
+# functions, each of these normalised to 1
+_SPHERICAL_D = np.array([[0.0, 1.0, 0.0, 0.0, 0.0, 0.0],
+                         [0.0, 0.0, 0.0, 0.0, 1.0, 0.0],
+                         [-0.5, 0.0, 0.0, -0.5, 0.0, 1.0],
+                         [0.0, 0.0, 1.0, 0.0, 0.0, 0.0],
+                         [0.75 ** 0.5, 0.0, 0.0, -(0.75 ** 0.5), 0.0, 0.0]])
+
+
+def component_norm(lmn):
+    """Factor that normalises the component x^l y^m z^n of a ``_Shell`` to 1: 1 / sqrt((2l-1)!! (2m-1)!! (2n-1)!!)."""
+    f = 1.0
+    for k in lmn:
+        for odd in range(2 * k - 1, 1, -2):
+            f *= odd
+    return 1.0 / np.sqrt(f)
+
+
+def normalised_shell(center, lmn, exps, coefs):
+    """A ``_Shell`` whose component is normalised to 1 for every (l, m, n)."""
+    sh = _Shell(center, lmn, exps, coefs)
+    sh.coefs = sh.coefs * component_norm(lmn)
+    return sh
+
+
+def shells_from_table(table, coords_bohr):
+    """Host shells of a ``GTOBasis``-style table ``[(atom, l, exponents, coefficients), ...]`` (``GTOBasis.table``) on
+    the centres ``coords_bohr`` [natm, 3]: one normalised Cartesian function per component, per shell in the order
+    s; x, y, z; xx, xy, xz, yy, yz, zz."""
+    out = []
+    for atom, l, ex, co in table:
+        for lmn in _CARTESIAN[int(l)]:
+            out.append(normalised_shell(coords_bohr[atom], lmn, ex, co))
+    return out
+
+
+def basis_transform(table, d_functions):
+    """[nao, ncart]: the functions of the basis in the Cartesian functions of ``shells_from_table``.  The identity for
+    ``d_functions="cartesian"``; for ``"spherical"`` every d shell becomes its 5 real solid harmonics."""
+    if d_functions not in ("spherical", "cartesian"):
+        raise ValueError(f"d_functions = {d_functions!r} ('spherical' or 'cartesian')")
+    blocks = [_SPHERICAL_D if (int(l) == 2 and d_functions == "spherical") else np.eye(len(_CARTESIAN[int(l)]))
+              for _, l, _, _ in table]
+    U = np.zeros((sum(b.shape[0] for b in blocks), sum(b.shape[1] for b in blocks)))
+    r = c = 0
+    for b in blocks:
+        U[r:r + b.shape[0], c:c + b.shape[1]] = b
+        r, c = r + b.shape[0], c + b.shape[1]
+    return U
+
+
+def cartesian_integrals_from_table(table, charges, coords_bohr, boys=None):
+    """(S, T + V, (pq|rs), nuclear repulsion) over the normalised Cartesian functions of ``shells_from_table``, on the
+    host.  ``boys``: a replacement of ``_boys`` for the duration of the call (the accuracy bounds perturb it)."""
+    global _boys
+    keep = _boys
+    if boys is not None:
+        _boys = boys
+    try:
+        shells = shells_from_table(table, coords_bohr)
+        S, T, V = one_electron_integrals(shells, charges, coords_bohr)
+        g = electron_repulsion_integrals(shells)
+    finally:
+        _boys = keep
+    nuc = sum(charges[i] * charges[j] / np.linalg.norm(coords_bohr[i] - coords_bohr[j])
+              for i in range(len(charges)) for j in range(i))
+    return S, T + V, g, nuc
+
+
+def transform_integrals(U, S, h, g, nuc):
+    """Integrals over Cartesian functions -> integrals over the functions ``U`` (``basis_transform``) stands for."""
+    return U @ S @ U.T, U @ h @ U.T, np.einsum("ap,bq,cr,ds,pqrs->abcd", U, U, U, U, g, optimize=True), nuc
+
+
+def integrals_from_table(table, charges, coords_bohr, d_functions="spherical", boys=None):
+    """(S, T + V, (pq|rs), nuclear repulsion) of a table with s, p and d shells on the host, in the chosen form."""
+    return transform_integrals(basis_transform(table, d_functions),
+                               *cartesian_integrals_from_table(table, charges, coords_bohr, boys))
 
 
 def sto3g_basis(symbols, coords_bohr):

@@ -2,7 +2,8 @@
 
 ``gaussian.py`` builds the integrals of ONE molecule with numpy loops on the host (0.7 s for formaldimine in
 STO-3G); a scan over the points of a Berry-phase loop spends its time there.  Here one basis description --
-``GTOBasis``: flat tables of contracted Cartesian s and p shells, built on the host once -- is shared by all
+``GTOBasis``: flat tables of contracted s, p and d shells (d as 5 spherical or 6 Cartesian functions), built on the
+host once -- is shared by all
 geometries, and ``integrals_batch`` fills overlap, core Hamiltonian, ``S^-1/2``, nuclear repulsion and ``(pq|rs)``
 of G geometries on the device.  Conventions are those of ``gaussian.py`` (atoms in input order; per atom 1s, 2s,
 2px, 2py, 2pz; contracted functions normalised); coordinates are in Angstrom here (``gaussian.BOHR``) and in Bohr
@@ -16,11 +17,12 @@ import torch
 
 from . import _lib
 from ._lib import check, dptr, stream_ptr
-from .gaussian import BOHR, _Shell, _STO3G, _STO3G_1S_COEF, _STO3G_2S_COEF, _STO3G_2P_COEF, zmatrix_to_cartesian
+from .gaussian import BOHR, _Shell, component_norm, _STO3G, _STO3G_1S_COEF, _STO3G_2S_COEF, _STO3G_2P_COEF, zmatrix_to_cartesian
 
 F64 = torch.float64
-MAX_L = 1                      # OOVQE_GTO_MAX_L
-MAX_PRIM = 6                   # OOVQE_GTO_MAX_PRIM
+MAX_L = 2                      # OOVQE_GTO_MAX_L
+MAX_PRIM = 10                  # OOVQE_GTO_MAX_PRIM
+CARTESIAN = 0x100              # OOVQE_GTO_CARTESIAN: flag of the l field of a d shell of 6 Cartesian functions
 INVSQRT_MAX_N = 64             # OOVQE_INVSQRT_MAX_N
 INVSQRT_MIN_EIG = 1e-8         # OOVQE_INVSQRT_MIN_EIG
 
@@ -46,18 +48,31 @@ class GTOBasis:
     Args:
         symbols: element symbols, in the order of the atoms of every geometry
         basis: ``"sto-3g"`` (the tables of ``gaussian.py``: H, C, N, O, F), or a dict
-            ``{element: [(l, exponents, coefficients), ...]}`` of s / p shells (``l`` = 0, 1 or ``"s"``, ``"p"``),
-            coefficients those of normalised primitives as basis-set tables list them
+            ``{element: [(l, exponents, coefficients), ...]}`` of s / p / d shells (``l`` = 0, 1, 2 or ``"s"``,
+            ``"p"``, ``"d"``), coefficients those of normalised primitives as basis-set tables list them, at most
+            ``MAX_PRIM`` primitives per shell.  Shells are segmented: a general contraction such as cc-pVDZ is
+            passed as one shell per contracted function, each repeating the primitives it uses.
+        d_functions: the form of the d shells, required as soon as the table holds one (there is no default between
+            5d and 6d).  ``"spherical"``: 5 functions per shell, each normalised, in the order xy, yz, 3z^2 - r^2, xz,
+            x^2 - y^2 (m = -2 .. 2, PySCF's order, with the signs of these polynomials).  ``"cartesian"``: 6
+            functions in the order xx, xy, xz, yy, yz, zz, EACH normalised to 1 -- libcint scales its Cartesian d
+            functions differently (there xx, yy, zz share the radial normalisation of xy and have norm^2 = 3).
 
-    Host arrays: ``shells`` [nshell, 4] int32 (atom, l, number of primitives, offset), ``exps``, ``coefs``
-    (contraction coefficients of the NORMALISED contracted function, primitive norms included -- ``_Shell.coefs``
-    of ``gaussian.py``), ``charges`` [natm]; ``nao``, ``nelectron`` (neutral molecule), ``max_nprim``.
+    Host arrays: ``shells`` [nshell, 4] int32 (atom, l field, number of primitives, offset; the l field of a Cartesian
+    d shell is ``2 | CARTESIAN``), ``exps``, ``coefs`` (contraction coefficients of the NORMALISED contracted
+    function, primitive norms included -- ``_Shell.coefs`` of ``gaussian.py``; for a d shell those that normalise
+    xx), ``charges`` [natm]; ``table`` [(atom, l, exponents, coefficients as given)]; ``nao``, ``nelectron`` (neutral
+    molecule), ``max_nprim``, ``max_l``.
     """
 
-    def __init__(self, symbols, basis="sto-3g"):
+    def __init__(self, symbols, basis="sto-3g", d_functions=None):
         self.symbols = [str(s) for s in symbols]
         if not self.symbols:
             raise ValueError("GTOBasis needs at least one atom")
+        if d_functions not in (None, "spherical", "cartesian"):
+            raise ValueError(f"d_functions = {d_functions!r} (None, 'spherical' or 'cartesian')")
+        self.d_functions = d_functions
+        self.table = []
         rows, exps, coefs, charges = [], [], [], []
         for atom, sym in enumerate(self.symbols):
             if isinstance(basis, str):
@@ -78,24 +93,32 @@ class GTOBasis:
                 if not isinstance(l, (int, np.integer)) or l < 0:
                     raise ValueError(f"shell of {sym!r}: angular momentum {l!r}")
                 if l > MAX_L:
-                    raise ValueError(f"shell of {sym!r} has l = {l}: only s and p shells (l <= {MAX_L}) are "
+                    raise ValueError(f"shell of {sym!r} has l = {l}: only s, p and d shells (l <= {MAX_L}) are "
                                      "implemented")
+                if l == 2 and d_functions is None:
+                    raise ValueError(f"shell of {sym!r} has l = 2: say which functions a d shell stands for, "
+                                     "d_functions='spherical' (5) or d_functions='cartesian' (6)")
                 ex = np.asarray(ex, dtype=np.float64).ravel()
                 co = np.asarray(co, dtype=np.float64).ravel()
                 if ex.size != co.size or not 1 <= ex.size <= MAX_PRIM:
                     raise ValueError(f"shell of {sym!r}: {ex.size} exponents, {co.size} coefficients "
                                      f"(1 .. {MAX_PRIM} primitives per shell)")
                 norm = _Shell(np.zeros(3), (int(l), 0, 0), ex, co)      # l <= 1: the same for px, py, pz
-                rows.append((atom, int(l), ex.size, len(exps)))
+                field = int(l) | (CARTESIAN if (l == 2 and d_functions == "cartesian") else 0)
+                rows.append((atom, field, ex.size, len(exps)))
+                self.table.append((atom, int(l), ex.copy(), co.copy()))
                 exps.extend(norm.exps.tolist())
-                coefs.extend(norm.coefs.tolist())
+                # (_Shell leaves xx with norm^2 = 3; the kernels take the coefficients that normalise xx)
+                coefs.extend((norm.coefs * component_norm((int(l), 0, 0))).tolist())
         self.shells = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
         self.exps = np.asarray(exps, dtype=np.float64)
         self.coefs = np.asarray(coefs, dtype=np.float64)
         self.charges = np.asarray(charges, dtype=np.float64)
         self.natm = len(self.symbols)
         self.nshell = self.shells.shape[0]
-        self.nao = int(sum(2 * l + 1 for l in self.shells[:, 1]))
+        ls = self.shells[:, 1] & 255
+        self.max_l = int(ls.max())
+        self.nao = int(sum(6 if f == (2 | CARTESIAN) else 2 * (f & 255) + 1 for f in self.shells[:, 1]))
         self.nelectron = int(round(self.charges.sum()))
         self.max_nprim = int(self.shells[:, 2].max())
         self._dev = {}
@@ -185,9 +208,17 @@ def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=Non
         dptr(work), stream_ptr()), "oovqe_gto_integrals_batch")
 
 
+def refuse_d_gradient(basis):
+    """Nuclear derivatives of d shells need f-type intermediates, which the derivative kernels do not have."""
+    if basis.max_l >= 2:
+        raise NotImplementedError("nuclear gradients are implemented for s and p shells only: this basis has d shells "
+                                  "(l = 2)")
+
+
 def gradient_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True, work=None):
     """``gradient_batch`` for geometries that are already a [G, natm, 3] device tensor in Bohr, on the current stream.
     ``work``: a buffer of ``oovqe_gto_gradient_work_size`` doubles to use instead of the basis' own."""
+    refuse_d_gradient(basis)
     lib = _lib.load()
     if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
             basis.natm, 3):
@@ -235,6 +266,7 @@ def gradient_batch(basis, coords, dm1=None, wq=None, dm2=None, nuc=True):
 
     Returns [G, natm, 3] on the device, in Hartree / Bohr.  A geometry's gradient has the same bits whatever stack it
     is part of."""
+    refuse_d_gradient(basis)
     device = _lib.require_device()
     return gradient_into(basis, coords_to_device(basis, coords, device), dm1, wq, dm2, nuc)
 
@@ -255,7 +287,7 @@ def sym_invsqrt_batch(S, out=None):
 
 
 def boys(nmax, T):
-    """F_0 .. F_nmax of the device Boys function for a device tensor T -> [len(T), nmax + 1]."""
+    """F_0 .. F_nmax (nmax <= 4 * MAX_L = 8) of the device Boys function for a device tensor T -> [len(T), nmax + 1]."""
     lib = _lib.load()
     T = T.contiguous()
     out = torch.empty((T.numel(), nmax + 1), dtype=F64, device=T.device)

@@ -654,12 +654,18 @@ int oovqe_ci_davidson_shift_batch(int ncas, int nelecas, int nroots, int batch, 
                                   double* energies, double* ci, double* s2, double* rnorm, int* info, double* work,
                                   oovqe_stream_t stream);
 
-/* ---- Gaussian integrals of a stack of geometries (gto.hip): contracted Cartesian s and p shells, McMurchie-Davidson.
- * One basis description is shared by all geometries, every array is a device array:
- *   shells [nshell][4] int32: atom index, l, number of primitives, offset of the shell's first primitive in exps / coefs
+/* ---- Gaussian integrals of a stack of geometries (gto.hip, gto_d.hip): contracted s, p and d shells,
+ * McMurchie-Davidson.  One basis description is shared by all geometries, every array is a device array:
+ *   shells [nshell][4] int32: atom index, l field, number of primitives, offset of the shell's first primitive in exps /
+ *     coefs.  The l field is the angular momentum 0, 1 or 2; a d shell written as 2 stands for its 5 real solid
+ *     harmonics, written as 2 | OOVQE_GTO_CARTESIAN for 6 Cartesian functions (the flag on any other shell is an error).
  *   exps, coefs [nprim_total]: exponents and contraction coefficients of the NORMALISED contracted function (primitive
- *     norms included), charges [natm], coords [batch][natm][3] in Bohr.
- * AO order: shells in table order, a p shell gives px, py, pz.  Outputs (each may be null to skip it): overlap and h_ao
+ *     norms included; for a d shell the coefficients that normalise x^2 times the radial part), charges [natm],
+ *     coords [batch][natm][3] in Bohr.  Shells are segmented: a general contraction is passed as one shell per
+ *     contracted function.
+ * AO order: shells in table order; a p shell gives px, py, pz; a spherical d shell xy, yz, 3z^2 - r^2, xz, x^2 - y^2
+ * (m = -2 .. 2, the signs of these polynomials), a Cartesian d shell xx, xy, xz, yy, yz, zz, every function normalised
+ * to 1 (libcint scales its Cartesian d functions differently: there xx has the norm^2 3).  Outputs (each may be null to skip it): overlap and h_ao
  * = kinetic + nuclear attraction [batch][nao][nao], exactly symmetric (each unique element computed once and stored to
  * both places); g_ao [batch][nao]^4 = (pq|rs), chemist order, every unique value stored to its (up to 8) symmetric
  * places from one register (oovqe_eri_ingest finds both symmetry flags); nuc [batch].
@@ -667,8 +673,9 @@ int oovqe_ci_davidson_shift_batch(int ncas, int nelecas, int nroots, int batch, 
  * OOVQE_GTO_MAX_PRIM primitives per shell, nshell <= OOVQE_GTO_MAX_SHELL, nao equal to the functions of the table.
  * The call reads the shell table back (one stream synchronisation) to enforce them and to size its launches.
  * work: oovqe_gto_work_size(nshell, largest number of primitives of a shell, batch) doubles. */
-#define OOVQE_GTO_MAX_L 1
-#define OOVQE_GTO_MAX_PRIM 6
+#define OOVQE_GTO_MAX_L 2
+#define OOVQE_GTO_MAX_PRIM 10
+#define OOVQE_GTO_CARTESIAN 0x100
 #define OOVQE_GTO_MAX_SHELL 128
 int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch);
 int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
@@ -682,13 +689,15 @@ int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int nprim_total
 #define OOVQE_INVSQRT_MAX_N 64
 #define OOVQE_INVSQRT_MIN_EIG 1e-8
 int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* info, oovqe_stream_t stream);
-/* f [count][nmax + 1] = F_0 .. F_nmax (Boys function) of t [count], nmax <= 4, through the device function of the
- * integral kernels. */
+/* f [count][nmax + 1] = F_0 .. F_nmax (Boys function) of t [count], nmax <= 4 * OOVQE_GTO_MAX_L = 8, through the
+ * device function of the integral kernels. */
 int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream);
 
 /* ---- nuclear gradients of a stack of geometries (gto_grad.hip): the derivatives of the integrals above with respect to
  * the nuclear coordinates, contracted on the fly with densities (no derivative integral is stored).  Basis tables,
- * limits and conventions are those of oovqe_gto_integrals_batch (coords in Bohr); for every geometry b and atom A
+ * limits and conventions are those of oovqe_gto_integrals_batch (coords in Bohr) except that s and p shells only are
+ * served: a table with a d shell (l = 2; its derivatives need f-type intermediates) is refused with a negative code
+ * before anything is launched.  For every geometry b and atom A
  *   grad[b][A][:] = sum_pq d1[b][p][q] dh[p][q]/dR_A + sum_pq wq[b][p][q] dS[p][q]/dR_A
  *                 + 1/2 sum_pqrs d2[b][p][q][r][s] d(pq|rs)/dR_A + (with_nuc != 0) dE_nuc/dR_A     (Hartree / Bohr)
  * with h = kinetic + nuclear attraction (the derivative of the operator on every nucleus included).  d1, wq
