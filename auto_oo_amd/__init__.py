@@ -12,9 +12,10 @@ _lib.load()   # fail loudly at import time when the HIP extension is missing
 from .pqc import Parameterized_circuit                      # noqa: E402
 from .moldata import Moldata, ao_to_oao, get_formal_geo                     # noqa: E402
 from .gaussian import Moldata_sto3g                         # noqa: E402
-from . import gto, nucgrad, scf                             # noqa: E402
+from . import gto, nucgrad, properties, scf                 # noqa: E402
 from .scf import RHFResult, rhf_batch                       # noqa: E402
-from .gto import GTOBasis, integrals_batch                  # noqa: E402
+from .gto import GTOBasis, integrals_batch, moment_integrals_batch   # noqa: E402
+from .properties import DEBYE, multipole_moments, traceless_quadrupole     # noqa: E402
 from .oo_pqc import OO_pqc                                  # noqa: E402
 from .batch import OO_pqc_batch                             # noqa: E402
 from .oo_energy import (                                    # noqa: E402
@@ -39,4 +40,5 @@ __all__ = [
     "int1e_transform", "int2e_transform", "general_4index_transform", "uniform_4index_transform",
     "vector_to_skew_symmetric", "skew_symmetric_to_vector", "non_redundant_indices", "NewtonStep", "BatchedNewtonStep", "ActiveSpaceRotation", "bogoliubov_atob_cas", "state_overlap",
     "generalized_pair_doubles", "active_space_integrals", "molecular_hamiltonian_coefficients", "casci", "CIResult",
+    "properties", "moment_integrals_batch", "multipole_moments", "traceless_quadrupole", "DEBYE",
 ]

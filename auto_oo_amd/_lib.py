@@ -225,6 +225,12 @@ SIGNATURES = {
     "oovqe_gto_gradient_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
                                                 ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int]
                                  + [c_double_p] * 3 + [ctypes.c_int] + [c_double_p] * 2 + [c_stream]),
+    "oovqe_gto_moments_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                               ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
+                                               ctypes.c_int] + [c_double_p] * 3 + [c_stream]),
+    "oovqe_gto_moments_expect_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                                      c_double_p, c_int32_p, c_double_p, c_stream]),
     "oovqe_cas_ao_densities_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                                     c_double_p, ctypes.c_int, c_double_p, c_double_p, c_stream]),
     "oovqe_fock_jk_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,

@@ -291,6 +291,116 @@ class OO_pqc_batch:
         return nucgrad.rhf_gradient(self.basis, self.coords_bohr[sel], result.mo_coeff, result.mo_energy,
                                     self.nelectron // 2)
 
+    # ---- dipole and second moments (auto_oo_amd/properties.py, csrc/gto_moments.hip) -----------------------------------
+    def _moment_rows(self, index, who):
+        if self.basis is None or self.coords_bohr is None:
+            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries")
+        if index is None:
+            return list(range(self.G))
+        rows = [int(i) for i in np.atleast_1d(index)]
+        if any(not 0 <= r < self.G for r in rows):
+            raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+        return rows
+
+    def _moments_of(self, rows, dens, order, origin, nuclear=True):
+        """Moments [len(rows), nd, 3 or 9] of the densities ``dens`` [len(rows), nd, N, N] at the geometries ``rows``;
+        ``origin`` [3] or [len(rows), 3] in Angstrom."""
+        from . import properties
+        sel = torch.as_tensor(rows, device=self.device)
+        o = GTO.origin_to_device(origin, len(rows), self.device, 1.0 / GTO.BOHR)
+        return properties.multipole_moments(self.basis, self.coords_bohr[sel], dens, order, o, nuclear)
+
+    def _state_density(self, thetas, rows):
+        """``D1`` [len(rows), N, N] of the circuit states at ``thetas`` and the batch's current orbitals, from the RDMs
+        the evaluation path makes (dense register: ``ops.circuit_rdms``; sector engine: the RDMs of
+        ``_evaluate_sector``)."""
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"the moments of a circuit state cover ncas <= {nucgrad.MAX_NCAS}")
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        pqc = self.pqc
+        if getattr(pqc, "_use_sector", False):
+            gamma, Gamma = pqc._sector.rdms(pqc._sector.state(thetas))
+        else:
+            gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
+                                            pqc._init_index, tangents=False)
+            gamma, Gamma = gamma[:, 0], Gamma[:, 0]
+        sel = torch.as_tensor(rows, device=self.device)
+        return nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel], Gamma[sel],
+                                        want_d2=False)[0]
+
+    def multipole_moments(self, thetas, order=2, index=None, origin=None):
+        """Dipole moment and second moments of every geometry's state at ``thetas`` [G, n_theta] and the batch's
+        current orbitals, in atomic units: ``mu = sum_A Z_A (R_A - O) - tr(D1 r)``, ``Q_ij = sum_A Z_A (R_A - O)_i
+        (R_A - O)_j - tr(D1 r_i r_j)`` (``properties.traceless_quadrupole`` makes the traceless form).
+
+        Args:
+            order: 2 -> (dipole [G, 3], second moments [G, 3, 3]); 1 -> the dipole alone
+            index: rows of the batch (default all); the result then has one entry per row asked for
+            origin: [3] or one [3] per row, in Angstrom like the geometries (default: the origin of the coordinates)
+
+        Expectation values of a state that is not variational in every parameter are not energy derivatives.  Needs a
+        batch made by ``from_geometries`` (RuntimeError otherwise); ncas <= 8.  Same bits whatever ``index``."""
+        rows = self._moment_rows(index, "multipole_moments")
+        GTO.moment_components(order)
+        from . import properties
+        out = self._moments_of(rows, self._state_density(thetas, rows)[:, None], order, origin)[:, 0]
+        return out if order == 1 else properties.split_moments(out)
+
+    def dipole_moment(self, thetas, index=None, origin=None):
+        """Dipole moment [G, 3] (device, atomic units; times ``properties.DEBYE`` for Debye) of every geometry's state
+        at ``thetas``: ``multipole_moments(thetas, order=1, ...)``."""
+        self._moment_rows(index, "dipole_moment")
+        return self.multipole_moments(thetas, order=1, index=index, origin=origin)
+
+    def rhf_dipole_moment(self, result=None, index=None, origin=None):
+        """Closed-shell Hartree-Fock dipole moment [G, 3] (device, atomic units) from a ``scf.RHFResult`` of the rows
+        ``index`` (default all; ``self.rhf(index=index)`` is run when none is given): ``D = 2 C_o C_o^T``."""
+        rows = self._moment_rows(index, "rhf_dipole_moment")
+        if result is None:
+            result = self.rhf(index=index)
+            scf.raise_unless_converged(result.info, rows)
+        if int(result.mo_coeff.shape[0]) != len(rows):
+            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
+                             "for")
+        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+        return self._moments_of(rows, d1[:, None], 1, origin)[:, 0]
+
+    def casci_dipole_matrix(self, nroots=2, fix_singlet=True, origin=None, tol=1e-9, max_iter=200):
+        """CASCI states of every geometry at its current orbitals (``casci``) and their dipole matrix -> (energies
+        [G, nroots], dipoles [G, nroots, nroots, 3]) on the device, atomic units.
+
+        ``dipoles[g, I, I]`` is the dipole moment of root I, nuclear part included.  ``dipoles[g, I, J]``, I != J, is
+        the transition dipole ``-tr(D^IJ r)`` with ``D^IJ = C_a gamma^IJ C_a^T`` and ``gamma^IJ = (<I|E_pq|J> +
+        <J|E_pq|I>) / 2``, taken as ``(gamma_+ - gamma_-) / 2`` from the RDMs of ``(c_I +- c_J) / sqrt 2``: no nuclear
+        term, and the core density drops out.  The matrix is symmetric in (I, J), exactly.  The SIGN of a transition
+        dipole is that of the product of the two CI vectors' signs, which ``casci`` fixes by making the largest
+        |component| of each vector positive; along a path on which that component changes, the sign can flip."""
+        rows = self._moment_rows(None, "casci_dipole_matrix")
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"casci_dipole_matrix covers ncas <= {nucgrad.MAX_NCAS}")
+        from . import ci
+        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        G, R, a = self.G, int(nroots), self.ncas
+        pairs = [(i, j) for i in range(R) for j in range(i)]
+        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
+        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
+        r2 = 0.5 ** 0.5
+        stack = torch.cat((vecs, r2 * (vecs[:, ii] + vecs[:, jj]), r2 * (vecs[:, ii] - vecs[:, jj])), dim=1)
+        n, P = R + 2 * len(pairs), len(pairs)
+        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
+        C = self.mo_coeff[:, None].expand(G, n, self.nao, self.nao).reshape(G * n, self.nao, self.nao)
+        d1 = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma, Gamma, want_d2=False)[0]
+        d1 = d1.reshape(G, n, self.nao, self.nao)
+        dens = torch.cat((d1[:, :R], 0.5 * (d1[:, R:R + P] - d1[:, R + P:])), dim=1)
+        val = self._moments_of(rows, dens, 1, origin, nuclear=[True] * R + [False] * P)
+        dip = torch.empty((G, R, R, 3), dtype=F64, device=self.device)
+        k = torch.arange(R, device=self.device)
+        dip[:, k, k] = val[:, :R]
+        if P:
+            dip[:, ii, jj] = val[:, R:]
+            dip[:, jj, ii] = val[:, R:]
+        return e, dip
+
     def _rhf_orbitals(self, how, rows):
         """``oao_mo_coeffs="rhf"``: the orbitals of the rows (None: all) from the device solver."""
         if how != "rhf":

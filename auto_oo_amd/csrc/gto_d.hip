@@ -19,18 +19,6 @@
 // instantiations compile in seconds, and no per-thread array is indexed at run time (no scratch).
 #include "gto.h"
 
-// (a CPU build that runs the lanes of a workgroup as host threads, for a thread sanitizer, defines GTO_HOST_BARRIER)
-__host__ __device__ __forceinline__ void gto_sync()
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __syncthreads();
-#elif defined(GTO_HOST_BARRIER)
-    GTO_HOST_BARRIER();
-#endif
-}
-// item i of fewer items than lanes belongs to lane i (to the only lane of a CPU build)
-__host__ __device__ __forceinline__ bool gto_mine(int i, int lane, int nlane) { return i % nlane == lane; }
-
 // (t, u, v), t + u + v <= L, packed: t ascending, then u, then v
 __host__ __device__ constexpr int gto_tet(int k) { return k * (k + 1) * (k + 2) / 6; }
 __host__ __device__ __forceinline__ int gto_ridx(int L, int t, int u, int v)
@@ -77,37 +65,6 @@ __host__ __device__ __forceinline__ void gto_R_build(double* Rn, const int* dec,
         }
         gto_sync();
     }
-}
-
-// One index of a component array in LDS, in place: the fibres of 6 Cartesian d components (xx, xy, xz, yy, yz, zz of a
-// radial part normalised for xx) become 6 normalised Cartesian functions or the 5 real solid harmonics
-// xy, yz, 3z^2 - r^2, xz, x^2 - y^2 (m = -2 .. 2) in the first 5 places.  A fibre is handled by one lane.
-__host__ __device__ __forceinline__ void gto_d_pass(double* a, int total, int stride, bool cartesian, int lane,
-                                                    int nlane)
-{
-    const double r3 = 1.7320508075688772935;
-    for (int i = lane; i < total; i += nlane) {
-        if ((i / stride) % 6 != 0) continue;
-        const double xx = a[i], xy = a[i + stride], xz = a[i + 2 * stride], yy = a[i + 3 * stride],
-                     yz = a[i + 4 * stride], zz = a[i + 5 * stride];
-        if (cartesian) {
-            a[i + stride] = r3 * xy;
-            a[i + 2 * stride] = r3 * xz;
-            a[i + 4 * stride] = r3 * yz;
-        } else {
-            a[i] = r3 * xy;
-            a[i + stride] = r3 * yz;
-            a[i + 2 * stride] = zz - 0.5 * (xx + yy);
-            a[i + 3 * stride] = r3 * xz;
-            a[i + 4 * stride] = (0.5 * r3) * (xx - yy);
-        }
-    }
-    gto_sync();
-}
-
-__host__ __device__ __forceinline__ double gto_pick(const double (&a)[3], int d)
-{
-    return d == 0 ? a[0] : (d == 1 ? a[1] : a[2]);
 }
 
 // ---- one-electron integrals of the pair classes ds, dp, dd -----------------------------------------------------------

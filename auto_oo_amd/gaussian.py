@@ -205,6 +205,39 @@ def integrals_from_table(table, charges, coords_bohr, d_functions="spherical", b
                                *cartesian_integrals_from_table(table, charges, coords_bohr, boys))
 
 
+# powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
+MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
+
+
+def moment_integrals_from_table(table, coords_bohr, d_functions="spherical", order=1, origin=None):
+    """``M[c, mu, nu] = <mu| (x - Ox)^ex (y - Oy)^ey (z - Oz)^ez |nu>`` [3 or 9, nao, nao] (``MOMENT_COMPONENTS``) over
+    the functions of ``integrals_from_table``, on the host: the twin of ``gto.moment_integrals_batch``.  Per dimension
+    ``sum_t E_t M^e_t`` with ``M^0 = (s)``, ``M^1 = (X s, s)``, ``M^2 = ((X^2 + 1/2p) s, 2 X s, 2 s)``, ``s = sqrt(pi /
+    p)``, ``X = P - O``.  ``origin`` [3] in Bohr (default 0)."""
+    if order not in (1, 2):
+        raise ValueError(f"order = {order!r} (1 or 2)")
+    O = np.zeros(3) if origin is None else np.asarray(origin, dtype=float).reshape(3)
+    shells = shells_from_table(table, np.asarray(coords_bohr, dtype=float))
+    comps = MOMENT_COMPONENTS[:3 if order == 1 else 9]
+    M = np.zeros((len(comps), len(shells), len(shells)))
+    for ia, A in enumerate(shells):
+        for ib in range(ia + 1):
+            B = shells[ib]
+            a, b = A.exps[:, None], B.exps[None, :]
+            p, Q = a + b, A.center - B.center
+            m = []
+            for d in range(3):
+                X = (a * A.center[d] + b * B.center[d]) / p - O[d]
+                e0, e1, e2 = (_E(A.lmn[d], B.lmn[d], t, Q[d], a, b) for t in range(3))
+                m.append([e0, X * e0 + e1, (X * X + 0.5 / p) * e0 + 2 * X * e1 + 2 * e2])
+            cc = A.coefs[:, None] * B.coefs[None, :] * (np.pi / p) ** 1.5
+            for c, (ex, ey, ez) in enumerate(comps):
+                M[c, ia, ib] = M[c, ib, ia] = np.sum(cc * m[0][ex] * m[1][ey] * m[2][ez])
+    U = basis_transform(table, d_functions)
+    M = U @ M @ U.T
+    return 0.5 * (M + M.transpose(0, 2, 1))          # (the products round the two halves differently)
+
+
 def sto3g_basis(symbols, coords_bohr):
     shells = []
     for sym, R in zip(symbols, coords_bohr):

@@ -23,6 +23,7 @@ F64 = torch.float64
 MAX_L = 2                      # OOVQE_GTO_MAX_L
 MAX_PRIM = 10                  # OOVQE_GTO_MAX_PRIM
 CARTESIAN = 0x100              # OOVQE_GTO_CARTESIAN: flag of the l field of a d shell of 6 Cartesian functions
+MAX_MOMENT = 2                 # OOVQE_GTO_MAX_MOMENT
 INVSQRT_MAX_N = 64             # OOVQE_INVSQRT_MAX_N
 INVSQRT_MIN_EIG = 1e-8         # OOVQE_INVSQRT_MIN_EIG
 
@@ -206,6 +207,75 @@ def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=Non
         basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
         dptr(t.charges), G, dptr(coords_bohr), N, dptr(overlap), dptr(int1e_ao), dptr(int2e_ao), dptr(nuc),
         dptr(work), stream_ptr()), "oovqe_gto_integrals_batch")
+
+
+def moment_components(order):
+    """Number of components of the moment integrals: 3 (x, y, z) for order 1, 9 (then xx, xy, xz, yy, yz, zz) for 2."""
+    if order not in (1, MAX_MOMENT):
+        raise ValueError(f"order = {order!r}: moment integrals are implemented for order 1 (dipole) and "
+                         f"{MAX_MOMENT} (dipole and second moments)")
+    return 3 if order == 1 else 9
+
+
+def origin_to_device(origin, G, device, scale=1.0):
+    """``origin`` ([3] or [G, 3], host or device; None: the origin of the coordinates) -> [G, 3] device tensor times
+    ``scale``, or None."""
+    if origin is None:
+        return None
+    o = origin.detach().to(F64) if isinstance(origin, torch.Tensor) else torch.as_tensor(
+        np.asarray(origin, dtype=np.float64))
+    if tuple(o.shape) == (3,):
+        o = o.expand(G, 3)
+    if tuple(o.shape) != (G, 3):
+        raise ValueError(f"origin of shape {tuple(o.shape)}, expected [3] or [{G}, 3]")
+    return (o.to(device) * scale).contiguous()
+
+
+def moment_integrals_into(basis, coords_bohr, moments, order=1, origin_bohr=None):
+    """``moment_integrals_batch`` for geometries that are already a [G, natm, 3] device tensor in Bohr, written into
+    the contiguous device tensor ``moments`` [G, 3 or 9, N, N] on the current stream.  ``origin_bohr``: [G, 3] device
+    tensor in Bohr, or None."""
+    lib = _lib.load()
+    ncomp = moment_components(order)
+    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
+            basis.natm, 3):
+        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
+                         f"[G, {basis.natm}, 3]")
+    G, N = int(coords_bohr.shape[0]), basis.nao
+    if tuple(moments.shape) != (G, ncomp, N, N):
+        raise ValueError(f"moments has shape {tuple(moments.shape)}, expected {(G, ncomp, N, N)}")
+    if origin_bohr is not None and tuple(origin_bohr.shape) != (G, 3):
+        raise ValueError(f"origin of shape {tuple(origin_bohr.shape)}, expected [{G}, 3]")
+    dev = coords_bohr.device
+    t = basis.device_tables(dev)
+    work = basis.work(dev, G)
+    check(lib.oovqe_gto_moments_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(coords_bohr), N, int(order), dptr(origin_bohr), dptr(moments), dptr(work),
+        stream_ptr()), "oovqe_gto_moments_batch")
+    return moments
+
+
+def moment_integrals_batch(basis, coords, order=1, origin=None):
+    """Dipole (and second-moment) integrals of G geometries on the device (``oovqe_gto_moments_batch``,
+    csrc/gto_moments.hip): ``M[g, c, mu, nu] = <mu| (x - Ox)^ex (y - Oy)^ey (z - Oz)^ez |nu>`` over the functions of
+    ``integrals_batch``, in atomic units.
+
+    Args:
+        basis: GTOBasis (s, p and d shells, both d forms)
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        order: 1 -> 3 components x, y, z; 2 -> 9 components x, y, z, xx, xy, xz, yy, yz, zz (the first three are those
+            of order 1 bit for bit)
+        origin: [3] or [G, 3] in Angstrom (default: the origin of the coordinates)
+
+    Returns [G, 3 or 9, N, N] on the device; every matrix is exactly symmetric and a geometry has the same bits whatever
+    stack it is part of."""
+    ncomp = moment_components(order)
+    device = _lib.require_device()
+    xyz = coords_to_device(basis, coords, device)
+    G = int(xyz.shape[0])
+    out = torch.empty((G, ncomp, basis.nao, basis.nao), dtype=F64, device=device)
+    return moment_integrals_into(basis, xyz, out, order, origin_to_device(origin, G, device, 1.0 / BOHR))
 
 
 def refuse_d_gradient(basis):

@@ -1,0 +1,102 @@
+"""Multipole moments of the wave functions of a geometry stack on the device (auto_oo_amd/csrc/gto_moments.hip).
+
+In atomic units, with the AO one-particle density ``D1`` of a state (``nucgrad.cas_ao_densities``), the moment
+integrals ``M^c`` of ``gto.moment_integrals_batch`` and an origin ``O``
+
+    mu_c = sum_A Z_A (R_A - O)^c - tr(D1 M^c),        c = x, y, z | xx, xy, xz, yy, yz, zz
+
+(electrons count negative).  The dipole of a neutral molecule does not depend on ``O``; second moments do.  A
+transition moment between two states is ``-tr(D^IJ M^c)`` with the symmetrised transition density and no nuclear term.
+The contraction (``oovqe_gto_moments_expect_batch``) adds in a fixed order: a geometry's moments have the same bits
+whatever stack, position, stream or chunk they are computed in.
+"""
+import torch
+
+from . import _lib, gto
+from ._lib import check, dptr, stream_ptr
+
+F64 = torch.float64
+DEBYE = 2.541746473            # Debye per atomic unit of dipole moment (e a0)
+# places of xx, xy, xz, yy, yz, zz among the 9 components of order 2, as a symmetric 3 x 3 matrix
+_SECOND = ((3, 4, 5), (4, 6, 7), (5, 7, 8))
+
+
+def moments_expectation(moments, dens, charges=None, coords_bohr=None, origin_bohr=None, nuclear=True):
+    """``out[g, k, c] = -tr(dens[g, k] moments[g, c]) + (nuclear[k]) sum_A Z_A (R_A - O)^c`` on the device.
+
+    Args:
+        moments: [G, 3 or 9, N, N] from ``gto.moment_integrals_into``
+        dens: [G, nd, N, N] device tensor
+        charges, coords_bohr: [natm], [G, natm, 3] device tensors (needed where ``nuclear`` is set)
+        origin_bohr: the [G, 3] device tensor the integrals were made with, or None
+        nuclear: bool, or one bool per density (a transition density takes no nuclear term)
+    """
+    lib = _lib.load()
+    G, ncomp, N = int(moments.shape[0]), int(moments.shape[1]), int(moments.shape[-1])
+    if dens.dim() != 4 or int(dens.shape[0]) != G or tuple(dens.shape[2:]) != (N, N):
+        raise ValueError(f"dens has shape {tuple(dens.shape)}, expected [{G}, nd, {N}, {N}]")
+    nd = int(dens.shape[1])
+    flags = [bool(f) for f in nuclear] if hasattr(nuclear, "__len__") else [bool(nuclear)] * nd
+    if len(flags) != nd:
+        raise ValueError(f"nuclear holds {len(flags)} flags for {nd} densities")
+    with_nuc = None
+    natm = 1
+    if any(flags):
+        if charges is None or coords_bohr is None:
+            raise ValueError("the nuclear term needs charges and coordinates")
+        natm = int(coords_bohr.shape[1])
+        with_nuc = torch.as_tensor(flags, dtype=torch.int32).to(moments.device)
+    dens = dens.to(F64).contiguous()
+    out = torch.empty((G, nd, ncomp), dtype=F64, device=moments.device)
+    check(lib.oovqe_gto_moments_expect_batch(
+        dptr(moments), ncomp, N, G, dptr(dens), nd, natm, dptr(charges), dptr(coords_bohr), dptr(origin_bohr),
+        dptr(with_nuc, torch.int32), dptr(out), stream_ptr()), "oovqe_gto_moments_expect_batch")
+    return out
+
+
+def multipole_moments(basis, coords_bohr, dens, order=1, origin=None, nuclear=True):
+    """Multipole moments of densities ``dens`` at the geometries ``coords_bohr``, in atomic units.
+
+    Args:
+        basis: gto.GTOBasis
+        coords_bohr: [G, natm, 3] device tensor in Bohr
+        dens: AO one-particle densities, [G, N, N] or [G, nd, N, N] device tensor (``D1`` of
+            ``nucgrad.cas_ao_densities``; taken as symmetric)
+        order: 1 -> the components x, y, z; 2 -> x, y, z, xx, xy, xz, yy, yz, zz
+        origin: [3] or [G, 3] in Bohr (default: the origin of the coordinates)
+        nuclear: add ``sum_A Z_A (R_A - O)^c``; one flag for all densities or one per density
+
+    Returns [G, 3 or 9] for ``dens`` [G, N, N], otherwise [G, nd, 3 or 9], on the device.  ``split_moments`` turns
+    the 9 components into the dipole and the 3 x 3 matrix of second moments."""
+    ncomp = gto.moment_components(order)
+    if not isinstance(coords_bohr, torch.Tensor) or not coords_bohr.is_cuda:
+        raise ValueError("coords_bohr must be a [G, natm, 3] device tensor in Bohr")
+    xyz = coords_bohr.to(F64).contiguous()
+    G, N, dev = int(xyz.shape[0]), basis.nao, xyz.device
+    single = dens.dim() == 3
+    d = dens[:, None] if single else dens
+    o = gto.origin_to_device(origin, G, dev)
+    M = torch.empty((G, ncomp, N, N), dtype=F64, device=dev)
+    gto.moment_integrals_into(basis, xyz, M, order, o)
+    out = moments_expectation(M, d, basis.device_tables(dev).charges, xyz, o, nuclear)
+    return out[:, 0] if single else out
+
+
+def split_moments(values):
+    """[..., 9] (order 2) -> (dipole [..., 3], second moments [..., 3, 3], symmetric)."""
+    idx = torch.as_tensor(_SECOND, device=values.device)
+    return values[..., :3], values[..., idx]
+
+
+def traceless_quadrupole(second):
+    """Traceless quadrupole ``Theta_ij = (3 Q_ij - delta_ij tr Q) / 2`` from second moments ``Q`` [..., 3, 3] (torch
+    tensor or numpy array; the convention of Buckingham: ``Theta_zz = sum q (3 z^2 - r^2) / 2``)."""
+    if isinstance(second, torch.Tensor):
+        eye = torch.eye(3, dtype=second.dtype, device=second.device)
+        trace = second.diagonal(dim1=-2, dim2=-1).sum(-1)
+    else:
+        import numpy as np
+        second = np.asarray(second)
+        eye = np.eye(3)
+        trace = np.trace(second, axis1=-2, axis2=-1)
+    return 1.5 * second - 0.5 * trace[..., None, None] * eye

@@ -693,6 +693,29 @@ int oovqe_sym_invsqrt_batch(const double* s, int n, int batch, double* x, int* i
  * device function of the integral kernels. */
 int oovqe_boys(int nmax, const double* t, int64_t count, double* f, oovqe_stream_t stream);
 
+/* ---- dipole and second-moment integrals of a stack of geometries (gto_moments.hip).  Basis tables, limits, return
+ * codes, AO order and normalisation are those of oovqe_gto_integrals_batch (s, p and d shells, both d forms; coords in
+ * Bohr; work of oovqe_gto_work_size doubles).
+ *   moments[b][c][mu][nu] = <mu| (x - Ox)^ex (y - Oy)^ey (z - Oz)^ez |nu>
+ * order = 1: 3 components x, y, z; order = 2: 9 components x, y, z, xx, xy, xz, yy, yz, zz (the first three are those
+ * of order 1, bit for bit).  An order outside 1 .. OOVQE_GTO_MAX_MOMENT is refused before anything is launched.
+ * origin [batch][3] in Bohr (device), or null for the origin of the coordinates.  Every matrix is exactly symmetric
+ * (each unique element computed once and stored to both places); a geometry has the same bits in any stack. */
+#define OOVQE_GTO_MAX_MOMENT 2
+int oovqe_gto_moments_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                            const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                            int nao, int order, const double* origin, double* moments, double* work,
+                            oovqe_stream_t stream);
+/* Multipole moments from those integrals, in atomic units (electrons count negative):
+ *   out[b][k][c] = -sum_pq dens[b][k][p][q] moments[b][c][p][q] + (with_nuc[k] != 0) sum_A Z_A (R_A - O)^c
+ * moments [batch][ncomp][nao][nao] (ncomp = 3 or 9), dens [batch][nd][nao][nao], with_nuc [nd] int32 on the device or
+ * null for no nuclear term (then charges and coords may be null), origin as above (the one the integrals were made
+ * with), out [batch][nd][ncomp].  One workgroup per (geometry, density) adds in a fixed order, the nuclei in the
+ * order of the atoms: the same bits in any stack.  batch <= 65535. */
+int oovqe_gto_moments_expect_batch(const double* moments, int ncomp, int nao, int batch, const double* dens, int nd,
+                                   int natm, const double* charges, const double* coords, const double* origin,
+                                   const int32_t* with_nuc, double* out, oovqe_stream_t stream);
+
 /* ---- nuclear gradients of a stack of geometries (gto_grad.hip): the derivatives of the integrals above with respect to
  * the nuclear coordinates, contracted on the fly with densities (no derivative integral is stored).  Basis tables,
  * limits and conventions are those of oovqe_gto_integrals_batch (coords in Bohr) except that s and p shells only are

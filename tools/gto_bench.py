@@ -13,7 +13,12 @@ bench.py.
 functions, two 8-primitive s shells per heavy atom; the exponents are even-tempered stand-ins, not a published basis.
 For these two the stack is the equilibrium geometry with small random displacements, the starting orbitals are the
 device RHF orbitals of the stack, and the host route is not timed (the host code takes seconds to minutes per
-geometry with d shells).  ``--sizes`` chooses the stack sizes."""
+geometry with d shells).  ``--sizes`` chooses the stack sizes.
+
+``--moments``: instead of the above, one line per stack size of the STO-3G ring with the medians of the dipole and
+second-moment integrals (``gto.moment_integrals_batch``, order 2), of ``OO_pqc_batch.dipole_moment`` (circuit RDMs, AO
+density, order-1 integrals, contraction) and ``rhf_dipole_moment`` from a given RHF result, next to the integral build
+``oovqe_gto_integrals_batch`` of the same stack (``gto.integrals_into``, without S^-1/2), the yardstick."""
 import argparse
 import json
 import os
@@ -86,6 +91,29 @@ def time_polarised(args):
                           "set_geometries_us_per_geometry": t_set[0] / G}), flush=True)
 
 
+def time_moments(args):
+    basis = gto.GTOBasis(["N", "C", "H", "H", "H"])
+    pqc = aoo.Parameterized_circuit(2, 2, None, ansatz="np_fabric", n_layers=1)
+    for G in args.sizes:
+        xyz = torch.as_tensor(basis.coordinates(ring(G))).cuda()
+        batch = aoo.OO_pqc_batch.from_geometries(pqc, basis, xyz, 2, 2, oao_mo_coeffs="rhf")
+        N = basis.nao
+        S, h = torch.empty((G, N, N), dtype=torch.float64).cuda(), torch.empty((G, N, N), dtype=torch.float64).cuda()
+        g, nuc = torch.empty((G, N, N, N, N), dtype=torch.float64).cuda(), torch.empty(G, dtype=torch.float64).cuda()
+        thetas = torch.zeros((G, batch.n_theta), dtype=torch.float64).cuda()
+        rhf = batch.rhf()
+        t_int = event_time(lambda: gto.integrals_into(basis, batch.coords_bohr, S, h, g, nuc), args.reps, args.warm)
+        t_mom = event_time(lambda: gto.moment_integrals_batch(basis, xyz, order=2), args.reps, args.warm)
+        t_one = event_time(lambda: gto.moment_integrals_batch(basis, xyz, order=1), args.reps, args.warm)
+        t_dip = event_time(lambda: batch.dipole_moment(thetas), args.reps, args.warm)
+        t_rhf = event_time(lambda: batch.rhf_dipole_moment(rhf), args.reps, args.warm)
+        print(json.dumps({"moments": True, "G": G, "nao": N, "gto_integrals_batch_us": t_int[0],
+                          "gto_integrals_batch_min_us": t_int[1], "moment_integrals_order2_us": t_mom[0],
+                          "moment_integrals_order2_min_us": t_mom[1], "moment_integrals_order1_us": t_one[0],
+                          "dipole_moment_us": t_dip[0], "dipole_moment_min_us": t_dip[1],
+                          "rhf_dipole_moment_us": t_rhf[0]}), flush=True)
+
+
 def event_time(fn, reps, warm):
     for _ in range(warm):
         fn()
@@ -109,7 +137,11 @@ def main():
     ap.add_argument("--profile", type=int, default=0, metavar="G")
     ap.add_argument("--basis", choices=("sto-3g", "water-pd", "polarised-43"), default="sto-3g")
     ap.add_argument("--sizes", type=int, nargs="+", default=None, metavar="G")
+    ap.add_argument("--moments", action="store_true", help="time the moment integrals and dipole moments instead")
     args = ap.parse_args()
+    if args.moments:
+        args.sizes = args.sizes or [64]
+        return time_moments(args)
     if args.basis != "sto-3g":
         args.sizes = args.sizes or [1, 64, 256]
         return time_polarised(args)
