@@ -225,6 +225,11 @@ SIGNATURES = {
     "oovqe_gto_gradient_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
                                                 ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int]
                                  + [c_double_p] * 3 + [ctypes.c_int] + [c_double_p] * 2 + [c_stream]),
+    "oovqe_gto_gradient_sets_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
+    "oovqe_gto_gradient_sets_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                                     ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                     ctypes.c_int] + [c_double_p] * 3 + [ctypes.c_uint]
+                                      + [c_double_p] * 2 + [c_stream]),
     "oovqe_gto_moments_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
                                                ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                                ctypes.c_int] + [c_double_p] * 3 + [c_stream]),

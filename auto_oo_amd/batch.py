@@ -16,6 +16,7 @@ geometry by geometry.
 """
 import ctypes
 import time
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -28,6 +29,8 @@ from .moldata import Moldata
 from .oo_energy import mo_ao_to_mo_oao, non_redundant_indices
 
 F64 = torch.float64
+
+CASCIGradients = namedtuple("CASCIGradients", "energies ci gradients")
 
 
 class OO_pqc_batch:
@@ -274,6 +277,88 @@ class OO_pqc_batch:
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
             out[k:k + step] = GTO.gradient_into(self.basis, self.coords_bohr[sel], d1, wq, d2, True)
         return out
+
+    def casci_nuclear_gradients(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200):
+        """CASCI states of every geometry at its current orbitals (``casci``) with their state and interstate nuclear
+        gradients -> ``CASCIGradients(energies [G', R], ci [G', R, Dc], gradients [G', R, R, natm, 3])`` on the device,
+        Hartree / Bohr (G' = the rows asked for, R = ``nroots``).
+
+        ``gradients[g, I, I]`` is dE_I/dR at fixed ``oao_mo_coeff`` -- exact, because the c_I are eigenvectors of the
+        CAS Hamiltonian (Hellmann-Feynman for the CI coefficients; the dependence of ``S^-1/2`` on the geometry is
+        pulled back to the overlap as in ``nuclear_gradient``).  ``gradients[g, I, J]``, I != J, is the interstate
+        coupling ``h_IJ = c_I^T (dH/dR) c_J`` with both CI vectors held fixed, the pull-back through ``S^-1/2``
+        included; it is symmetric in (I, J) exactly (one set is computed and stored to both places).  All R (R + 1) / 2
+        elements come from ONE pass over the derivative integrals (``gto.gradient_sets_into``): the transition
+        densities and Fock matrices are half-differences of those of ``(c_I +- c_J) / sqrt 2``, from which the
+        core-only parts and the nuclear term drop out exactly.  ``nucgrad.branching_plane`` picks ``(G_jj - G_ii) / 2``
+        and ``G_ij``, the two vectors that span the branching plane of a conical intersection.
+
+        - The SIGN of an off-diagonal element is that of the product of the two CI vectors' signs as ``casci`` fixes
+          them (largest |component| positive), as for the transition dipoles of ``casci_dipole_matrix``.
+        - Within a degenerate pair of roots only the 2 x 2 block is defined (up to a rotation of the pair), not its
+          split into elements.
+        - ``G_IJ / (E_J - E_I)`` is the CI part of the derivative coupling only: the orbital-connection term
+          ``<p|dq/dR>`` is not built.
+
+        Args:
+            nroots, fix_singlet, tol, max_iter: as for ``casci`` (which raises when a solve does not converge)
+            index: rows of the batch (default all); the result then has one entry per row asked for
+            chunk: geometries per pass of the contraction (default all at once): the AO two-particle densities are kept
+                for ``chunk`` geometries only, ``chunk (R (R + 1) / 2 + 2) N^4`` doubles
+
+        The same bits whatever ``index`` and ``chunk``.  Works for any batch whatever its circuit (only orbitals and
+        integrals are used).  Needs a batch made by ``from_geometries`` (RuntimeError otherwise); d shells and
+        ``ncas > nucgrad.MAX_NCAS`` raise NotImplementedError, a CI problem out of scope ValueError
+        (``ci.check_scope``)."""
+        from . import ci
+        rows = self._gradient_rows(index, "casci_nuclear_gradients")
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"casci_nuclear_gradients covers ncas <= {nucgrad.MAX_NCAS}")
+        ci.check_scope(self.ncas, self.nelecas, nroots)
+        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        G, R, a, N, natm = self.G, int(nroots), self.ncas, self.nao, self.basis.natm
+        pairs = nucgrad.state_pairs(R)
+        P = len(pairs)
+        n, K = R + 2 * P, R + P
+        # RDMs and generalised Fock matrices of the R states and the 2 P polarisation vectors, whole stack
+        stack = nucgrad.polarisation_vectors(vecs)
+        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
+        gamma = gamma.reshape(G, n, a, a)
+        Gamma = Gamma.reshape((G, n) + (a,) * 4)
+        fock = torch.empty((G, n, N, N), dtype=F64, device=self.device)
+        for s in range(n):      # (the CAS path takes the RDMs of set 0 for the Fock matrix: one call per vector)
+            fock[:, s] = self._cas_batch(gamma[:, s:s + 1], Gamma[:, s:s + 1], G, want_fock=True)[2]
+        fock = nucgrad.transition_sets(fock, R)
+        step = len(rows) if chunk is None else max(1, int(chunk))
+        out = torch.empty((len(rows), R, R, natm, 3), dtype=F64, device=self.device)
+        k = torch.arange(R, device=self.device)
+        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
+        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
+        for k0 in range(0, len(rows), step):
+            sel = torch.as_tensor(rows[k0:k0 + step], device=self.device)
+            c = len(sel)
+            C = self.mo_coeff[sel]
+            d1 = nucgrad.transition_sets(
+                nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel], Gamma[sel], want_d2=False)[0], R)
+            buf = self._dm2_buffer(c * (K + 2))
+            d2 = buf[:c * K].view((c, K) + (N,) * 4)
+            tmp = buf[c * K:c * (K + 2)]
+            for s in range(R):
+                t = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel, s], Gamma[sel, s], out=tmp)[1]
+                d2[:, s].copy_(t)
+            for p in range(P):      # the pair's + and - densities side by side, their half-difference in place
+                pm = [R + p, R + P + p]
+                t = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel][:, pm], Gamma[sel][:, pm], out=tmp)[1]
+                d2[:, R + p].copy_(t[:, 0].sub_(t[:, 1]).mul_(0.5))
+            wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
+            val = GTO.gradient_sets_into(self.basis, self.coords_bohr[sel], d1, wq, d2, [True] * R + [False] * P)
+            blk = out[k0:k0 + c]
+            blk[:, k, k] = val[:, :R]
+            if P:
+                blk[:, ii, jj] = val[:, R:]
+                blk[:, jj, ii] = val[:, R:]
+        sel = torch.as_tensor(rows, device=self.device)
+        return CASCIGradients(e[sel], vecs[sel], out)
 
     def rhf_nuclear_gradient(self, result=None, index=None):
         """Closed-shell Hartree-Fock gradient -> [G, natm, 3] (device, Hartree / Bohr) from a converged

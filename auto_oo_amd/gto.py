@@ -24,6 +24,8 @@ MAX_L = 2                      # OOVQE_GTO_MAX_L
 MAX_PRIM = 10                  # OOVQE_GTO_MAX_PRIM
 CARTESIAN = 0x100              # OOVQE_GTO_CARTESIAN: flag of the l field of a d shell of 6 Cartesian functions
 MAX_MOMENT = 2                 # OOVQE_GTO_MAX_MOMENT
+MAX_GRAD_SETS = 10             # OOVQE_GTO_GRAD_MAX_SETS
+GRAD_SETS_TILE = 5             # OOVQE_GTO_GRAD_SETS_TILE
 INVSQRT_MAX_N = 64             # OOVQE_INVSQRT_MAX_N
 INVSQRT_MIN_EIG = 1e-8         # OOVQE_INVSQRT_MIN_EIG
 
@@ -178,13 +180,21 @@ class GTOBasis:
             buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
         return buf
 
-    def gradient_work(self, device, G):
-        """Work buffer of ``oovqe_gto_gradient_batch`` for G geometries, one per (device, stream) like ``work``."""
+    def gradient_work(self, device, G, nset=1):
+        """Work buffer of ``oovqe_gto_gradient_batch`` for G geometries (``nset`` > 1: of
+        ``oovqe_gto_gradient_sets_batch`` for that many density sets per geometry), one per (device, stream) like
+        ``work``."""
         key = ("gradient", str(device), torch.cuda.current_stream().cuda_stream)
         buf = self._work.get(key)
-        size = int(_lib.load().oovqe_gto_gradient_work_size(self.nshell, self.max_nprim, self.natm, G))
+        lib = _lib.load()
+        if nset > 1:
+            what = "oovqe_gto_gradient_sets_work_size"
+            size = int(lib.oovqe_gto_gradient_sets_work_size(self.nshell, self.max_nprim, self.natm, G, int(nset)))
+        else:
+            what = "oovqe_gto_gradient_work_size"
+            size = int(lib.oovqe_gto_gradient_work_size(self.nshell, self.max_nprim, self.natm, G))
         if size < 0:
-            check(size, "oovqe_gto_gradient_work_size")
+            check(size, what)
         if buf is None or buf.numel() < size:
             buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
         return buf
@@ -339,6 +349,73 @@ def gradient_batch(basis, coords, dm1=None, wq=None, dm2=None, nuc=True):
     refuse_d_gradient(basis)
     device = _lib.require_device()
     return gradient_into(basis, coords_to_device(basis, coords, device), dm1, wq, dm2, nuc)
+
+
+def gradient_sets_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True, work=None):
+    """``gradient_sets_batch`` for geometries that are already a [G, natm, 3] device tensor in Bohr, on the current
+    stream.  ``work``: a buffer of ``oovqe_gto_gradient_sets_work_size`` doubles to use instead of the basis' own."""
+    refuse_d_gradient(basis)
+    lib = _lib.load()
+    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
+            basis.natm, 3):
+        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
+                         f"[G, {basis.natm}, 3]")
+    G, N = int(coords_bohr.shape[0]), basis.nao
+    given = [(name, x) for name, x in (("dm1", dm1), ("wq", wq), ("dm2", dm2)) if x is not None]
+    if not given:
+        raise ValueError("gradient_sets_into takes the number of sets from dm1, wq or dm2: give at least one")
+    for name, x in given:
+        if not isinstance(x, torch.Tensor) or x.dim() < 2:
+            raise ValueError(f"{name} has shape {tuple(getattr(x, 'shape', ()))}, expected [G, K, ...]")
+    K = int(given[0][1].shape[1])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} density sets per geometry (1 .. {MAX_GRAD_SETS})")
+    dev = coords_bohr.device
+    t = basis.device_tables(dev)
+    ins = []
+    for name, x, shape in (("dm1", dm1, (G, K, N, N)), ("wq", wq, (G, K, N, N)), ("dm2", dm2, (G, K, N, N, N, N))):
+        if x is not None:
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {shape}")
+            x = x.to(device=dev, dtype=F64).contiguous()
+        ins.append(x)
+    if isinstance(nuc, (bool, np.bool_)):
+        bits = [bool(nuc)] * K
+    else:
+        bits = [bool(b) for b in nuc]
+        if len(bits) != K:
+            raise ValueError(f"nuc holds {len(bits)} flags for {K} sets")
+    mask = sum(1 << k for k, b in enumerate(bits) if b)
+    grad = torch.empty((G, K, basis.natm, 3), dtype=F64, device=dev)
+    if G == 0:
+        return grad
+    if work is None:
+        work = basis.gradient_work(dev, G, K)
+    xyz = coords_bohr.to(F64).contiguous()
+    check(lib.oovqe_gto_gradient_sets_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(xyz), N, K, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), ctypes.c_uint(mask), dptr(grad),
+        dptr(work), stream_ptr()), "oovqe_gto_gradient_sets_batch")
+    return grad
+
+
+def gradient_sets_batch(basis, coords, dm1=None, wq=None, dm2=None, nuc=True):
+    """``gradient_batch`` for K density sets per geometry in ONE pass over the derivative integrals
+    (``oovqe_gto_gradient_sets_batch``, csrc/gto_grad_sets.hip): the integrals of a primitive quartet are evaluated
+    once and weighted with every set -- the state and interstate gradients of several CASCI roots.
+
+    Args:
+        basis: GTOBasis (s and p shells)
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        dm1, wq: [G, K, N, N], dm2: [G, K, N, N, N, N], symmetric as for ``gradient_batch`` (None skips a term for all
+            sets); K (1 .. ``MAX_GRAD_SETS``) is taken from the tensors
+        nuc: add the derivative of the nuclear repulsion: a bool, or one bool per set
+
+    Returns [G, K, natm, 3] on the device, in Hartree / Bohr.  A set's gradient has the same bits whatever the stack,
+    the other sets of the call, their number and its place among them."""
+    refuse_d_gradient(basis)
+    device = _lib.require_device()
+    return gradient_sets_into(basis, coords_to_device(basis, coords, device), dm1, wq, dm2, nuc)
 
 
 def sym_invsqrt_batch(S, out=None):

@@ -31,6 +31,17 @@ def cas_ao_densities(mo_coeff, n_core, ncas, one_rdm=None, two_rdm=None, want_d2
     g + nuc``) from orbitals ``mo_coeff`` [G, N, N] (AO x MO: ``n_core`` doubly occupied, then ``ncas`` active) and the
     active RDMs [G, a, a], [G, a, a, a, a] in the convention of the batch (``oovqe_cas_ao_densities_batch``).
     ``ncas = 0``: closed shell.  ``out``: a [>= G, N, N, N, N] tensor to take ``D2``.  -> (D1, D2 or None)."""
+    if ncas > 0 and one_rdm is not None and two_rdm is not None and one_rdm.dim() == 4:
+        # K sets of RDMs per geometry [G, K, a, a], [G, K, a, a, a, a] -> D1 [G, K, N, N], D2 [G, K, N, N, N, N]: the
+        # orbitals repeated per set, every (geometry, set) an entry of the batch
+        G, K, N = int(one_rdm.shape[0]), int(one_rdm.shape[1]), int(mo_coeff.shape[-1])
+        if tuple(mo_coeff.shape) != (G, N, N) or two_rdm.dim() != 6 or tuple(two_rdm.shape[:2]) != (G, K):
+            raise ValueError(f"mo_coeff of shape {tuple(mo_coeff.shape)}, RDM sets of shapes {tuple(one_rdm.shape)}, "
+                             f"{tuple(two_rdm.shape)}: expected [G, N, N], [G, K, a, a], [G, K, a, a, a, a]")
+        C = mo_coeff[:, None].expand(G, K, N, N).reshape(G * K, N, N)
+        d1, d2 = cas_ao_densities(C, n_core, ncas, one_rdm.reshape((G * K,) + tuple(one_rdm.shape[2:])),
+                                  two_rdm.reshape((G * K,) + tuple(two_rdm.shape[2:])), want_d2, out)
+        return d1.reshape(G, K, N, N), None if d2 is None else d2.reshape(G, K, N, N, N, N)
     lib = _lib.load()
     _lib.require_device()
     C = mo_coeff.contiguous()
@@ -62,6 +73,11 @@ def overlap_pullback(overlap, oao_mo_coeff, fock):
     ``S = V diag(s) V^T``, ``WQ = V [K o (V^T G_X V)] V^T``, ``K_ij = -1 / (sqrt(s_i) sqrt(s_j) (sqrt(s_i) +
     sqrt(s_j)))`` (the divided differences of ``s^-1/2``).  N x N work per geometry on the device: the eigensolver of
     the SCF kernels and the batched small products; no matrix passes through the host."""
+    if fock.dim() == 4:
+        # K Fock matrices per geometry [G, K, N, N] -> WQ [G, K, N, N]: overlap and U repeated per set (WQ is linear in F)
+        G, K, N = int(fock.shape[0]), int(fock.shape[1]), int(fock.shape[-1])
+        rep = lambda x: x[:, None].expand(G, K, N, N).reshape(G * K, N, N)
+        return overlap_pullback(rep(overlap), rep(oao_mo_coeff), fock.reshape(G * K, N, N)).reshape(G, K, N, N)
     w, V, _ = scf.sym_eigh_batch(overlap.contiguous())
     mm = ops.matmul_nn_batch
     sq = torch.sqrt(w)
@@ -93,6 +109,48 @@ def rhf_gradient(basis, coords_bohr, mo_coeff, mo_energy, n_occ):
     d1, d2 = cas_ao_densities(mo_coeff, n_occ, 0)
     wq = energy_weighted_pullback(mo_coeff, mo_energy, n_occ)
     return gto.gradient_into(basis, coords_bohr, d1, wq, d2, True)
+
+
+# ---- several states of one geometry --------------------------------------------------------------------------------
+def state_pairs(nroots):
+    """The pairs (I, J), I > J, of ``nroots`` states in the order of the interstate sets: (1, 0), (2, 0), (2, 1), ...;
+    with the ``nroots`` states in front of them, ``nroots (nroots + 1) / 2`` sets."""
+    return [(i, j) for i in range(int(nroots)) for j in range(i)]
+
+
+def polarisation_vectors(vecs):
+    """CI vectors [G, R, Dc] -> [G, R + 2 P, Dc]: the R vectors, then ``(c_I + c_J) / sqrt 2`` for the P pairs of
+    ``state_pairs``, then ``(c_I - c_J) / sqrt 2``.  RDMs, AO densities and the Fock matrix are quadratic forms of the
+    vector, so half the difference of a ``+`` and a ``-`` quantity is the symmetrised transition quantity ``(<I|.|J> +
+    <J|.|I>) / 2``; whatever does not depend on the vector (the core-only parts, the nuclear term) drops out exactly."""
+    pairs = state_pairs(vecs.shape[1])
+    if not pairs:
+        return vecs
+    ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=vecs.device)
+    jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=vecs.device)
+    r2 = 0.5 ** 0.5
+    return torch.cat((vecs, r2 * (vecs[:, ii] + vecs[:, jj]), r2 * (vecs[:, ii] - vecs[:, jj])), dim=1)
+
+
+def transition_sets(x, nroots):
+    """``x`` [G, R + 2 P, ...] of the vectors of ``polarisation_vectors`` -> [G, R + P, ...]: the R state quantities,
+    then the P half-differences ``(x_+ - x_-) / 2``."""
+    R, P = int(nroots), len(state_pairs(nroots))
+    if P == 0:
+        return x.contiguous()
+    return torch.cat((x[:, :R], 0.5 * (x[:, R:R + P] - x[:, R + P:])), dim=1).contiguous()
+
+
+def branching_plane(result, i, j):
+    """The two vectors that span the branching plane of states i and j from a result of
+    ``OO_pqc_batch.casci_nuclear_gradients`` (anything with ``gradients`` [G, R, R, natm, 3]) -> ``(g, h)``, each
+    [G, natm, 3]: the gradient half-difference ``g = (G_jj - G_ii) / 2`` and the interstate coupling ``h = G_ij``."""
+    grads = result.gradients
+    R = int(grads.shape[1])
+    i, j = int(i), int(j)
+    if not (0 <= i < R and 0 <= j < R) or i == j:
+        raise ValueError(f"states i = {i}, j = {j}: two different states of 0..{R - 1}")
+    return 0.5 * (grads[:, j, j] - grads[:, i, i]), grads[:, i, j]
 
 
 # ---- numpy twins (tests) ----------------------------------------------------------------------------------------------

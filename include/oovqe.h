@@ -735,7 +735,22 @@ int oovqe_gto_gradient_batch(int nshell, const int32_t* shells, int nprim_total,
                              const double* coefs, int natm, const double* charges, int batch, const double* coords,
                              int nao, const double* d1, const double* wq, const double* d2, int with_nuc, double* grad,
                              double* work, oovqe_stream_t stream);
-/* AO densities of a CAS wave function for the call above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
+/* The same contraction for nset density sets per geometry in ONE pass over the derivative integrals
+ * (gto_grad_sets.hip): the Boys function, R_tuv and the Hermite sums of a primitive quartet are evaluated once and
+ * weighted with every set.  d1, wq [batch][nset][nao][nao], d2 [batch][nset][nao]^4 (symmetries as above), grad
+ * [batch][nset][natm][3]; a null d1, wq or d2 skips that term for all sets; bit k of nuc_mask adds dE_nuc/dR to set k.
+ * 1 <= nset <= OOVQE_GTO_GRAD_MAX_SETS (the symmetric matrix of 4 states has 10 elements).  A set's gradient has the
+ * same bits whatever the stack, the other sets of the call, their number and its place among them.  Limits and the
+ * refusal of d shells are those of oovqe_gto_gradient_batch.  work: oovqe_gto_gradient_sets_work_size(...) doubles
+ * (for nset = 1 the size of oovqe_gto_gradient_work_size). */
+#define OOVQE_GTO_GRAD_MAX_SETS 10
+#define OOVQE_GTO_GRAD_SETS_TILE 5   /* sets per pass over the integrals; more sets run ceil(nset / 5) passes */
+int64_t oovqe_gto_gradient_sets_work_size(int nshell, int max_nprim, int natm, int batch, int nset);
+int oovqe_gto_gradient_sets_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                  const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                                  int nao, int nset, const double* d1, const double* wq, const double* d2,
+                                  unsigned nuc_mask, double* grad, double* work, oovqe_stream_t stream);
+/* AO densities of a CAS wave function for the calls above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
  * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
  * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
  *   d1 = Dc + Da, Dc = 2 C_c C_c^T, Da = C_a gamma C_a^T;
