@@ -2846,7 +2846,8 @@ void cas_final_kernel(const double* __restrict__ Fcol, const double* __restrict_
 // Every sum runs in the order of those kernels: the results are those of the three launches, bit
 // for bit.  It replaces sym_gm_kernel + cas_panel_kernel + cas_final_kernel (g_mo: 2 x 64 MB of
 // memory traffic at 256 geometries, three grids of short latency-bound workgroups) by one launch;
-// measured at N = 43, M = 9, 256 geometries: see DESIGN.md section 5.
+// measured at N = 43, M = 9, 256 geometries: see DESIGN.md section 5.  KS is the kernel's own k-depth
+// (tail_depth: 11 steps and 44 rows of T3s for 41 <= N <= 44, else the ks of stage1_variant).
 // ------------------------------------------------------------------------------------------
 constexpr int TAIL_THREADS = 512;
 
@@ -2860,6 +2861,21 @@ __host__ __device__ inline bool tail_needed(int x, int y, int z, int no)
     return x >= no || x == lo;                               // lo core, hi active
 }
 
+// OOVQE_TAIL_PROBE (measurement builds only, tools/tail_probe.py): every workgroup meets at a barrier at each phase
+// boundary and thread 0 stores the 100 MHz wall clock there; oovqe_tail_probe_read copies the readings out
+#ifdef OOVQE_TAIL_PROBE
+constexpr int TAIL_PROBE_WGS = 512, TAIL_PROBE_MARKS = 32;
+__device__ long long g_tail_probe[TAIL_PROBE_WGS][TAIL_PROBE_MARKS];
+#define TAIL_MARK(i)                                                                              \
+    do {                                                                                          \
+        __syncthreads();                                                                          \
+        if (threadIdx.x == 0 && blockIdx.x < TAIL_PROBE_WGS && (i) < TAIL_PROBE_MARKS)            \
+            g_tail_probe[blockIdx.x][i] = wall_clock64();                                         \
+    } while (0)
+#else
+#define TAIL_MARK(i) do {} while (0)
+#endif
+
 template <int KS>
 __global__ __launch_bounds__(TAIL_THREADS, 2)
 void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C, const double* __restrict__ Wpre,
@@ -2872,7 +2888,8 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     extern __shared__ double lds[];
     constexpr int NW = TAIL_THREADS / 64;
     constexpr int PW = (4 * KS + NW - 1) / NW;       // rows p per wave in q -> x
-    constexpr int PB = PW * KS > 48 ? (PW + 1) / 2 : PW;   // of them with their loads in flight together
+    constexpr int GR = 2, NG = (PW + GR - 1) / GR;   // ... in NG groups of GR rows
+    constexpr int NTN = (4 * KS + 15) / 16;          // 16-blocks of n in p -> n
     const int M = no + na, M2 = M * M, M3 = M2 * M;
     const int na2 = na * na, na3 = na2 * na, na4 = na2 * na2;
     const int ncol = M * (M + 1) / 2, nty = (ncol + 15) / 16;
@@ -2911,60 +2928,99 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     const int LDP = M * 16 + 8;
 
     // ---- q -> x, p -> n per tile of (y <= z) (sym_gm_kernel's arithmetic) ------------------------------
-    // J comes in (at most) two halves of the wave's rows per tile, each half's loads all in flight together;
-    // the first tile's first half is in flight under the staging of the inputs below (the workgroup barriers
-    // wait for LDS only)
+    // A wave's rows p = wave + NW i of J come in groups of GR rows through two register sets in rotation: step
+    // s = ty NG + g multiplies set s & 1 and at once reloads it with the rows of step s + 2, so the loads of a later
+    // group are in flight under every product, under the p -> n step of the tile and under the staging of the inputs
+    // below (the workgroup barriers wait for LDS only).  Rows p >= N are neither loaded (their loads go to a buffer of
+    // no bytes: no memory access) nor multiplied; their T3s rows are written as zeros.
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     const __amdgpu_buffer_rsrc_t csrd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<double*>(C), 0, (int)((size_t)N * N * sizeof(double)), 0x00020000);
-    double af[KS];
+    // the C^T operands of p -> n for every 16-block of n: the same for every tile
+    double cfa[NTN][KS];
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int pp = 4 * ks + lq, n = 16 * nt + lr;
+            const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
+                csrd, (pp < N && n < N) ? (unsigned)((pp * N + n) * (int)sizeof(double)) : 0x7fffffffu, 0, 0);
+            cfa[nt][ks] = __builtin_bit_cast(double, v);
+        }
+    // byte offsets in a tile of J [tri][16] of the pair (p, q), q = 4 ks + lq: triangle row base(min) + max with
+    // base(a) = a (2N - a + 1) / 2 - a.  q < p: colq[ks] + 128 p; else base(p) + lin0 + 512 ks (q >= N there meets
+    // af = 0 and reads a later row or, past the end of the tile, the zero of the range check)
+    // (the 12-step build has no registers left for colq and forms it at each load instead)
+    constexpr bool COLQ_REGS = KS < 12;
+    int colq[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        const int q = 4 * ks + lq;
-        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
-            csrd, (q < N && lr < M) ? (unsigned)((q * N + lr) * (int)sizeof(double)) : 0x7fffffffu, 0, 0);
-        af[ks] = __builtin_bit_cast(double, v);
+        const int q = 4 * ks + lq < N ? 4 * ks + lq : N - 1;
+        colq[ks] = ((q * (2 * N - q + 1) / 2 - q) * 16 + lr) * (int)sizeof(double);
     }
-    // rows h0 .. h0 + PB - 1 of the wave, tile ty
-    auto load_half = [&](double (&bf)[PB][KS], int ty, int h0) {
-        const __amdgpu_buffer_rsrc_t jsrd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<double*>(J + (size_t)ty * tri * 16), 0, (int)(tri * 16 * sizeof(double)), 0x00020000);
+    const int lin0 = (lq * 16 + lr) * (int)sizeof(double);
+    // group g of the wave's rows, tile ty
+    auto load_group = [&](double (&bf)[GR][KS], int ty, int g) {
 #pragma unroll
-        for (int i = 0; i < PB; ++i) {
-            const int p = wave + NW * (h0 + i);
-            const int pc = p < N ? p : N - 1;                           // wave-uniform
-            const int basep = pc * (2 * N - pc + 1) / 2 - pc;
+        for (int r = 0; r < GR; ++r) {
+            const int i = g * GR + r;
+            if (i >= PW) continue;
+            // (opaque: the row's offsets are formed here from scalars, not kept in 11 registers per row from tile
+            // to tile)
+            int wv = wave;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+s"(wv));
+#endif
+            const int p = wv + NW * i;                                  // wave-uniform
+            int lqo = lq;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(lqo));
+#endif
+            // a row p >= N or a tile past the last: a buffer of no bytes, every load answers zero without a memory
+            // access (the loads are issued all the same: the count of loads in flight is the same on every path,
+            // which is what lets the compiler wait for the older set alone)
+            const __amdgpu_buffer_rsrc_t jsrd = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<double*>(J + (size_t)(ty < nty ? ty : 0) * tri * 16), 0,
+                p < N && ty < nty ? (int)(tri * 16 * sizeof(double)) : 0, 0x00020000);
+            const int colp = p * 16 * (int)sizeof(double);
+            const int rowp = (p * (2 * N - p + 1) / 2 - p) * 16 * (int)sizeof(double) + lin0;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                // triangle row of the pair (p, q): base(min) + max, base(a) = a (2N - a + 1) / 2 - a
-                const int q = 4 * ks + lq < N ? 4 * ks + lq : N - 1;
-                const int t = q < pc ? q * (2 * N - q + 1) / 2 - q + pc : basep + q;
-                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
-                    jsrd, (unsigned)((t * 16 + lr) * (int)sizeof(double)), 0, 0);
-                bf[i][ks] = __builtin_bit_cast(double, v);
+                const int q = 4 * ks + lqo;
+                const int cq = COLQ_REGS ? colq[ks] : (q * (2 * N - 1 - q) / 2 * 16 + lr) * (int)sizeof(double);
+                const int off = lq < p - 4 * ks ? cq + colp : rowp + ks * 64 * (int)sizeof(double);
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(jsrd, (unsigned)off, 0, 0);
+                bf[r][ks] = __builtin_bit_cast(double, v);
             }
         }
     };
     double* T3s = scr;                               // [4 KS][LDP], rows p >= N are zero
-    auto mfma_half = [&](const double (&bf)[PB][KS], int h0) {
+    auto mfma_group = [&](const double (&af)[KS], const double (&bf)[GR][KS], int g) {
 #pragma unroll
-        for (int i = 0; i < PB; ++i) {
-            if (h0 + i >= PW) continue;
-            const int p = wave + NW * (h0 + i);
+        for (int r = 0; r < GR; ++r) {
+            const int i = g * GR + r;
+            if (i >= PW) continue;
+            int wv = wave;                                              // (opaque, as in load_group)
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+s"(wv));
+#endif
+            const int p = wv + NW * i;
+            if (p >= 4 * KS) continue;
             d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+            if (p < N) {
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(af[ks], bf[i][ks], acc);
-            double* row = T3s + (size_t)(p < 4 * KS ? p : 0) * LDP + lr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x = lq + 4 * j;
-                if (x < M && p < 4 * KS) row[x * 16] = p < N ? acc[j] : 0.0;
+                for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(af[ks], bf[r][ks], acc);
             }
+            double* row = T3s + (p * LDP + lq * 16 + lr);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (lq + 4 * j < M) row[j * 64] = acc[j];
         }
     };
-    static_assert(2 * PB >= PW, "two halves cover the rows of a wave");
-    double bf[PB][KS];
-    load_half(bf, 0, 0);
+    double bs[2][GR][KS];
+    TAIL_MARK(0);
+#pragma unroll
+    for (int s0 = 0; s0 < 2; ++s0) load_group(bs[s0], s0 / NG, s0 % NG);
 
     // ---- inputs; the position table by a ballot prefix over (x, y <= z) in order ------------------
     for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
@@ -2978,6 +3034,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         krow[idx] = kap_row[idx];
         kcol[idx] = kap_col[idx];
     }
+    TAIL_MARK(1);
     {
         const int total = M * ncol;
         int base = 0;
@@ -3009,6 +3066,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             base += all;
         }
     }
+    TAIL_MARK(2);
     // h_mo[n, x] = sum_q W[n, q] C[q, x]
     for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
         const int n = idx / M, x = idx - n * M;
@@ -3017,16 +3075,36 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         hn[idx] = acc;
     }
     __syncthreads();
+    TAIL_MARK(3);
 
     {
         const int ntn = (N + 15) / 16;
-        for (int ty = 0; ty < nty; ++ty) {
-            mfma_half(bf, 0);
-            if (PB < PW) {
-                load_half(bf, ty, PB);
-                mfma_half(bf, PB);
+        // one tile; par = set of its first group (the parity of step ty NG)
+        auto tail_tile = [&](auto par, int ty) {
+            constexpr int P = decltype(par)::value;
+            // the C operand of q -> x from the LDS copy, tile by tile: its registers are free during p -> n
+            double af[KS];
+            int lqv = lq;                                               // (opaque: no address registers kept per k-step)
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(lqv));
+#endif
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int q = 4 * ks + lqv;
+                const double c = Cl[(q < N ? q : N - 1) * M + (lr < M ? lr : 0)];
+                af[ks] = (q < N && lr < M) ? c : 0.0;
+            }
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                mfma_group(af, bs[(P + g) & 1], g);
+                // (the loads stay behind the products that read the registers they fill: one set, not two, is live)
+                __builtin_amdgcn_sched_barrier(0);
+                load_group(bs[(P + g) & 1], ty + (g + 2) / NG, (g + 2) % NG);
+                __builtin_amdgcn_sched_barrier(0);
+                if (g == 0) TAIL_MARK(ty < 3 ? 4 + 3 * ty : 31);
             }
             __syncthreads();
+            TAIL_MARK(ty < 3 ? 5 + 3 * ty : 31);
             const int yz = 16 * ty + lr;
             int off = 0;
             if (yz < ncol) {
@@ -3034,39 +3112,35 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
                 tri_decode(yz, M, y, z);
                 off = y * M + z;
             }
-            int cur_nt = -1;
-            double cf[KS];
-            for (int tile = wave; tile < ntn * M; tile += NW) {
-                const int nt = tile / M, x = tile - nt * M;
-                if (nt != cur_nt) {
-                    const int n = 16 * nt + lr;
+            // 16 x 16 tiles (nt, x) of g_mo[n, x, yz], tile = nt M + x, dealt to the waves in turn
 #pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        const int pp = 4 * ks + lq;
-                        const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
-                            csrd, (pp < N && n < N) ? (unsigned)((pp * N + n) * (int)sizeof(double)) : 0x7fffffffu,
-                            0, 0);
-                        cf[ks] = __builtin_bit_cast(double, v);
-                    }
-                    cur_nt = nt;
-                }
-                double tf[KS];
+            for (int nt = 0; nt < NTN; ++nt) {
+                if (nt >= ntn) continue;
+                const int t0 = nt * M;
+                for (int tile = t0 + (wave - t0 % NW + NW) % NW; tile < t0 + M; tile += NW) {
+                    const int x = tile - t0;
+                    double tf[KS];
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) tf[ks] = T3s[(size_t)(4 * ks + lq) * LDP + x * 16 + lr];
-                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+                    for (int ks = 0; ks < KS; ++ks) tf[ks] = T3s[(size_t)(4 * ks + lq) * LDP + x * 16 + lr];
+                    d4 acc = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(cf[ks], tf[ks], acc);
-                const int ci = yz < ncol ? tab[x * M2 + off] : -1;
-                if (ci >= 0) {
+                    for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(cfa[nt][ks], tf[ks], acc);
+                    const int ci = yz < ncol ? tab[x * M2 + off] : -1;
+                    if (ci >= 0) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int n = 16 * nt + lq + 4 * j;
-                        if (n < N) Gc[(size_t)n * NC + ci] = acc[j];
+                        for (int j = 0; j < 4; ++j) {
+                            const int n = 16 * nt + lq + 4 * j;
+                            if (n < N) Gc[(size_t)n * NC + ci] = acc[j];
+                        }
                     }
                 }
             }
-            if (ty + 1 < nty) load_half(bf, ty + 1, 0);
             __syncthreads();
+            TAIL_MARK(ty < 3 ? 6 + 3 * ty : 31);
+        };
+        for (int ty = 0; ty < nty; ty += 2) {
+            tail_tile(std::integral_constant<int, 0>{}, ty);
+            if (ty + 1 < nty) tail_tile(std::integral_constant<int, NG & 1>{}, ty + 1);
         }
     }
 
@@ -3078,6 +3152,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         for (int i = 0; i < no; ++i) fi += 2.0 * TAIL_G(n, x, i, i) - TAIL_G(n, i, i, x);
         FIn[idx] = fi;
     }
+    TAIL_MARK(13);
     double* Fl = scr;                                // [nrdm][M][N]  Fock columns
     double* El = Fl + (size_t)nrdm * M * N;          // [nrdm][N]     Epart
     double* Ga = El + (size_t)nrdm * N;              // [N][na3]      g_mo[n, no + w, no + x, no + y]
@@ -3095,6 +3170,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         Dc[idx] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
     }
     __syncthreads();
+    TAIL_MARK(14);
     for (int n = tid; n < N; n += TAIL_THREADS) Cp[n] = n < no ? hn[n * M + n] + FIn[n * M + n] : 0.0;
     for (int idx = tid; idx < na * (na + na3); idx += TAIL_THREADS) {
         const int pl = idx / (na + na3), r0 = idx - pl * (na + na3);
@@ -3110,6 +3186,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             c2[(size_t)pl * na3 + i3] = 0.5 * TAIL_G(n, no + q, no + r, no + s);
         }
     }
+    TAIL_MARK(15);
     // Fock columns: one thread per (n, set k, row m), the core rows first (waves without divergent rows)
     const int ncore = N * nrdm * no;
     for (int idx = tid; idx < N * nrdm * M; idx += TAIL_THREADS) {
@@ -3148,6 +3225,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         }
         Fl[((size_t)k * M + m) * N + n] = val;
     }
+    TAIL_MARK(16);
     // E_k contribution of row p = n - no (active n only), serial per (n, set)
     for (int idx = tid; idx < N * nrdm; idx += TAIL_THREADS) {
         const int n = idx / nrdm, k = idx - n * nrdm;
@@ -3167,6 +3245,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     }
 #undef TAIL_G
     __syncthreads();
+    TAIL_MARK(17);
 
     // ---- assembly (cas_final_kernel) ----------------------------------------------------------------
     for (int idx = tid; idx < nrdm * n_kappa; idx += TAIL_THREADS) {
@@ -3190,9 +3269,19 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             dE[k - 1] = acc;
         }
     }
+    TAIL_MARK(18);
 }
 
 }  // namespace
+
+#ifdef OOVQE_TAIL_PROBE
+// the readings of the last tail launch: out[workgroup][mark], n = number of long longs of out
+extern "C" int oovqe_tail_probe_read(long long* out, int n)
+{
+    const size_t bytes = sizeof(long long) * (size_t)(n < TAIL_PROBE_WGS * TAIL_PROBE_MARKS ? n : TAIL_PROBE_WGS * TAIL_PROBE_MARKS);
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_probe), bytes) == hipSuccess ? 0 : 1;
+}
+#endif
 
 // ---- the stage-1 kernel that serves a shape -----------------------------------------------------------------
 // LAUNCH(KCH, NRB, NPC, further arguments) for the Stage1Variant v / LAUNCH(KS) for its q -> x depth: the rows of stage1_variant
@@ -3489,6 +3578,17 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
     return 0;
 }
 
+// k-depth of cas_tail_kernel (its own, not the ks of sym_gm_kernel): the stage-1 variant's, but 11 steps where they
+// cover N (41 <= N <= 44)
+static int tail_depth(int N, const Stage1Variant& v) { return N >= 41 && N <= 44 ? 11 : v.ks; }
+#define OOVQE_TAIL_DISPATCH(ks, LAUNCH)                                                           \
+    switch (ks) {                                                                                 \
+    case 4: LAUNCH(4); break;                                                                     \
+    case 8: LAUNCH(8); break;                                                                     \
+    case 11: LAUNCH(11); break;                                                                   \
+    default: LAUNCH(12); break;                                                                   \
+    }
+
 // cas_tail_kernel: kept entries of g_mo[n] (NC) and LDS bytes for one workgroup per geometry (0: it does not fit)
 static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* NC)
 {
@@ -3502,7 +3602,7 @@ static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* 
     *NC = nc;
     const size_t na2 = (size_t)na * na, na4 = na2 * na2;
     size_t scr = (size_t)N * N;                                           // W
-    const size_t t3 = (size_t)4 * v.ks * (M * 16 + 8);                    // T3s
+    const size_t t3 = (size_t)4 * tail_depth(N, v) * (M * 16 + 8);        // T3s
     const size_t fe = (size_t)nrdm * M * N + (size_t)nrdm * N +           // Fcol + Epart + Ga + Dc
                       (size_t)N * na * na * na + (size_t)N * no * na2;
     if (t3 > scr) scr = t3;
@@ -3527,7 +3627,7 @@ static int cas_tail_batched(const CasEvalArgs& a, const EvalPlan& p, const doubl
                            a.out_stride);                                                         \
     } while (0)
     oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
-    OOVQE_KS_DISPATCH(v, OOVQE_LAUNCH_TAIL)
+    OOVQE_TAIL_DISPATCH(tail_depth(a.N, v), OOVQE_LAUNCH_TAIL)
     oovqe_profile_mark_stop(st);
 #undef OOVQE_LAUNCH_TAIL
     OOVQE_CHECK_LAUNCH("cas_eval/tail");
@@ -4453,6 +4553,11 @@ extern "C" const char* oovqe_oo_eval_plan_describe(int n_theta, int n_gates, int
             add("%s%s@%zu+%zu", first ? "" : ",", block_names[b], p.off[b], p.len[b]);
             first = 0;
         }
+    if (p.path == PATH_PACKED_TAIL) {
+        Stage1Variant v;
+        if (stage1_variant(N, &v)) return nullptr;
+        add("; tail=cas_tail_kernel<%d>; tail_lds=%zu", tail_depth(N, v), p.tail_lds);
+    }
     return line;
 }
 

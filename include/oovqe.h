@@ -50,6 +50,7 @@ const char* oovqe_last_stage1_kernel(void);
  *    oovqe_last_stage1_kernel reports it>; circuit=<none|rides|own>; w=<0|1>; launches=<kernel launches>;
  *    k1_hosts=<0|1: the batched contraction launch of the path, if it makes one, can host circuit workgroups>;
  *    labels=<bracketed launches by profile label, comma separated>; blocks=<name>@<offset>+<doubles>,..."
+ *   and, on the packed_tail path only, "; tail=cas_tail_kernel<k-depth>; tail_lds=<LDS bytes of its workgroup>"
  * for an oovqe_oo_eval_batch call of this shape (n_qubits == 0: an oovqe_cas_eval_batch call with
  * nrdm = derivatives ? 1 + n_theta : 1) under the debug options set now and the CU count of the current device
  * (256 without one).  w: the circuit's own launch leaves W = C^T h_ao for the Fock stage; blocks: the parts of the
