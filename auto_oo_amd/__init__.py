@@ -34,6 +34,9 @@ from .berry import ActiveSpaceRotation, bogoliubov_atob_cas, state_overlap   # n
 from .excitations import generalized_pair_doubles           # noqa: E402
 from .active_space import active_space_integrals, molecular_hamiltonian_coefficients   # noqa: E402
 from .ci import casci, CIResult                             # noqa: E402
+from . import overlaps                                      # noqa: E402
+from .overlaps import sector_overlaps, state_overlaps_oao, track_roots, apply_tracking   # noqa: E402
+from .gto import cross_overlap_batch                        # noqa: E402
 
 __all__ = [
     "Parameterized_circuit", "Moldata", "Moldata_sto3g", "GTOBasis", "integrals_batch", "gto", "scf", "nucgrad", "RHFResult", "rhf_batch", "ao_to_oao", "get_formal_geo", "OO_pqc", "OO_pqc_batch", "OO_energy", "mo_ao_to_mo_oao",
@@ -41,4 +44,5 @@ __all__ = [
     "vector_to_skew_symmetric", "skew_symmetric_to_vector", "non_redundant_indices", "NewtonStep", "BatchedNewtonStep", "ActiveSpaceRotation", "bogoliubov_atob_cas", "state_overlap",
     "generalized_pair_doubles", "active_space_integrals", "molecular_hamiltonian_coefficients", "casci", "CIResult",
     "properties", "moment_integrals_batch", "multipole_moments", "traceless_quadrupole", "DEBYE",
+    "overlaps", "sector_overlaps", "state_overlaps_oao", "track_roots", "apply_tracking", "cross_overlap_batch",
 ]

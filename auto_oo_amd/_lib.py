@@ -236,6 +236,14 @@ SIGNATURES = {
     "oovqe_gto_moments_expect_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                                       c_double_p, c_int32_p, c_double_p, c_stream]),
+    "oovqe_gto_cross_overlap_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                                     ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int,
+                                                     c_double_p, c_stream]),
+    "oovqe_sector_overlap_batch": (ctypes.c_int, [c_double_p] + [ctypes.c_int] * 6 + [c_double_p, ctypes.c_int,
+                                                                                    c_double_p, ctypes.c_int, c_int32_p,
+                                                                                    ctypes.c_int64, ctypes.c_int,
+                                                                                    ctypes.c_int, c_double_p, c_double_p,
+                                                                                    c_stream]),
     "oovqe_cas_ao_densities_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                                     c_double_p, ctypes.c_int, c_double_p, c_double_p, c_stream]),
     "oovqe_fock_jk_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,

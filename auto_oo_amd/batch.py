@@ -295,6 +295,8 @@ class OO_pqc_batch:
 
         - The SIGN of an off-diagonal element is that of the product of the two CI vectors' signs as ``casci`` fixes
           them (largest |component| positive), as for the transition dipoles of ``casci_dipole_matrix``.
+          ``overlaps.track_roots`` on the ``O`` of ``casci_overlaps`` gives the order and signs that are continuous along
+          a path, ``overlaps.apply_tracking`` applies them to ``gradients``.
         - Within a degenerate pair of roots only the 2 x 2 block is defined (up to a rotation of the pair), not its
           split into elements.
         - ``G_IJ / (E_J - E_I)`` is the CI part of the derivative coupling only: the orbital-connection term
@@ -459,7 +461,9 @@ class OO_pqc_batch:
         <J|E_pq|I>) / 2``, taken as ``(gamma_+ - gamma_-) / 2`` from the RDMs of ``(c_I +- c_J) / sqrt 2``: no nuclear
         term, and the core density drops out.  The matrix is symmetric in (I, J), exactly.  The SIGN of a transition
         dipole is that of the product of the two CI vectors' signs, which ``casci`` fixes by making the largest
-        |component| of each vector positive; along a path on which that component changes, the sign can flip."""
+        |component| of each vector positive; along a path on which that component changes, the sign can flip:
+        ``overlaps.track_roots`` on the ``O`` of ``casci_overlaps`` gives the order and signs that are continuous along a
+        path, ``overlaps.apply_tracking`` applies them to ``dipoles``."""
         rows = self._moment_rows(None, "casci_dipole_matrix")
         if self.ncas > nucgrad.MAX_NCAS:
             raise NotImplementedError(f"casci_dipole_matrix covers ncas <= {nucgrad.MAX_NCAS}")
@@ -485,6 +489,122 @@ class OO_pqc_batch:
             dip[:, ii, jj] = val[:, R:]
             dip[:, jj, ii] = val[:, R:]
         return e, dip
+
+    # ---- overlaps between the states of different geometries (auto_oo_amd/overlaps.py, csrc/overlap.hip) --------------
+    def _pair_rows(self, pairs, closed):
+        """``pairs`` -> ([P] rows a, [P] rows b) on the host; the default is the loop (g, g + 1 mod G) when ``closed``,
+        else the open path (g, g + 1)."""
+        if pairs is None:
+            a = list(range(self.G if closed else self.G - 1))
+            return a, [(g + 1) % self.G for g in a]
+        p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+        p = p.reshape(-1, 2) if p.size else p.reshape(0, 2)
+        if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError("pairs must be [P, 2] integer rows of the batch")
+        if p.size and (p.min() < 0 or p.max() >= self.G):
+            raise ValueError(f"pairs must hold rows in 0..{self.G - 1}")
+        return [int(v) for v in p[:, 0]], [int(v) for v in p[:, 1]]
+
+    def _exact_overlaps(self, ra, rb, bra, ket, n_alpha, n_beta, orthogonalize, index):
+        """``core_det^2 out`` of ``overlaps.sector_overlaps`` in the true AO metric for the pairs (ra[p], rb[p]):
+        ``s = C_a[:, :M]^T S_ab C_b[:, :M]``, M = core + active orbitals, ``S_ab`` from ``gto.cross_overlap_into``."""
+        from . import overlaps
+        M = self._n_occ + self.ncas
+        ia = torch.as_tensor(ra, device=self.device)
+        ib = torch.as_tensor(rb, device=self.device)
+        S_ab = GTO.cross_overlap_into(self.basis, self.coords_bohr[ia], self.coords_bohr[ib])
+        Ca_t = self.mo_coeff[ia][:, :, :M].transpose(1, 2).contiguous()
+        Cb = self.mo_coeff[ib][:, :, :M].contiguous()
+        s = ops.matmul_nn_batch(Ca_t, ops.matmul_nn_batch(S_ab, Cb))
+        out, core = overlaps.sector_overlaps(s, self._n_occ, self.ncas, n_alpha, n_beta, bra, ket, orthogonalize, True,
+                                             index)
+        return out * (core * core)[:, None, None]
+
+    def state_overlaps(self, thetas, pairs=None, metric="ao", orthogonalize=None):
+        """Overlaps between the circuit states of pairs of geometries -> [P] on the device, all pairs from one launch
+        of ``oovqe_sector_overlap_batch``.
+
+        Args:
+            thetas: [G, n_theta], the parameters of every geometry's state
+            pairs: [P, 2] rows (a, b) of the batch; default the closed loop (g, g + 1 mod G)
+            metric: ``"ao"``: the exact ``<Psi_a|Psi_b>`` of the two all-electron wave functions at the batch's current
+                orbitals, ``s = C_a[:, :M]^T S_ab C_b[:, :M]`` with the AO overlap ``S_ab`` between the two geometries
+                (``gto.cross_overlap_batch``), core included; needs a batch made by ``from_geometries`` (RuntimeError
+                otherwise).  ``"oao"``: the reference notebook's estimator ``<psi_b| G_{a->b} |psi_a>``
+                (``overlaps.state_overlaps_oao``: the two orthonormal-AO bases treated as one, no core), any batch
+            orthogonalize: ``"givens"`` or False; default ``"givens"`` for ``"oao"``, False for ``"ao"``
+
+        Both circuit engines are served (dense registers through the index table of the sector).  ncas <= 8; every
+        error is raised before anything is launched."""
+        from . import overlaps
+        from .sector import sector_of
+        if metric not in ("ao", "oao"):
+            raise ValueError(f"metric = {metric!r} ('ao' or 'oao')")
+        if orthogonalize is None:
+            orthogonalize = "givens" if metric == "oao" else False
+        overlaps.orthogonalize_mode(orthogonalize)
+        n_alpha, n_beta = sector_of(self.pqc.hfstate, self.ncas)
+        overlaps.check_scope(self.ncas, n_alpha, n_beta, self._n_occ if metric == "ao" else 0)
+        if metric == "ao" and (self.basis is None or self.coords_bohr is None):
+            raise RuntimeError("state_overlaps(metric='ao') needs a batch made by OO_pqc_batch.from_geometries")
+        ra, rb = self._pair_rows(pairs, closed=True)
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        if not ra:
+            return torch.empty(0, dtype=F64, device=self.device)
+        pqc = self.pqc
+        if getattr(pqc, "_use_sector", False):
+            psi, index = pqc._sector.state(thetas), None
+        else:
+            psi = ops.circuit_state(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, pqc._init_index)
+            index = overlaps.dense_index(self.ncas, n_alpha, n_beta, self.device)
+        ia = torch.as_tensor(ra, device=self.device)
+        ib = torch.as_tensor(rb, device=self.device)
+        if metric == "oao":
+            return overlaps.state_overlaps_oao(psi[ib], psi[ia], self.oao_mo_coeff[ia], self.oao_mo_coeff[ib],
+                                               self.act_idx, self.nelecas, orthogonalize)
+        return self._exact_overlaps(ra, rb, psi[ia][:, None], psi[ib][:, None], n_alpha, n_beta, orthogonalize,
+                                    index)[:, 0, 0]
+
+    def berry_phase(self, thetas, metric="oao"):
+        """The Berry-phase estimator of the closed loop the batch's geometries form -> ``(W, overlaps)`` on the device:
+        ``overlaps`` [G] are ``state_overlaps(thetas, metric=metric)`` of the pairs (g, g + 1 mod G) and ``W`` their
+        product (-1 around a conical intersection, +1 otherwise, for a finely sampled loop)."""
+        o = self.state_overlaps(thetas, None, metric)
+        return torch.prod(o), o
+
+    def casci_overlaps(self, nroots=2, pairs=None, fix_singlet=True, vecs=None, tol=1e-9, max_iter=200):
+        """CASCI states of every geometry at its current orbitals (``casci``) and their exact overlaps between pairs
+        of geometries -> ``(energies [G, R], vecs [G, R, Dc], O [P, R, R])`` on the device, ``O[p, I, J] =
+        <Psi_I(R_a)|Psi_J(R_b)>`` in the true AO metric (core included) for the pair p = (a, b).
+
+        Args:
+            nroots, fix_singlet, tol, max_iter: as for ``casci``
+            pairs: [P, 2] rows of the batch; default the open path (g, g + 1), which is what
+                ``overlaps.track_roots`` takes
+            vecs: [G, R, Dc] CI vectors of an earlier ``casci`` to use instead of solving again (``energies`` is then
+                returned as None)
+
+        Needs a batch made by ``from_geometries`` (RuntimeError otherwise)."""
+        from . import ci, overlaps
+        ci.check_scope(self.ncas, self.nelecas, nroots)
+        n = self.nelecas // 2
+        overlaps.check_scope(self.ncas, n, n, self._n_occ)
+        if self.basis is None or self.coords_bohr is None:
+            raise RuntimeError("casci_overlaps needs a batch made by OO_pqc_batch.from_geometries")
+        ra, rb = self._pair_rows(pairs, closed=False)
+        e = None
+        if vecs is None:
+            e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        else:
+            vecs = ops.as_device(vecs, self.device)
+            if vecs.dim() != 3 or tuple(vecs.shape[:2]) != (self.G, int(nroots)):
+                raise ValueError(f"vecs has shape {tuple(vecs.shape)}, expected [{self.G}, {int(nroots)}, Dc]")
+        R = int(nroots)
+        if not ra:
+            return e, vecs, torch.empty((0, R, R), dtype=F64, device=self.device)
+        ia = torch.as_tensor(ra, device=self.device)
+        ib = torch.as_tensor(rb, device=self.device)
+        return e, vecs, self._exact_overlaps(ra, rb, vecs[ia], vecs[ib], n, n, False, None)
 
     def _rhf_orbitals(self, how, rows):
         """``oao_mo_coeffs="rhf"``: the orbitals of the rows (None: all) from the device solver."""

@@ -205,6 +205,19 @@ def integrals_from_table(table, charges, coords_bohr, d_functions="spherical", b
                                *cartesian_integrals_from_table(table, charges, coords_bohr, boys))
 
 
+def cross_overlap_from_table(table, coords_a_bohr, coords_b_bohr, d_functions="spherical"):
+    """``S_ab[mu, nu] = <chi_mu at R_a | chi_nu at R_b>`` [nao, nao] over the functions of ``integrals_from_table``, on
+    the host: the twin of ``gto.cross_overlap_batch``.  The off-diagonal block of the overlap of the basis placed on
+    both geometries at once; not symmetric."""
+    A = np.asarray(coords_a_bohr, dtype=float)
+    B = np.asarray(coords_b_bohr, dtype=float)
+    shells = shells_from_table(table, A) + shells_from_table(table, B)
+    n = len(shells) // 2
+    S = one_electron_integrals(shells, (), ())[0]
+    U = basis_transform(table, d_functions)
+    return U @ S[:n, n:] @ U.T
+
+
 # powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
 MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
 

@@ -288,6 +288,46 @@ def moment_integrals_batch(basis, coords, order=1, origin=None):
     return moment_integrals_into(basis, xyz, out, order, origin_to_device(origin, G, device, 1.0 / BOHR))
 
 
+def cross_overlap_into(basis, coords_a_bohr, coords_b_bohr, out=None):
+    """``cross_overlap_batch`` for geometries that are already [P, natm, 3] device tensors in Bohr, written into the
+    contiguous device tensor ``out`` [P, N, N] (made when None) on the current stream."""
+    lib = _lib.load()
+    for name, x in (("coords_a_bohr", coords_a_bohr), ("coords_b_bohr", coords_b_bohr)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (basis.natm, 3):
+            raise ValueError(f"{name} of shape {tuple(getattr(x, 'shape', ()))}, expected [P, {basis.natm}, 3]")
+    P, N = int(coords_a_bohr.shape[0]), basis.nao
+    if int(coords_b_bohr.shape[0]) != P:
+        raise ValueError(f"{P} bra geometries and {int(coords_b_bohr.shape[0])} ket geometries")
+    dev = coords_a_bohr.device
+    if out is None:
+        out = torch.empty((P, N, N), dtype=F64, device=dev)
+    elif tuple(out.shape) != (P, N, N):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(P, N, N)}")
+    t = basis.device_tables(dev)
+    xa = coords_a_bohr.to(F64).contiguous()
+    xb = coords_b_bohr.to(device=dev, dtype=F64).contiguous()
+    check(lib.oovqe_gto_cross_overlap_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm, P,
+        dptr(xa), dptr(xb), N, dptr(out), stream_ptr()), "oovqe_gto_cross_overlap_batch")
+    return out
+
+
+def cross_overlap_batch(basis, coords_a, coords_b):
+    """AO overlap between two geometries, for P pairs on the device (``oovqe_gto_cross_overlap_batch``,
+    csrc/gto_cross.hip): ``S_ab[p, mu, nu] = <chi_mu at coords_a[p] | chi_nu at coords_b[p]>`` over the functions of
+    ``integrals_batch`` (s, p and d shells, both d forms).
+
+    Args:
+        basis: GTOBasis
+        coords_a, coords_b: P geometries each, in the forms ``integrals_batch`` takes (Angstrom)
+
+    Returns [P, N, N] on the device.  The matrices are not symmetric (``S_ab(a, b) = S_ab(b, a)^T``); a pair has the
+    same bits wherever it stands in the list."""
+    device = _lib.require_device()
+    return cross_overlap_into(basis, coords_to_device(basis, coords_a, device),
+                              coords_to_device(basis, coords_b, device))
+
+
 def refuse_d_gradient(basis):
     """Nuclear derivatives of d shells need f-type intermediates, which the derivative kernels do not have."""
     if basis.max_l >= 2:

@@ -793,6 +793,39 @@ int oovqe_rhf_batch(const double* h, const double* g, const double* s, const dou
                     double* mo_energy, double* e_elec, double* diis_error, int32_t* iterations, int32_t* info,
                     double* work, int32_t* verdict_host, oovqe_stream_t stream);
 
+/* ---- overlaps between the states of two geometries (gto_cross.hip, overlap.hip) -------------------------------------
+ * AO overlap between two geometries: out[p][mu][nu] = <chi_mu at coords_a[p] | chi_nu at coords_b[p]> for npair pairs,
+ * coords_a, coords_b [npair][natm][3] in Bohr, out [npair][nao][nao] (not symmetric: every one of the nshell^2 ordered
+ * shell pairs is computed).  Basis tables, limits, return codes, AO order and normalisation are those of
+ * oovqe_gto_integrals_batch (s, p and d shells, both d forms); no work buffer.  The call reads the shell table back (one
+ * stream synchronisation).  A pair has the same bits wherever it stands in the list. */
+int oovqe_gto_cross_overlap_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                  const double* coefs, int natm, int npair, const double* coords_a,
+                                  const double* coords_b, int nao, double* out, oovqe_stream_t stream);
+/* Overlaps of vectors of the (n_alpha, n_beta) sector of ncas orbitals over non-orthogonal orbitals, one workgroup per
+ * pair p:
+ *   out[p][i][j] = sum_{J, I} bra[p][i][Ja, Jb] det U[occ(Ja), occ(Ia)] det U[occ(Jb), occ(Ib)] ket[p][j][Ia, Ib]
+ * s [npair][m][m], m = n_core + ncas: the overlap of the doubly occupied (first n_core) and active orbitals of the bra
+ * geometry (rows) with those of the ket geometry (columns).  core_det[p] = det(s_cc) (LU with partial pivoting; 0 for a
+ * singular block, out[p] is then NaN) and U = s_aa - s_ac s_cc^-1 s_ca, so that the all-electron overlap of two CAS wave
+ * functions is core_det^2 out; n_core = 0: U = s.  mode 1 replaces U by the Q factor of U = Q R with a positive diagonal
+ * of R, mode 0 uses it as it is.  bra [npair][rb][ld], ket [npair][rk][ld] hold the vectors in the sector layout
+ * c[ia * nb + ib] (strings ascending by value, orbital p at bit ncas - 1 - p) when index is null (ld >= na nb), else
+ * element (ia, ib) at index[ia * nb + ib] < ld (int32 [na nb] on the device; entries outside [0, ld) read as 0): a dense
+ * register of 2^(2 ncas) amplitudes goes in directly.  with_signs != 0 multiplies both sides with the sign that moves
+ * every alpha operator in front of the beta ones (the vectors of the circuit engines and of oovqe_ci_davidson_batch
+ * carry the interleaved order).  Determinants of order 1 .. 8 pivot: a permutation matrix is a legitimate U.
+ * Scope: ncas <= OOVQE_OVERLAP_MAX_NCAS, m <= OOVQE_OVERLAP_MAX_M, at most OOVQE_OVERLAP_MAX_STRINGS strings per spin,
+ * 1 <= rb, rk <= OOVQE_OVERLAP_MAX_ROOTS, mode 0 or 1; anything else returns a negative code before any launch
+ * (oovqe_last_error gives the text).  A pair has the same bits wherever it stands in the list. */
+#define OOVQE_OVERLAP_MAX_NCAS 8
+#define OOVQE_OVERLAP_MAX_M 48
+#define OOVQE_OVERLAP_MAX_STRINGS 70
+#define OOVQE_OVERLAP_MAX_ROOTS 4
+int oovqe_sector_overlap_batch(const double* s, int m, int n_core, int ncas, int n_alpha, int n_beta, int npair,
+                               const double* bra, int rb, const double* ket, int rk, const int32_t* index, int64_t ld,
+                               int mode, int with_signs, double* out, double* core_det, oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
