@@ -52,10 +52,12 @@ __host__ __device__ inline void gto_setup_body(const int* __restrict__ shells, i
     }
 }
 
+#ifndef GTO_BODIES_ONLY
 __global__ void gto_setup_kernel(const int* __restrict__ shells, int nshell, int* __restrict__ iw)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) gto_setup_body(shells, nshell, iw);
 }
+#endif
 
 __host__ __device__ __forceinline__ void gto_pair_body(long tid, const int* __restrict__ shells, int nshell,
                                                        const double* __restrict__ exps,
@@ -105,6 +107,7 @@ __host__ __device__ __forceinline__ void gto_pair_body(long tid, const int* __re
     v.x = a / p; v.y = b / p; o2[3] = v;
 }
 
+#ifndef GTO_BODIES_ONLY
 __global__ __launch_bounds__(256) void gto_pair_kernel(const int* __restrict__ shells, int nshell,
                                                        const double* __restrict__ exps,
                                                        const double* __restrict__ coefs,
@@ -115,10 +118,12 @@ __global__ __launch_bounds__(256) void gto_pair_kernel(const int* __restrict__ s
     gto_pair_body((long)blockIdx.x * blockDim.x + threadIdx.x, shells, nshell, exps, coefs, charges, natm, coords,
                   batch, kp, pairs, nuc);
 }
+#endif
 
 // ---- one-electron integrals ---------------------------------------------------------------------------------------
 // (the bodies of the integral kernels are __host__ __device__ functions of the thread index: a CPU build of this file
-// can run them in a loop under a host debugger or sanitizer)
+// -- GTO_BODIES_ONLY: no kernel, no entry point; tools/gto_host.hip -- runs them in a loop, under a host debugger or
+// sanitizer if need be)
 template <int LA, int LB, int SPLIT>
 __host__ __device__ __forceinline__ void gto_one_body(long tid, const int* __restrict__ iw,
                                                       const int* __restrict__ shells, int nshell, int count,
@@ -219,6 +224,7 @@ __host__ __device__ __forceinline__ void gto_one_body(long tid, const int* __res
     });
 }
 
+#ifndef GTO_BODIES_ONLY
 template <int LA, int LB>
 __global__ __launch_bounds__(GTO_NT) void gto_one_kernel(const int* __restrict__ iw, const int* __restrict__ shells,
                                                          int nshell, int count, const double* __restrict__ charges,
@@ -229,6 +235,7 @@ __global__ __launch_bounds__(GTO_NT) void gto_one_kernel(const int* __restrict__
     gto_one_body<LA, LB, GTO_SPLIT>((long)blockIdx.x * GTO_NT + threadIdx.x, iw, shells, nshell, count, charges, natm, coords,
                          batch, pairs, kp, nao, overlap, h_ao);
 }
+#endif
 
 // ---- two-electron integrals ---------------------------------------------------------------------------------------
 template <int LA, int LB, int LC, int LD, int SPLIT>
@@ -363,6 +370,7 @@ __host__ __device__ __forceinline__ void gto_eri_body(long tid, const int* __res
     });
 }
 
+#ifndef GTO_BODIES_ONLY
 template <int LA, int LB, int LC, int LD>
 __global__ __launch_bounds__(GTO_NT) void gto_eri_kernel(const int* __restrict__ iw, const int* __restrict__ shells,
                                                          int nshell, int nbra, int nket, long nquart,
@@ -373,7 +381,9 @@ __global__ __launch_bounds__(GTO_NT) void gto_eri_kernel(const int* __restrict__
     gto_eri_body<LA, LB, LC, LD, GTO_SPLIT>((long)blockIdx.x * GTO_NT + threadIdx.x, iw, shells, nshell, nbra, nket, nquart,
                                  coords, natm, batch, pairs, kp, nao, g_ao);
 }
+#endif
 
+#ifndef GTO_BODIES_ONLY
 // ---- Boys function on its own (the accuracy test) ----------------------------------------------------------------
 template <int L>
 __global__ void gto_boys_kernel(const double* __restrict__ T, long count, double* __restrict__ F)
@@ -601,3 +611,4 @@ extern "C" int oovqe_boys(int nmax, const double* t, int64_t count, double* f, o
     OOVQE_CHECK_LAUNCH("gto_boys_kernel");
     return 0;
 }
+#endif  // GTO_BODIES_ONLY

@@ -195,6 +195,7 @@ __host__ __device__ __forceinline__ void gto_d_one_body(long grp, int lane, int 
     }
 }
 
+#ifndef GTO_BODIES_ONLY
 template <int LA, int LB>
 __global__ __launch_bounds__(GTO_D1_NT) void gto_d_one_kernel(const int* __restrict__ iw,
                                                               const int* __restrict__ shells, int nshell, int count,
@@ -207,6 +208,7 @@ __global__ __launch_bounds__(GTO_D1_NT) void gto_d_one_kernel(const int* __restr
     gto_d_one_body<LA, LB>((long)blockIdx.x, (int)threadIdx.x, GTO_D1_NT, s, iw, shells, nshell, count, charges, natm,
                            coords, batch, pairs, kp, nao, overlap, h_ao);
 }
+#endif
 
 // ---- two-electron integrals of the 15 quartet classes with a d shell -------------------------------------------------
 template <int LA, int LB, int LC, int LD> struct gto_dq_lds_t {
@@ -381,6 +383,7 @@ __host__ __device__ __forceinline__ void gto_d_eri_body(long grp, int lane, int 
     }
 }
 
+#ifndef GTO_BODIES_ONLY
 template <int LA, int LB, int LC, int LD>
 __global__ __launch_bounds__((gto_dq_lds_t<LA, LB, LC, LD>::NT)) void gto_d_eri_kernel(
     const int* __restrict__ iw, const int* __restrict__ shells, int nshell, int nbra, int nket, long nquart,
@@ -443,3 +446,4 @@ int gto_d_launch_two_electron(const gto_launch_t& a)
 #undef GTO_D_ERI
     return 0;
 }
+#endif  // GTO_BODIES_ONLY

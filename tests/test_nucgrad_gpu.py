@@ -57,7 +57,8 @@ def dev():
 def case(name):
     """(basis, coordinates [natm, 3] in Bohr as a host array)"""
     if name == "h2":
-        # one 1-primitive and one 6-primitive s shell per atom (MAX_PRIM; 36 primitive pairs are no multiple of 8)
+        # one 1-primitive and one 6-primitive s shell per atom (36 primitive pairs are no multiple of 8; MAX_PRIM = 10
+        # is reached in tests/test_gto_edges_gpu.py)
         table = {"H": [(0, [0.6], [1.0]),
                        (0, [30.0, 8.0, 2.5, 0.9, 0.35, 0.12], [0.02, 0.08, 0.25, 0.4, 0.3, 0.1])]}
         basis = gto.GTOBasis(["H", "H"], table)
@@ -150,7 +151,7 @@ def analytic(name, which, coords_bohr=None):
 def test_raw_contraction_term_by_term_and_together(name):
     """Every term alone (the others null) and all together against the finite-difference reference, each within 10 x
     the disagreement of the reference's two step sizes for that term; the parts add up to the whole to 1e-12.
-    h2: MAX_PRIM primitives, 36 primitive pairs on 8 lanes; hf: every pair and quartet class on two centres; water:
+    h2: 6 primitives, 36 primitive pairs on 8 lanes; hf: every pair and quartet class on two centres; water:
     three centres; formaldimine: four."""
     ref, dis, dis_all = raw_reference(name)
     parts = []
