@@ -30,12 +30,12 @@
 #define OVL_US 8                 // row stride of U
 
 // sign of moving every alpha creation operator in front of the beta ones (berry.sector_tables)
-__device__ __forceinline__ double ovl_sign(unsigned ma, unsigned mb)
+__host__ __device__ __forceinline__ double ovl_sign(unsigned ma, unsigned mb)
 {
     int n = 0;
     while (ma) {
-        const int b = __ffs((int)ma) - 1;
-        n += __popc(mb >> (b + 1));
+        const int b = __builtin_ffs((int)ma) - 1;
+        n += __builtin_popcount(mb >> (b + 1));
         ma &= ma - 1;
     }
     return (n & 1) ? -1.0 : 1.0;
@@ -43,7 +43,8 @@ __device__ __forceinline__ double ovl_sign(unsigned ma, unsigned mb)
 
 // det U[occ(mj), occ(mi)] of order K: occupied orbitals ascending = set bits descending
 template <int K>
-__device__ __forceinline__ double ovl_minor(const double* __restrict__ U, int ncas, unsigned mj, unsigned mi)
+__host__ __device__ __forceinline__ double ovl_minor(const double* __restrict__ U, int ncas, unsigned mj,
+                                                     unsigned mi)
 {
     if constexpr (K == 0) {
         return 1.0;
@@ -51,7 +52,7 @@ __device__ __forceinline__ double ovl_minor(const double* __restrict__ U, int nc
         int rj[K], ci[K];
 #pragma unroll
         for (int r = 0; r < K; ++r) {
-            const int hj = 31 - __clz((int)mj), hi = 31 - __clz((int)mi);
+            const int hj = 31 - (mj ? __builtin_clz(mj) : 32), hi = 31 - (mi ? __builtin_clz(mi) : 32);
             rj[r] = (ncas - 1 - hj) * OVL_US;
             ci[r] = ncas - 1 - hi;
             mj &= ~(1u << hj);
@@ -99,6 +100,7 @@ __device__ __forceinline__ double ovl_minor(const double* __restrict__ U, int nc
     }
 }
 
+#ifndef OVERLAP_BODIES_ONLY
 template <int K>
 __device__ __forceinline__ void ovl_minors(double* __restrict__ MT, const double* __restrict__ U, int ncas,
                                            const int* __restrict__ str, int n, int t)
@@ -316,3 +318,4 @@ extern "C" int oovqe_sector_overlap_batch(const double* s, int m, int n_core, in
     OOVQE_CHECK_LAUNCH("sector_overlap_kernel");
     return 0;
 }
+#endif  // OVERLAP_BODIES_ONLY

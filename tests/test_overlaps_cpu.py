@@ -13,7 +13,7 @@ import torch
 
 from tests import _gto_d as D
 from tests import _overlaps as V
-from auto_oo_amd import _lib, gaussian, gto, overlaps
+from auto_oo_amd import _lib, berry, gaussian, gto, overlaps
 from auto_oo_amd.berry import sector_tables
 from auto_oo_amd.sector import sector_of
 from oracle import cpu_ref as R
@@ -241,3 +241,120 @@ def test_python_errors_come_before_any_device_call():
         overlaps.sector_overlaps(np.zeros((1, 49, 49)), 45, 4, 2, 2, v, v)
     with pytest.raises(ValueError, match="ActiveSpaceRotation"):
         overlaps.state_overlaps_oao(v[:, 0], v[:, 0], z, z, [0, 1, 2], 4, orthogonalize="polar")
+
+
+# ---- 6. the determinant and sign routines of the sector kernel on the CPU ---------------------------------------------
+def _strings(ncas, k):
+    return [v for v in range(1 << ncas) if bin(v).count("1") == k]
+
+
+def _minor_cases():
+    mats = dict(V.pivot_matrices(8))
+    mats["random"] = V.trial_matrices(8, 88)["nonorthogonal"]
+    mats["permutation"] = V.trial_matrices(8, 88)["permutation"]
+    out = [(8, name, U) for name, U in mats.items()]
+    out.append((5, "random", V.trial_matrices(5, 55)["nonorthogonal"]))       # (another ncas: the strings' bit order)
+    out.append((5, "exchange", V.pivot_matrices(5)["exchange"]))
+    return out
+
+
+@pytest.mark.parametrize("case", _minor_cases(), ids=lambda c: f"{c[1]}{c[0]}")
+def test_ovl_minor_on_the_cpu_against_mpmath_det(case):
+    """Every order K = 0 .. ncas, every pair of strings: ``ovl_minor<K>`` through the kernel's switch against
+    ``np.linalg.det`` of the submatrix, and 40 seeded pairs per order against 40-digit ``mpmath.det``.  Bound: 1e-13 x
+    the Hadamard bound of the submatrix (the product of the norms of its rows) -- an LU of order <= 8 in float64 loses
+    a few 1e-16 of that.  Measured: at most 3.9e-16 of it (mpmath), 1.1e-15 (numpy, whose own LU is in that figure)."""
+    ncas, name, U = case
+    res = V.run_overlap_host([(ncas, k, U, _strings(ncas, k), _strings(ncas, k)) for k in range(ncas + 1)])
+    rng = np.random.default_rng(ncas)
+    worst_mp = worst_np = 0.0
+    for k, (got, _) in enumerate(res):
+        strs = _strings(ncas, k)
+        occ = [[p for p in range(ncas) if (m >> (ncas - 1 - p)) & 1] for m in strs]
+        assert got.shape == (len(strs), len(strs)) and np.isfinite(got).all()
+        if k == 0:
+            assert got[0, 0] == 1.0
+            continue
+        sub = np.stack([[U[np.ix_(oj, oi)] for oi in occ] for oj in occ])            # [J, I, k, k]
+        hadamard = np.prod(np.linalg.norm(sub, axis=3), axis=2)
+        err = np.abs(got - np.linalg.det(sub))
+        assert (err <= 1e-13 * hadamard).all(), (name, k)
+        worst_np = max(worst_np, (err / np.maximum(hadamard, 1e-300)).max())
+        # where a column or a row of the submatrix vanishes, the minor is exactly 0
+        dead = (np.abs(sub).max(axis=2) == 0).any(axis=2) | (np.abs(sub).max(axis=3) == 0).any(axis=2)
+        assert (got[dead] == 0.0).all()
+        if name in ("zero_column", "zero_row"):
+            assert dead.sum() == (len(strs) * sum(1 for o in occ if 2 in o))
+        pairs = {(int(a), int(b)) for a, b in rng.integers(0, len(strs), (40, 2))} | {(0, 0), (len(strs) - 1, 0)}
+        for j, i in sorted(pairs):
+            ref = float(V.exact_det(sub[j, i].tolist()))
+            e = abs(got[j, i] - ref)
+            assert e <= 1e-13 * hadamard[j, i], (name, k, j, i, got[j, i], ref)
+            if hadamard[j, i] > 0:
+                worst_mp = max(worst_mp, e / hadamard[j, i])
+    print(f"ovl_minor {name} ncas {ncas}: worst {worst_mp:.2e} (mpmath), {worst_np:.2e} (numpy) of the Hadamard bound")
+
+
+def test_ovl_minor_sees_a_transposition_and_a_missed_exchange():
+    """The test above would notice: the minors of U^T, and the minors without their exchange signs, differ from those
+    of U by far more than the bound."""
+    U = V.pivot_matrices(8)["exchange"]
+    strs = _strings(8, 4)
+    (a, _), (b, _) = V.run_overlap_host([(8, 4, U, strs, strs), (8, 4, U.T.copy(), strs, strs)])
+    assert np.abs(a - b.T).max() < 1e-13 and np.abs(a - b).max() > 1e-2
+    assert np.abs(np.abs(a) - a).max() > 1e-2                   # (both signs occur: a lost exchange would show)
+
+
+def test_ovl_sign_on_the_cpu_is_the_sign_table_of_every_sector():
+    recs, want = [], []
+    for ncas in range(1, 9):
+        for n_alpha in range(ncas + 1):
+            for n_beta in range(ncas + 1):
+                ua, ub, _, sign = sector_tables(ncas, n_alpha, n_beta)
+                assert list(ua) == _strings(ncas, n_alpha) and list(ub) == _strings(ncas, n_beta)
+                recs.append((ncas, -1, np.eye(ncas), list(ua), list(ub)))
+                want.append(sign)
+    for (minors, got), ref, rec in zip(V.run_overlap_host(recs), want, recs):
+        assert minors is None and np.array_equal(got, ref), rec[0]
+
+
+# ---- 7. the 40-digit reference and its fixtures -----------------------------------------------------------------------
+def test_exact_reference_is_the_host_route_and_brute_force():
+    rng = np.random.default_rng(17)
+    s = V._generic_s(5, 2, rng)
+    bra, ket = rng.standard_normal((2, 9)), rng.standard_normal((3, 9))
+    out, det, U = V.exact_reference(s, 2, 3, 2, 1, bra, ket)
+    brute = V.brute_force(s, 2, 3, 2, 1, bra, ket)
+    assert np.abs(det * det * out - brute).max() < 1e-13 and abs(det - np.linalg.det(s[:2, :2])) < 1e-15
+    # unsigned, through an index table with entries outside the vector, and the Q factor
+    index = np.array([3, -1, 0, 9, 8, 1, 2, 7, 4])
+    out1, _, Q = V.exact_reference(s, 2, 3, 2, 1, bra, ket, index, 1, False)
+    host, _ = V.host_reference(s, 2, 3, 2, 1, bra, ket, index, 1, False)
+    assert np.abs(out1 - host).max() < 1e-13
+    assert np.abs(Q.T @ Q - np.eye(3)).max() < 1e-15
+    assert np.abs(Q - berry.givens_orthogonal(U)).max() < 1e-14 and (np.diag(Q.T @ U) > 0).all()
+
+
+def test_the_scope_fixtures_are_complete_and_one_regenerates():
+    for name in V.SCOPE_CASES:
+        f = V.scope_fixture(name)
+        ncas, n_alpha, n_beta, n_core, mode, P, rb, rk, _ = V.SCOPE_CASES[name]
+        assert (int(f["ncas"]), int(f["n_alpha"]), int(f["n_beta"]), int(f["n_core"]), int(f["mode"])) == \
+            (ncas, n_alpha, n_beta, n_core, mode)
+        assert f["out"].shape == (P, rb, rk) and f["core_det"].shape == (P,) and np.isfinite(f["out"]).all()
+        assert os.path.getsize(V.scope_fixture_path(name)) < 120 * 1024
+        if V.SCOPE_CASES[name][8] == "generic" and n_core > 1:
+            assert f["cond_core"].max() < 5.0
+            assert (np.abs(f["s"][:, 1:n_core, 0]).max(axis=1) > np.abs(f["s"][:, 0, 0])).all()      # the first search swaps
+    for name, cond in (("c4_32_cond3", 1e3), ("c4_32_cond6", 1e6)):
+        assert np.abs(V.scope_fixture(name)["cond_core"] / cond - 1).max() < 1e-6
+    for name, cond in (("c6_42_q2", 1e2), ("c6_42_q5", 1e5)):
+        assert np.abs(V.scope_fixture(name)["cond_U"] / cond - 1).max() < 1e-6
+    f = V.scope_fixture("c4_21_perm6")
+    assert np.array_equal(np.abs(f["core_det"]), np.ones(2)) and (np.diagonal(f["s"][:, :6, :6], axis1=1, axis2=2) == 0).all()
+    a, b = V.scope_fixture("c8_43_core40"), V.scope_fixture("c8_34_core40")
+    assert np.array_equal(a["s"], b["s"]) and not np.array_equal(a["out"], b["out"])
+    new, old = V.make_scope_case("c5_05_core3"), V.scope_fixture("c5_05_core3")
+    assert set(new) == set(old)
+    for key in new:
+        assert np.array_equal(np.asarray(new[key]), old[key]), key
