@@ -167,6 +167,9 @@ SIGNATURES = {
     "oovqe_sector_rdms_tb": (ctypes.c_int, [c_double_p, ctypes.c_int, c_int32_p, c_int32_p, c_int32_p,
                                             c_int32_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                             c_double_p, c_double_p, c_double_p, c_stream]),
+    "oovqe_sector_transition_rdm1": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, c_int32_p, c_int32_p,
+                                                    c_int32_p, c_int32_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    c_double_p, c_stream]),
     "oovqe_sector_pairs_size": (ctypes.c_int64, [ctypes.c_int] * 3),
     "oovqe_sector_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int32_p, c_int32_p,
                                           c_int32_p, c_int32_p, ctypes.c_int, ctypes.c_int, c_int32_p, c_stream]),
@@ -230,6 +233,11 @@ SIGNATURES = {
                                                      ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                                      ctypes.c_int] + [c_double_p] * 3 + [ctypes.c_uint]
                                       + [c_double_p] * 2 + [c_stream]),
+    "oovqe_gto_overlap_connection_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
+    "oovqe_gto_overlap_connection_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p,
+                                                          c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                          c_double_p, ctypes.c_int, ctypes.c_int]
+                                           + [c_double_p] * 3 + [c_stream]),
     "oovqe_gto_moments_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
                                                ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                                ctypes.c_int] + [c_double_p] * 3 + [c_stream]),

@@ -31,6 +31,7 @@ from .oo_energy import mo_ao_to_mo_oao, non_redundant_indices
 F64 = torch.float64
 
 CASCIGradients = namedtuple("CASCIGradients", "energies ci gradients")
+CASCICouplings = namedtuple("CASCICouplings", "energies ci gradients couplings ci_term orbital_term")
 
 
 class OO_pqc_batch:
@@ -299,8 +300,8 @@ class OO_pqc_batch:
           a path, ``overlaps.apply_tracking`` applies them to ``gradients``.
         - Within a degenerate pair of roots only the 2 x 2 block is defined (up to a rotation of the pair), not its
           split into elements.
-        - ``G_IJ / (E_J - E_I)`` is the CI part of the derivative coupling only: the orbital-connection term
-          ``<p|dq/dR>`` is not built.
+        - ``G_IJ / (E_J - E_I)`` is the CI part of the derivative coupling only: ``casci_derivative_couplings`` adds the
+          orbital-connection term ``<p|dq/dR>`` and returns the whole nonadiabatic coupling vector.
 
         Args:
             nroots, fix_singlet, tol, max_iter: as for ``casci`` (which raises when a solve does not converge)
@@ -312,12 +313,23 @@ class OO_pqc_batch:
         integrals are used).  Needs a batch made by ``from_geometries`` (RuntimeError otherwise); d shells and
         ``ncas > nucgrad.MAX_NCAS`` raise NotImplementedError, a CI problem out of scope ValueError
         (``ci.check_scope``)."""
+        rows, e, vecs, out = self._casci_gradient_pass("casci_nuclear_gradients", nroots, fix_singlet, index, chunk, tol,
+                                                       max_iter)
+        sel = torch.as_tensor(rows, device=self.device)
+        return CASCIGradients(e[sel], vecs[sel], out)
+
+    def _casci_gradient_pass(self, who, nroots, fix_singlet, index, chunk, tol, max_iter, after_solve=None):
+        """The body of ``casci_nuclear_gradients`` -> (rows, energies [G, R], ci [G, R, Dc] of the WHOLE stack, gradients
+        [len(rows), R, R, natm, 3]).  ``after_solve(rows, energies)`` is called between the CASCI solve and the pass over
+        the derivative integrals (what it raises leaves before that pass)."""
         from . import ci
-        rows = self._gradient_rows(index, "casci_nuclear_gradients")
+        rows = self._gradient_rows(index, who)
         if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"casci_nuclear_gradients covers ncas <= {nucgrad.MAX_NCAS}")
+            raise NotImplementedError(f"{who} covers ncas <= {nucgrad.MAX_NCAS}")
         ci.check_scope(self.ncas, self.nelecas, nroots)
         e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        if after_solve is not None:
+            after_solve(rows, e)
         G, R, a, N, natm = self.G, int(nroots), self.ncas, self.nao, self.basis.natm
         pairs = nucgrad.state_pairs(R)
         P = len(pairs)
@@ -359,8 +371,87 @@ class OO_pqc_batch:
             if P:
                 blk[:, ii, jj] = val[:, R:]
                 blk[:, jj, ii] = val[:, R:]
+        return rows, e, vecs, out
+
+    def casci_derivative_couplings(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200,
+                                   min_gap=1e-6, small_gap="raise"):
+        """CASCI states of every geometry at its current orbitals with their nonadiabatic (derivative) coupling vectors
+        ``d_IJ^A = <Psi_I | d Psi_J / dR_A>`` -> ``CASCICouplings(energies [G', R], ci [G', R, Dc], gradients, couplings,
+        ci_term, orbital_term)`` on the device; the last four are [G', R, R, natm, 3], ``gradients`` in Hartree / Bohr
+        and exactly what ``casci_nuclear_gradients`` returns for the same roots, the others in 1 / Bohr:
+
+            couplings = ci_term + orbital_term,   ci_term_IJ = G_IJ / (E_J - E_I),
+            orbital_term_IJ^A = sum_pq gamma^IJ_pq <phi_p | d phi_q / dR_A> = Da . T^A + WQc . dS/dR_A
+
+        with the transition 1-RDM ``gamma^IJ_pq = <c_I|E_pq|c_J>`` (``ci.transition_rdm1``), of which only the
+        antisymmetric part ``a = (gamma^IJ - gamma^IJ^T) / 2`` enters (``<phi_p|d phi_q>`` is antisymmetric; the core
+        contributes nothing), ``Da = C_act a C_act^T`` contracted with the derivative of the ket of the AO overlap
+        (``gto.overlap_connection_into``), and ``WQc`` the pull-back of the dependence of ``S^-1/2`` on the geometry
+        (``nucgrad.connection_pullback``) contracted with ``dS/dR`` (``gto.gradient_sets_into``).  Exact for the wave
+        functions the batch defines: orbitals ``C(R) = S(R)^-1/2 U`` with ``U`` fixed, CASCI roots of those orbitals.
+        No electron-translation factors: ``sum_A couplings`` is the net of the ``Da . T^A`` part, not zero.
+
+        - All three matrices are antisymmetric in (I, J) exactly (one element is computed and stored to both places
+          with opposite sign) and their diagonal is exactly zero.
+        - The SIGN of an element is that of the product of the two CI vectors' signs as ``casci`` fixes them;
+          ``overlaps.apply_tracking(couplings, perm, sign)`` gives the couplings of the tracked states.
+        - Within a (near-)degenerate pair the coupling diverges.  ``min_gap``: a pair with ``|E_J - E_I|`` below it is
+          handled as ``small_gap`` says: ``"raise"``: ValueError naming the geometries and pairs, before the pass over
+          the derivative integrals; ``"nan"``: NaN in ``ci_term`` and ``couplings`` for those elements only,
+          ``orbital_term`` still filled.
+
+        ``index``, ``chunk``, the scope and the errors are those of ``casci_nuclear_gradients``; the same bits whatever
+        ``index`` and ``chunk``."""
+        from . import ci
+        if small_gap not in ("raise", "nan"):
+            raise ValueError(f"small_gap = {small_gap!r} ('raise' or 'nan')")
+        who = "casci_derivative_couplings"
+        R, a, N = int(nroots), self.ncas, self.nao
+        pairs = nucgrad.state_pairs(R)
+        min_gap = float(min_gap)
+
+        def gaps_ok(rows, e):
+            if small_gap != "raise" or not pairs:
+                return
+            eh = e.detach().cpu().numpy()
+            bad = [(g, i, j) for g in rows for i, j in pairs if abs(eh[g, i] - eh[g, j]) < min_gap]
+            if bad:
+                raise ValueError(f"{who}: |E_J - E_I| < {min_gap:g} Ha for (geometry, I, J) = "
+                                 + ", ".join(str(b) for b in bad) + ": the coupling diverges there "
+                                 "(small_gap='nan' marks these elements instead)")
+
+        rows, e, vecs, grads = self._casci_gradient_pass(who, nroots, fix_singlet, index, chunk, tol, max_iter, gaps_ok)
+        natm = self.basis.natm
         sel = torch.as_tensor(rows, device=self.device)
-        return CASCIGradients(e[sel], vecs[sel], out)
+        c, P = len(rows), len(pairs)
+        e, vecs = e[sel], vecs[sel]
+        ci_term = torch.zeros((c, R, R, natm, 3), dtype=F64, device=self.device)
+        orb = torch.zeros_like(ci_term)
+        if P and c:
+            ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
+            jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
+            # transition 1-RDMs <c_I|E_pq|c_J> of the pairs (I > J) and their antisymmetric parts
+            t = ci.transition_rdm1(vecs[:, ii].reshape(c * P, -1), vecs[:, jj].reshape(c * P, -1), a, self.nelecas)
+            asym = (0.5 * (t - t.transpose(1, 2))).contiguous()
+            # Da = C_act a C_act^T, and a in the whole MO basis for the pull-back through S^-1/2
+            Ca = self.mo_coeff[sel][:, :, self._n_occ:self._n_occ + a]
+            Ca = Ca[:, None].expand(c, P, N, a).reshape(c * P, N, a).contiguous()
+            Da = ops.matmul_nn_batch(ops.matmul_nn_batch(Ca, asym), Ca.transpose(1, 2).contiguous())
+            a_mo = torch.zeros((c * P, N, N), dtype=F64, device=self.device)
+            a_mo[:, self._n_occ:self._n_occ + a, self._n_occ:self._n_occ + a] = asym
+            wqc = nucgrad.connection_pullback(self.overlap[sel], self.oao_mo_coeff[sel], a_mo.view(c, P, N, N))
+            xyz = self.coords_bohr[sel]
+            val = GTO.overlap_connection_into(self.basis, xyz, Da.view(c, P, N, N))
+            val = val + GTO.gradient_sets_into(self.basis, xyz, None, wqc, None, False)
+            orb[:, ii, jj] = val
+            orb[:, jj, ii] = -val
+            gap = e[:, jj] - e[:, ii]                                    # E_J - E_I of element (I, J)
+            cval = grads[:, ii, jj] / gap[:, :, None, None]
+            if small_gap == "nan":
+                cval = torch.where((gap.abs() < min_gap)[:, :, None, None], torch.full_like(cval, float("nan")), cval)
+            ci_term[:, ii, jj] = cval
+            ci_term[:, jj, ii] = -cval
+        return CASCICouplings(e, vecs, grads, ci_term + orb, ci_term, orb)
 
     def rhf_nuclear_gradient(self, result=None, index=None):
         """Closed-shell Hartree-Fock gradient -> [G, natm, 3] (device, Hartree / Bohr) from a converged

@@ -196,6 +196,36 @@ def sector_rdms(vecs, ncas, nelecas):
     return gamma, Gamma
 
 
+def transition_rdm1(bra, ket, ncas, nelecas):
+    """Spin-summed transition 1-RDMs ``gamma[n, p, q] = <bra_n| E_pq |ket_n>`` [n, a, a] of pairs of sector vectors
+    bra, ket [n, Dc] (``oovqe_sector_transition_rdm1``, csrc/sector_trdm.hip).  NOT symmetric in (p, q) for different
+    vectors and not symmetrised: ``gamma[n].T`` is the matrix with bra and ket exchanged.  Equal vectors give the gamma
+    of ``sector_rdms``.  The scope is ``check_scope``'s; a pair's matrix has the same bits whatever the other pairs."""
+    a = int(ncas)
+    dc = check_scope(a, nelecas)
+    lib = _lib.load()
+    ua, ra = string_tables(a, int(nelecas) // 2)
+    na = len(ua)
+    if not isinstance(bra, torch.Tensor) or not isinstance(ket, torch.Tensor) or not bra.is_cuda:
+        raise ValueError("bra and ket must be device tensors")
+    if bra.shape != ket.shape or bra.dim() < 1 or int(bra.shape[-1]) != dc:
+        raise ValueError(f"bra of shape {tuple(bra.shape)}, ket of shape {tuple(ket.shape)}: expected two [n, {dc}]")
+    dev = bra.device
+    bra = bra.to(F64).reshape(-1, dc).contiguous()
+    ket = ket.to(device=dev, dtype=F64).reshape(-1, dc).contiguous()
+    n = int(bra.shape[0])
+    gamma = torch.empty((n, a, a), dtype=F64, device=dev)
+    if n == 0:
+        return gamma
+    un = torch.as_tensor(ua.astype(np.int32)).to(dev)
+    rk = torch.as_tensor(ra).to(dev)
+    i32 = torch.int32
+    check(lib.oovqe_sector_transition_rdm1(dptr(bra), dptr(ket), a, dptr(un, i32), dptr(un, i32), dptr(rk, i32),
+                                           dptr(rk, i32), na, na, n, dptr(gamma), stream_ptr()),
+          "oovqe_sector_transition_rdm1")
+    return gamma
+
+
 # ---- the reference's solver methods ---------------------------------------------------------------------------
 def _need_orbitals(mol):
     mol.run_rhf()            # (raises the RuntimeError of run_rhf when the container has no orbitals)

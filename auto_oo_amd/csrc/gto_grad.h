@@ -104,6 +104,11 @@ static inline int64_t grad_records(int nshell, int natm)
     return npair * (natm + 1) + npair * (npair + 1) * 3;     // (at most: every quartet (pp|pp))
 }
 
+// gto_grad_reduce_kernel (gto_grad.hip) for `rows` stacks of nrec records each, stack r to grad[r][natm][3]; with_nuc
+// adds the nuclear repulsion of coords[r]
+int gto_grad_reduce_launch(const double* rec, long nrec, const double* charges, int natm, const double* coords,
+                           int with_nuc, long rows, double* grad, hipStream_t st);
+
 // records per quartet: two sides; (pp|pp) in three launches per side (GRAD_PPPP_PARTS)
 #define GRAD_PPPP_PARTS 3
 template <int LA, int LB, int LC, int LD> constexpr int grad_parts()

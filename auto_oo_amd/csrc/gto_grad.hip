@@ -333,6 +333,21 @@ __global__ __launch_bounds__(GRAD_RT) void gto_grad_reduce_kernel(const double* 
     }
 }
 
+// the reduction for `rows` stacks of nrec records (gto_grad.h: for the kernels of other files); grad [rows][natm][3]
+int gto_grad_reduce_launch(const double* rec, long nrec, const double* charges, int natm, const double* coords,
+                           int with_nuc, long rows, double* grad, hipStream_t st)
+{
+    for (long r0 = 0; r0 < rows; r0 += 65535) {
+        const long n = rows - r0 < 65535 ? rows - r0 : 65535;
+        hipLaunchKernelGGL(gto_grad_reduce_kernel, dim3(natm, (unsigned)n), dim3(GRAD_RT), 0, st,
+                           rec + (size_t)r0 * nrec * GRAD_REC, nrec, charges, natm,
+                           coords ? coords + (size_t)r0 * natm * 3 : nullptr, with_nuc ? 1 : 0,
+                           grad + (size_t)r0 * natm * 3);
+        OOVQE_CHECK_LAUNCH("gto_grad_reduce_kernel");
+    }
+    return 0;
+}
+
 // ---- AO densities of a CAS wave function ----------------------------------------------------------------------------
 // D1 = Dc + Da, Dc = 2 C_c C_c^T, Da = C_a sym(gamma) C_a^T, and (E_2 = 1/2 sum (pq|rs) D2_pqrs)
 //   D2_pqrs = Dc_pq Dc_rs - (Dc_pr Dc_qs + Dc_ps Dc_qr) / 4 + Dc_pq Da_rs + Dc_rs Da_pq

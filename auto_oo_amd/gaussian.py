@@ -218,6 +218,34 @@ def cross_overlap_from_table(table, coords_a_bohr, coords_b_bohr, d_functions="s
     return U @ S[:n, n:] @ U.T
 
 
+def overlap_connection_from_table(table, coords_bohr, d_functions="spherical"):
+    """``T[A, d, mu, nu] = <chi_mu | d chi_nu / dR_A,d>`` [natm, 3, nao, nao] over the functions of
+    ``integrals_from_table``, on the host and analytic: the twin of ``gto.overlap_connection_batch`` (which contracts it
+    with a matrix).  Non-zero only for ``nu`` on atom A, pairs of functions on ONE atom included.  The derivative of the
+    ket with respect to its centre raises and lowers one power, ``2 b x^(j+1) - j x^(j-1)``, the contraction
+    coefficients kept: every element is a combination of the overlaps of ``one_electron_integrals``.  ``T^A + T^A^T =
+    dS / dR_A``."""
+    R = np.asarray(coords_bohr, dtype=float)
+    shells = shells_from_table(table, R)
+    atoms = [int(atom) for atom, l, _, _ in table for _ in _CARTESIAN[int(l)]]
+    n = len(shells)
+    T = np.zeros((len(R), 3, n, n))
+    for ia, A in enumerate(shells):
+        for ib, B in enumerate(shells):
+            a, b = A.exps[:, None], B.exps[None, :]
+            Q = A.center - B.center
+            cc = A.coefs[:, None] * B.coefs[None, :]
+            s = [_overlap_1d(A.lmn[d], B.lmn[d], Q[d], a, b) for d in range(3)]
+            for d in range(3):
+                j = B.lmn[d]
+                ds = 2.0 * b * _overlap_1d(A.lmn[d], j + 1, Q[d], a, b)
+                if j:
+                    ds = ds - j * _overlap_1d(A.lmn[d], j - 1, Q[d], a, b)
+                T[atoms[ib], d, ia, ib] = np.sum(cc * ds * s[(d + 1) % 3] * s[(d + 2) % 3])
+    U = basis_transform(table, d_functions)
+    return U @ T @ U.T
+
+
 # powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
 MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
 

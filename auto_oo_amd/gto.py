@@ -200,6 +200,21 @@ class GTOBasis:
         return buf
 
 
+    def connection_work(self, device, G, nset):
+        """Work buffer of ``oovqe_gto_overlap_connection_batch`` for G geometries of ``nset`` matrices, one per
+        (device, stream) like ``work``."""
+        key = ("connection", str(device), torch.cuda.current_stream().cuda_stream)
+        buf = self._work.get(key)
+        what = "oovqe_gto_overlap_connection_work_size"
+        size = int(_lib.load().oovqe_gto_overlap_connection_work_size(self.nshell, self.max_nprim, self.natm, G,
+                                                                      int(nset)))
+        if size < 0:
+            check(size, what)
+        if buf is None or buf.numel() < size:
+            buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
+        return buf
+
+
 def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=None, nuc=None):
     """The integrals of the geometries ``coords_bohr`` ([G, natm, 3] device tensor, Bohr) written into the given
     contiguous device tensors ([G, N, N], [G, N, N], [G, N, N, N, N], [G]; None skips one), on the current stream."""
@@ -456,6 +471,63 @@ def gradient_sets_batch(basis, coords, dm1=None, wq=None, dm2=None, nuc=True):
     refuse_d_gradient(basis)
     device = _lib.require_device()
     return gradient_sets_into(basis, coords_to_device(basis, coords, device), dm1, wq, dm2, nuc)
+
+
+def overlap_connection_into(basis, coords_bohr, D, work=None):
+    """``overlap_connection_batch`` for geometries that are already a [G, natm, 3] device tensor in Bohr, on the current
+    stream.  ``work``: a buffer of ``oovqe_gto_overlap_connection_work_size`` doubles to use instead of the basis'
+    own."""
+    refuse_d_gradient(basis)
+    lib = _lib.load()
+    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
+            basis.natm, 3):
+        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
+                         f"[G, {basis.natm}, 3]")
+    G, N = int(coords_bohr.shape[0]), basis.nao
+    if not isinstance(D, torch.Tensor) or D.dim() != 4:
+        raise ValueError(f"D has shape {tuple(getattr(D, 'shape', ()))}, expected [G, K, N, N]")
+    K = int(D.shape[1])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} matrices per geometry (1 .. {MAX_GRAD_SETS})")
+    if tuple(D.shape) != (G, K, N, N):
+        raise ValueError(f"D has shape {tuple(D.shape)}, expected {(G, K, N, N)}")
+    dev = coords_bohr.device
+    t = basis.device_tables(dev)
+    D = D.to(device=dev, dtype=F64).contiguous()
+    out = torch.empty((G, K, basis.natm, 3), dtype=F64, device=dev)
+    if G == 0:
+        return out
+    if work is None:
+        work = basis.connection_work(dev, G, K)
+    xyz = coords_bohr.to(F64).contiguous()
+    check(lib.oovqe_gto_overlap_connection_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(xyz), N, K, dptr(D), dptr(out), dptr(work), stream_ptr()),
+        "oovqe_gto_overlap_connection_batch")
+    return out
+
+
+def overlap_connection_batch(basis, coords, D):
+    """The derivative of the ket of the overlap contracted with K general matrices per geometry on the device
+    (``oovqe_gto_overlap_connection_batch``, csrc/gto_connection.hip; no derivative integral is stored):
+
+        out[g, k, A, :] = sum over mu, and nu on atom A, of D[g, k, mu, nu] <chi_mu | grad_A chi_nu>
+
+    -- with ``D = C_a a C_a^T`` the AO part ``Da . T^A`` of the orbital-connection term of a derivative coupling
+    (``gaussian.overlap_connection_from_table`` is ``T`` on the host).
+
+    Args:
+        basis: GTOBasis (s and p shells)
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        D: [G, K, N, N] device tensor, K = 1 .. ``MAX_GRAD_SETS``; NOT taken as symmetric or antisymmetric: both
+            (mu, nu) and (nu, mu) are read.  For symmetric D the result is ``gradient_batch(wq=D / 2, nuc=False)``
+
+    Returns [G, K, natm, 3] on the device, in 1 / Bohr.  Functions on ONE atom contribute (``<s|d p>`` on one centre).
+    A (geometry, matrix) has the same bits whatever the stack, the other matrices, their number and its place among
+    them."""
+    refuse_d_gradient(basis)
+    device = _lib.require_device()
+    return overlap_connection_into(basis, coords_to_device(basis, coords, device), D)
 
 
 def sym_invsqrt_batch(S, out=None):

@@ -87,10 +87,39 @@ def overlap_pullback(overlap, oao_mo_coeff, fock):
     de_dc = 2.0 * mm(mm(x_inv, U), _t(fock))
     gx = mm(de_dc, _t(U))
     gx = 0.5 * (gx + gx.transpose(1, 2))
+    return _pull_back(gx, sq, V, Vt)
+
+
+def _pull_back(gx, sq, V, Vt):
+    """``V [K o (V^T G_X V)] V^T``, symmetrised: a symmetric ``G_X = d./dX`` [G, N, N] pulled back to the overlap
+    ``S = V diag(sq^2) V^T``."""
+    mm = ops.matmul_nn_batch
     m = mm(mm(Vt, gx.contiguous()), V)
     k = -1.0 / (sq[:, :, None] * sq[:, None, :] * (sq[:, :, None] + sq[:, None, :]))
     wq = mm(mm(V, (k * m).contiguous()), Vt)
     return (0.5 * (wq + wq.transpose(1, 2))).contiguous()
+
+
+def connection_pullback(overlap, oao_mo_coeff, a):
+    """``WQc`` [G, N, N] with ``WQc . dS = sum_pq a_pq (U^T X^-1 dX U)_pq``, the part of the orbital connection
+    ``<phi_p|d phi_q>`` of ``C = X U`` that comes from ``X = S^-1/2`` at fixed ``U``, contracted with ``a`` [G, N, N]
+    in the MO basis (for a derivative coupling the antisymmetric part of a transition 1-RDM, zero outside the active
+    block): ``G_X = sym(X^-1 U a U^T)`` -- which does not vanish for antisymmetric ``a``, since ``X^-1`` stands on one
+    side only -- pulled back to the overlap with the divided differences of ``overlap_pullback``.  ``a`` [G, K, N, N]:
+    K sets per geometry -> [G, K, N, N]."""
+    if a.dim() == 4:
+        G, K, N = int(a.shape[0]), int(a.shape[1]), int(a.shape[-1])
+        rep = lambda x: x[:, None].expand(G, K, N, N).reshape(G * K, N, N)
+        return connection_pullback(rep(overlap), rep(oao_mo_coeff), a.reshape(G * K, N, N)).reshape(G, K, N, N)
+    w, V, _ = scf.sym_eigh_batch(overlap.contiguous())
+    mm = ops.matmul_nn_batch
+    sq = torch.sqrt(w)
+    Vt = _t(V)
+    U = oao_mo_coeff.contiguous()
+    x_inv = mm((V * sq[:, None, :]).contiguous(), Vt)
+    gx = mm(mm(x_inv, U), mm(a.contiguous(), _t(U)))
+    gx = 0.5 * (gx + gx.transpose(1, 2))
+    return _pull_back(gx, sq, V, Vt)
 
 
 def energy_weighted_pullback(mo_coeff, mo_energy, n_occ):
@@ -184,3 +213,12 @@ def overlap_pullback_host(overlap, g_x):
     k = -1.0 / (sq[:, None] * sq[None, :] * (sq[:, None] + sq[None, :]))
     g_x = 0.5 * (g_x + g_x.T)
     return V @ (k * (V.T @ g_x @ V)) @ V.T
+
+
+def connection_pullback_host(overlap, oao_mo_coeff, a):
+    """numpy twin of ``connection_pullback`` for ONE geometry: ``G_X = X^-1 U a U^T`` (``overlap_pullback_host``
+    symmetrises it)."""
+    s, V = np.linalg.eigh(np.asarray(overlap))
+    U = np.asarray(oao_mo_coeff)
+    x_inv = (V * np.sqrt(s)) @ V.T
+    return overlap_pullback_host(overlap, x_inv @ U @ np.asarray(a) @ U.T)

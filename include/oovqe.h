@@ -473,6 +473,12 @@ int64_t oovqe_sector_tables_size(int ncas, int na, int nb);
 int oovqe_sector_rdms_tb(const double* psi_c, int ncas, const uint32_t* unrank_a, const uint32_t* unrank_b,
                          const int32_t* rank_a, const int32_t* rank_b, int na, int nb, int batch, const uint16_t* tabs,
                          double* gamma, double* Gamma, double* work, oovqe_stream_t stream);
+/* Transition one-particle density matrices (csrc/sector_trdm.hip): gamma[n][p][q] = <bra_n| E_pq |ket_n> for npairs pairs
+ * of sector vectors bra, ket [npairs][na * nb]; N_alpha = N_beta (na == nb <= 70), ncas <= 8.  Not symmetrised in (p, q);
+ * equal bra and ket give the gamma of oovqe_sector_rdms.  Fixed summation order, one workgroup per pair. */
+int oovqe_sector_transition_rdm1(const double* bra, const double* ket, int ncas, const uint32_t* unrank_a,
+                                 const uint32_t* unrank_b, const int32_t* rank_a, const int32_t* rank_b, int na, int nb,
+                                 int npairs, double* gamma, oovqe_stream_t stream);
 int oovqe_sector_pairs(const oovqe_gate_t* gates, int n_gates, int ncas, const uint32_t* unrank_a,
                        const uint32_t* unrank_b, const int32_t* rank_a, const int32_t* rank_b, int na, int nb,
                        uint32_t* pairs, oovqe_stream_t stream);
@@ -751,6 +757,18 @@ int oovqe_gto_gradient_sets_batch(int nshell, const int32_t* shells, int nprim_t
                                   const double* coefs, int natm, const double* charges, int batch, const double* coords,
                                   int nao, int nset, const double* d1, const double* wq, const double* d2,
                                   unsigned nuc_mask, double* grad, double* work, oovqe_stream_t stream);
+/* One-sided overlap-derivative contraction (csrc/gto_connection.hip), the orbital-connection term of a derivative
+ * coupling: for nset general matrices dm [batch][nset][nao][nao] per geometry (neither symmetric nor antisymmetric: both
+ * (mu, nu) and (nu, mu) are read)
+ *   out[g][k][A][:] = sum over mu, and nu on atom A, of dm[g][k][mu][nu] <chi_mu | grad_A chi_nu>,
+ * pairs of functions on ONE atom included.  s and p shells (a table with l = 2 is refused before any launch),
+ * 1 <= nset <= OOVQE_GTO_GRAD_MAX_SETS; a (geometry, set) has the same bits whatever the stack, the other sets, their
+ * number and its place among them.  work: oovqe_gto_overlap_connection_work_size(...) doubles. */
+int64_t oovqe_gto_overlap_connection_work_size(int nshell, int max_nprim, int natm, int batch, int nset);
+int oovqe_gto_overlap_connection_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                       const double* coefs, int natm, const double* charges, int batch,
+                                       const double* coords, int nao, int nset, const double* dm, double* out,
+                                       double* work, oovqe_stream_t stream);
 /* AO densities of a CAS wave function for the calls above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
  * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
  * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
