@@ -37,6 +37,7 @@ from .ci import casci, CIResult, transition_rdm1            # noqa: E402
 from . import overlaps                                      # noqa: E402
 from .overlaps import sector_overlaps, state_overlaps_oao, track_roots, apply_tracking   # noqa: E402
 from .gto import cross_overlap_batch, overlap_connection_batch   # noqa: E402
+from .gto import point_charge_integrals_batch, point_charge_gradient_batch   # noqa: E402
 
 __all__ = [
     "Parameterized_circuit", "Moldata", "Moldata_sto3g", "GTOBasis", "integrals_batch", "gto", "scf", "nucgrad", "RHFResult", "rhf_batch", "ao_to_oao", "get_formal_geo", "OO_pqc", "OO_pqc_batch", "OO_energy", "mo_ao_to_mo_oao",
@@ -45,5 +46,5 @@ __all__ = [
     "generalized_pair_doubles", "active_space_integrals", "molecular_hamiltonian_coefficients", "casci", "CIResult",
     "properties", "moment_integrals_batch", "multipole_moments", "traceless_quadrupole", "DEBYE",
     "overlaps", "sector_overlaps", "state_overlaps_oao", "track_roots", "apply_tracking", "cross_overlap_batch",
-    "transition_rdm1", "overlap_connection_batch",
+    "transition_rdm1", "overlap_connection_batch", "point_charge_integrals_batch", "point_charge_gradient_batch",
 ]

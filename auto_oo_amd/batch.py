@@ -34,6 +34,21 @@ CASCIGradients = namedtuple("CASCIGradients", "energies ci gradients")
 CASCICouplings = namedtuple("CASCICouplings", "energies ci gradients couplings ci_term orbital_term")
 
 
+def _host_point_charges(basis, coords, point_charges):
+    """``point_charges = (q, xyz in Angstrom)`` of ``from_geometries`` / ``set_geometries`` -> host arrays ([G, M],
+    [G, M, 3] in Angstrom) checked against the number of geometries in ``coords``, or None.  Host work only."""
+    if point_charges is None:
+        return None
+    if not isinstance(point_charges, (tuple, list)) or len(point_charges) != 2:
+        raise ValueError("point_charges must be a pair (q, xyz): charges [G, M] or [M], positions [G, M, 3] or [M, 3] "
+                         "in Angstrom")
+    if isinstance(coords, torch.Tensor) and coords.is_cuda:
+        G = 1 if coords.dim() == 2 else int(coords.shape[0])
+    else:
+        G = int(basis.coordinates(coords).shape[0])
+    return GTO.point_charges_host(G, point_charges[0], point_charges[1])
+
+
 class OO_pqc_batch:
     def __init__(self, pqc, mols, ncas, nelecas, oao_mo_coeffs=None, freeze_active=False):
         """
@@ -107,11 +122,14 @@ class OO_pqc_batch:
         self.step_by_calls = False
         self.basis = None
         self.coords_bohr = None
+        self.charge_q = None            # point charges of an embedded batch [G, M] and
+        self.charge_xyz_bohr = None     # their positions [G, M, 3] in Bohr (from_geometries(point_charges=...))
         self._grad_dm2 = None
 
     # ---- integrals made on the device (auto_oo_amd/gto.py) ----------------------------------------------------------
     @classmethod
-    def from_geometries(cls, pqc, basis, coords, ncas, nelecas, oao_mo_coeffs=None, freeze_active=False):
+    def from_geometries(cls, pqc, basis, coords, ncas, nelecas, oao_mo_coeffs=None, freeze_active=False,
+                        point_charges=None):
         """A batch whose AO integrals are computed on the device (``gto.integrals_batch``) instead of being copied
         from host-built molecules.
 
@@ -124,11 +142,23 @@ class OO_pqc_batch:
                 solver (``OO_pqc_batch.rhf``; no integral tensor is copied to the host, ``OovqeError`` names the
                 geometries that did not converge).  Default (None): RHF orbitals from the host ``gaussian.rhf`` on
                 the integrals copied back once -- slow for a large stack, prefer ``"rhf"``
+            point_charges: ``(q, xyz)``: an environment of M fixed point charges per geometry, ``q`` [G, M] (or [M],
+                shared by all geometries) in units of e and ``xyz`` [G, M, 3] (or [M, 3]) in Angstrom.  The batch is then
+                the molecule EMBEDDED in these charges: ``int1e_ao`` holds the attraction of the electrons by them
+                (``gto.point_charge_integrals_batch``) and ``nuc`` the energy of the nuclei in their field, so energies,
+                orbital derivatives, ``rhf``, ``casci`` and the Newton steps are those of the polarised molecule;
+                ``nuclear_gradient`` and its kin include the charges' pull on the atoms and ``point_charge_gradient``
+                gives the derivative with respect to the charges' positions.  No charge-charge energy is added.  M is
+                fixed for the life of the batch; the charges are kept in ``charge_q`` / ``charge_xyz_bohr`` (Bohr).
         """
         self = cls.__new__(cls)
+        pc = _host_point_charges(basis, coords, point_charges)       # (checked before the device is touched)
         xyz = GTO.coords_to_device(basis, coords)
         self._allocate(pqc, int(xyz.shape[0]), basis.nao, basis.nelectron, ncas, nelecas, freeze_active)
         self.basis = basis
+        if pc is not None:
+            self.charge_q = torch.as_tensor(pc[0]).to(self.device)
+            self.charge_xyz_bohr = torch.as_tensor(pc[1] / GTO.BOHR).to(self.device)
         self._write_integrals(xyz, None)
         if isinstance(oao_mo_coeffs, str):
             self._rhf_orbitals(oao_mo_coeffs, None)
@@ -170,21 +200,43 @@ class OO_pqc_batch:
             a, b = rows[k], rows[e - 1] + 1
             GTO.integrals_into(self.basis, xyz_bohr[k:e], self.overlap[a:b], self.int1e_ao[a:b], self.int2e_ao[a:b],
                                self.nuc[a:b])
+            if self.charge_q is not None:
+                # the embedded molecule: the electrons' attraction by the charges and the nuclei's energy in their field
+                q, r = self.charge_q[a:b], self.charge_xyz_bohr[a:b]
+                self.int1e_ao[a:b] += GTO.point_charge_integrals_into(self.basis, xyz_bohr[k:e], q, r)
+                Z = self.basis.device_tables(self.device).charges
+                dist = (xyz_bohr[k:e, :, None, :] - r[:, None, :, :]).norm(dim=-1)
+                self.nuc[a:b] += (Z[None, :, None] * q[:, None, :] / dist).sum(dim=(1, 2))
             infos.append(GTO.sym_invsqrt_batch(self.overlap[a:b], out=self.oao_coeff[a:b])[1])
             k = e
         GTO.raise_if_dependent(torch.cat(infos), rows)
 
-    def set_geometries(self, coords, index=None, oao_mo_coeffs=None):
+    def set_geometries(self, coords, index=None, oao_mo_coeffs=None, point_charges=None):
         """Move the batch (or its rows ``index``) to new geometries: ``int2e_ao``, ``int1e_ao``, ``oao_coeff`` and
         ``nuc`` are computed in place on the device, then the symmetry flags / packed copy are re-made (``_ingest``)
         and ``mo_coeff = S^-1/2 C_oao`` refreshed.  ``oao_mo_coeffs=None`` keeps the current orbitals (the tracking
         regime of a Berry-phase loop); ``"rhf"`` takes the RHF orbitals of the new geometries from the device solver
         (``OO_pqc_batch.rhf``; ``OovqeError`` names the geometries that did not converge); otherwise one [N, N] matrix
-        per new geometry.  No integral tensor passes through the host."""
+        per new geometry.  No integral tensor passes through the host.  ``point_charges``: ``(q, xyz)`` as for
+        ``from_geometries``, one cloud per new geometry, for a batch that was built with point charges (ValueError
+        otherwise, and for another M); None keeps the stored charges of those rows -- a frozen environment."""
         if self.basis is None:
             raise RuntimeError("set_geometries needs a batch made by OO_pqc_batch.from_geometries")
+        if point_charges is not None and self.charge_q is None:
+            raise ValueError("set_geometries: this batch was built without point charges (give them to "
+                             "from_geometries: their number is fixed at construction)")
+        pc = _host_point_charges(self.basis, coords, point_charges)
+        if pc is not None and pc[0].shape[1] != int(self.charge_q.shape[1]):
+            raise ValueError(f"set_geometries: {pc[0].shape[1]} point charges per geometry, the batch was built with "
+                             f"{int(self.charge_q.shape[1])}")
         xyz = GTO.coords_to_device(self.basis, coords, self.device)
         rows = None if index is None else [int(i) for i in np.atleast_1d(index)]
+        if pc is not None:
+            if len(pc[0]) != (self.G if rows is None else len(rows)):
+                raise ValueError(f"{len(pc[0])} clouds of point charges for {self.G if rows is None else len(rows)} rows")
+            where = slice(None) if rows is None else torch.as_tensor(rows, device=self.device)
+            self.charge_q[where] = torch.as_tensor(pc[0]).to(self.device)
+            self.charge_xyz_bohr[where] = torch.as_tensor(pc[1] / GTO.BOHR).to(self.device)
         self._write_integrals(xyz, rows)
         if isinstance(oao_mo_coeffs, str):
             self._rhf_orbitals(oao_mo_coeffs, rows)
@@ -277,7 +329,54 @@ class OO_pqc_batch:
                                               Gamma[sel, 0], out=self._dm2_buffer(len(sel)))
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
             out[k:k + step] = GTO.gradient_into(self.basis, self.coords_bohr[sel], d1, wq, d2, True)
+            if self.charge_q is not None:
+                out[k:k + step] += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                                                  self.charge_xyz_bohr[sel], d1, True)[0]
         return out
+
+    def _point_charge_rows(self, index, who):
+        rows = self._gradient_rows(index, who)
+        if self.charge_q is None:
+            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries(point_charges=...)")
+        return rows
+
+    def point_charge_gradient(self, thetas, index=None):
+        """dE/dr_k of every geometry of an embedded batch -> [G', M, 3] (device, Hartree / Bohr): the derivative of
+        ``energy_from_parameters(theta_g)`` with respect to the positions of the geometry's point charges at fixed
+        parameters and orbitals; the force on a charge is its negative.  Only the operator's centre moves (the basis
+        does not depend on the charges), so this is ``D1 . dV_ext/dr_k`` plus the nuclei's term, exact at any
+        parameters.  ``index``, the scope and the errors are those of ``nuclear_gradient``; RuntimeError for a batch
+        without point charges."""
+        rows = self._point_charge_rows(index, "point_charge_gradient")
+        if getattr(self.pqc, "_use_sector", False):
+            raise NotImplementedError("point_charge_gradient covers dense-register circuits; circuits in the sector "
+                                      "engine (more than 10 qubits) are not implemented")
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"point_charge_gradient covers ncas <= {nucgrad.MAX_NCAS}")
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        pqc = self.pqc
+        gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
+                                        pqc._init_index, tangents=False)
+        sel = torch.as_tensor(rows, device=self.device)
+        d1 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel, 0], Gamma[sel, 0],
+                                      want_d2=False)[0]
+        return GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                              self.charge_xyz_bohr[sel], d1, True)[1]
+
+    def rhf_point_charge_gradient(self, result=None, index=None):
+        """dE_RHF/dr_k -> [G', M, 3] (device, Hartree / Bohr) of an embedded batch from a converged ``scf.RHFResult``
+        of the rows ``index`` (``self.rhf(index=index)`` is run when none is given), as ``rhf_nuclear_gradient``."""
+        rows = self._point_charge_rows(index, "rhf_point_charge_gradient")
+        if result is None:
+            result = self.rhf(index=index)
+            scf.raise_unless_converged(result.info, rows)
+        if int(result.mo_coeff.shape[0]) != len(rows):
+            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
+                             "for")
+        sel = torch.as_tensor(rows, device=self.device)
+        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+        return GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                              self.charge_xyz_bohr[sel], d1, True)[1]
 
     def casci_nuclear_gradients(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200):
         """CASCI states of every geometry at its current orbitals (``casci``) with their state and interstate nuclear
@@ -366,6 +465,12 @@ class OO_pqc_batch:
                 d2[:, R + p].copy_(t[:, 0].sub_(t[:, 1]).mul_(0.5))
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
             val = GTO.gradient_sets_into(self.basis, self.coords_bohr[sel], d1, wq, d2, [True] * R + [False] * P)
+            if self.charge_q is not None:
+                # the charges' pull on the atoms, one pass per set: with the nuclei's term for a state, without it
+                # for a transition density
+                for s in range(K):
+                    val[:, s] += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                                                self.charge_xyz_bohr[sel], d1[:, s], s < R)[0]
             blk = out[k0:k0 + c]
             blk[:, k, k] = val[:, :R]
             if P:
@@ -466,8 +571,13 @@ class OO_pqc_batch:
             raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
                              "for")
         sel = torch.as_tensor(rows, device=self.device)
-        return nucgrad.rhf_gradient(self.basis, self.coords_bohr[sel], result.mo_coeff, result.mo_energy,
+        grad = nucgrad.rhf_gradient(self.basis, self.coords_bohr[sel], result.mo_coeff, result.mo_energy,
                                     self.nelectron // 2)
+        if self.charge_q is not None:
+            d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+            grad += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                                   self.charge_xyz_bohr[sel], d1, True)[0]
+        return grad
 
     # ---- dipole and second moments (auto_oo_amd/properties.py, csrc/gto_moments.hip) -----------------------------------
     def _moment_rows(self, index, who):

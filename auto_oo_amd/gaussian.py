@@ -246,6 +246,49 @@ def overlap_connection_from_table(table, coords_bohr, d_functions="spherical"):
     return U @ T @ U.T
 
 
+def point_charge_integrals_from_table(table, coords_bohr, q, qxyz_bohr, d_functions="spherical", per_charge=False):
+    """``V_ext[mu, nu] = - sum_k q_k <mu| 1 / |r - r_k| |nu>`` [nao, nao] over the functions of ``integrals_from_table``,
+    on the host: the twin of ``gto.point_charge_integrals_batch``.  The ``V`` of ``one_electron_integrals`` with the
+    charges ``q`` [M] on the centres ``qxyz_bohr`` [M, 3] in place of the nuclei (the same recursions; the charges are
+    an axis of the arrays instead of a loop), followed by ``basis_transform``.  ``per_charge``: the contributions of the
+    charges one by one, [M, nao, nao], instead of their sum."""
+    q = np.asarray(q, dtype=float).reshape(-1)
+    C = np.asarray(qxyz_bohr, dtype=float).reshape(-1, 3)
+    if C.shape[0] != q.size:
+        raise ValueError(f"{q.size} charges and {C.shape[0]} positions")
+    shells = shells_from_table(table, np.asarray(coords_bohr, dtype=float))
+    V = np.zeros((q.size if per_charge else 1, len(shells), len(shells)))
+    for ia, A in enumerate(shells):
+        for ib in range(ia + 1):
+            pair = _Pair(A, shells[ib])
+            p = pair.p[None]
+            PC = [pair.P[None, ..., d] - C[:, d, None, None] for d in range(3)]            # [M, na, nb]
+            Tt = p * (PC[0] ** 2 + PC[1] ** 2 + PC[2] ** 2)
+            cache = {}
+            term = 0.0
+            for (t, u, v) in pair.tuv:
+                term = term + pair.herm(t, u, v)[None] * _R(t, u, v, 0, p, PC, Tt, cache)
+            x = q[:, None, None] * (pair.cc * 2.0 * np.pi / pair.p)[None] * term
+            V[:, ia, ib] = V[:, ib, ia] = -(np.sum(x, axis=(1, 2)) if per_charge else np.sum(x))
+    U = basis_transform(table, d_functions)
+    V = U @ V @ U.T
+    V = 0.5 * (V + V.transpose(0, 2, 1))               # (the products round the two halves differently)
+    return V if per_charge else V[0]
+
+
+def point_charge_energy(charges, coords_bohr, q, qxyz_bohr):
+    """``sum_{A, k} Z_A q_k / |R_A - r_k|``: the classical energy of the nuclei in the field of the point charges (no
+    charge-charge term: the self-energy of the environment is the caller's business)."""
+    Z = np.asarray(charges, dtype=float).reshape(-1)
+    R = np.asarray(coords_bohr, dtype=float).reshape(-1, 3)
+    q = np.asarray(q, dtype=float).reshape(-1)
+    C = np.asarray(qxyz_bohr, dtype=float).reshape(-1, 3)
+    if R.shape[0] != Z.size or C.shape[0] != q.size:
+        raise ValueError(f"{Z.size} nuclear charges for {R.shape[0]} atoms, {q.size} charges for {C.shape[0]} positions")
+    d = np.linalg.norm(R[:, None, :] - C[None, :, :], axis=2)
+    return float(np.sum(Z[:, None] * q[None, :] / d))
+
+
 # powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
 MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
 

@@ -530,6 +530,179 @@ def overlap_connection_batch(basis, coords, D):
     return overlap_connection_into(basis, coords_to_device(basis, coords, device), D)
 
 
+# ---- point-charge embedding (csrc/gto_charges.hip) ---------------------------------------------------------------------
+MAX_POINT_CHARGES = 65535      # per geometry
+
+
+def point_charges_host(G, charges, charge_coords):
+    """``charges`` ([G, M], or [M] shared by all geometries) and ``charge_coords`` ([G, M, 3] or [M, 3]) -> host arrays
+    ([G, M], [G, M, 3]) float64, checked: matching M, 1 <= M <= ``MAX_POINT_CHARGES``, finite values.  Runs on the host
+    only: nothing here touches the device."""
+    def host(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+    q = np.asarray(host(charges), dtype=np.float64)
+    r = np.asarray(host(charge_coords), dtype=np.float64)
+    if q.ndim == 1:
+        q = np.broadcast_to(q, (G,) + q.shape)
+    if r.ndim == 2:
+        r = np.broadcast_to(r, (G,) + r.shape)
+    if q.ndim != 2 or q.shape[0] != G:
+        raise ValueError(f"point charges of shape {np.shape(charges)}, expected [M] or [{G}, M]")
+    M = int(q.shape[1])
+    if r.shape != (G, M, 3):
+        raise ValueError(f"positions of the point charges of shape {np.shape(charge_coords)}, expected [{M}, 3] or "
+                         f"[{G}, {M}, 3] for {M} charges")
+    if not 1 <= M <= MAX_POINT_CHARGES:
+        raise ValueError(f"{M} point charges per geometry (1 .. {MAX_POINT_CHARGES})")
+    if not (np.isfinite(q).all() and np.isfinite(r).all()):
+        raise ValueError("point charges and their positions must be finite")
+    return np.array(q, order="C"), np.array(r, order="C")            # (copies: a broadcast view is read-only)
+
+
+def _check_point_charges(basis, coords_bohr, q, qxyz_bohr):
+    """The device-tensor arguments of the ``point_charge_*_into`` functions -> (G, M, coords, q, qxyz) contiguous."""
+    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
+            basis.natm, 3):
+        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
+                         f"[G, {basis.natm}, 3]")
+    G = int(coords_bohr.shape[0])
+    if G > 65535:
+        raise ValueError(f"{G} geometries in one call (at most 65535)")
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or int(q.shape[0]) != G:
+        raise ValueError(f"point charges of shape {tuple(getattr(q, 'shape', ()))}, expected [{G}, M]")
+    M = int(q.shape[1])
+    if not isinstance(qxyz_bohr, torch.Tensor) or tuple(qxyz_bohr.shape) != (G, M, 3):
+        raise ValueError(f"positions of the point charges of shape {tuple(getattr(qxyz_bohr, 'shape', ()))}, expected "
+                         f"[{G}, {M}, 3]")
+    if not 1 <= M <= MAX_POINT_CHARGES:
+        raise ValueError(f"{M} point charges per geometry (1 .. {MAX_POINT_CHARGES})")
+    dev = coords_bohr.device
+    xyz = coords_bohr.to(F64).contiguous()
+    q = q.to(device=dev, dtype=F64).contiguous()
+    r = qxyz_bohr.to(device=dev, dtype=F64).contiguous()
+    if not (bool(torch.isfinite(xyz).all()) and bool(torch.isfinite(q).all()) and bool(torch.isfinite(r).all())):
+        raise ValueError("coordinates, point charges and their positions must be finite")
+    return G, M, xyz, q, r
+
+
+def point_charge_integrals_into(basis, coords_bohr, q, qxyz_bohr, out=None):
+    """``point_charge_integrals_batch`` for geometries [G, natm, 3], charges [G, M] and positions [G, M, 3] that are
+    already device tensors in atomic units (Bohr), written into the contiguous device tensor ``out`` [G, N, N] (made
+    when None) on the current stream."""
+    G, M, xyz, q, r = _check_point_charges(basis, coords_bohr, q, qxyz_bohr)
+    N = basis.nao
+    dev = xyz.device
+    if out is None:
+        out = torch.empty((G, N, N), dtype=F64, device=dev)
+    elif tuple(out.shape) != (G, N, N):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(G, N, N)}")
+    if G == 0:
+        return out
+    lib = _lib.load()
+    t = basis.device_tables(dev)
+    work = basis.work(dev, G)
+    check(lib.oovqe_gto_point_charge_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(out), dptr(work), stream_ptr()),
+        "oovqe_gto_point_charge_batch")
+    return out
+
+
+def point_charge_integrals_batch(basis, coords, charges, charge_coords):
+    """The embedding operator of G geometries, each in its own cloud of M point charges, on the device
+    (``oovqe_gto_point_charge_batch``, csrc/gto_charges.hip):
+
+        V_ext[g, mu, nu] = - sum_k q[g, k] <chi_mu | 1 / |r - r[g, k]| | chi_nu>
+
+    over the functions of ``integrals_batch`` (s, p and d shells, both d forms); ``int1e_ao + V_ext`` is the core
+    Hamiltonian of the embedded molecule.
+
+    Args:
+        basis: GTOBasis
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        charges: [G, M], or [M] shared by all geometries (units of e), 1 <= M <= ``MAX_POINT_CHARGES``
+        charge_coords: [G, M, 3] or [M, 3] in Angstrom; a charge may lie anywhere, also on a nucleus
+
+    Returns [G, N, N] on the device; every matrix is exactly symmetric and a geometry has the same bits wherever it
+    stands in the stack (``gaussian.point_charge_integrals_from_table`` is the host twin)."""
+    xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
+    q, r = point_charges_host(int(xyz.shape[0]) if xyz.ndim == 3 else 1, charges, charge_coords)
+    device = _lib.require_device()
+    return point_charge_integrals_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(q).to(device),
+                                       torch.as_tensor(r / BOHR).to(device))
+
+
+def refuse_d_point_charge_gradient(basis):
+    if basis.max_l >= 2:
+        raise NotImplementedError("point-charge gradients are implemented for s and p shells only: this basis has "
+                                  "d shells (l = 2)")
+
+
+def point_charge_gradient_work(basis, device, G, M):
+    """Work buffer of ``oovqe_gto_point_charge_gradient_batch``, one per (device, stream) like ``GTOBasis.work``."""
+    key = ("point_charges", str(device), torch.cuda.current_stream().cuda_stream)
+    buf = basis._work.get(key)
+    what = "oovqe_gto_point_charge_gradient_work_size"
+    size = int(_lib.load().oovqe_gto_point_charge_gradient_work_size(basis.nshell, basis.max_nprim, basis.natm, G, M))
+    if size < 0:
+        check(size, what)
+    if buf is None or buf.numel() < size:
+        buf = basis._work[key] = torch.empty(size, dtype=F64, device=device)
+    return buf
+
+
+def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
+    """``point_charge_gradient_batch`` for device tensors in atomic units (geometries [G, natm, 3], charges [G, M],
+    positions [G, M, 3] in Bohr), on the current stream -> (gA [G, natm, 3], gQ [G, M, 3])."""
+    refuse_d_point_charge_gradient(basis)
+    G, M, xyz, q, r = _check_point_charges(basis, coords_bohr, q, qxyz_bohr)
+    N = basis.nao
+    if not isinstance(dm1, torch.Tensor) or tuple(dm1.shape) != (G, N, N):
+        raise ValueError(f"dm1 has shape {tuple(getattr(dm1, 'shape', ()))}, expected {(G, N, N)}")
+    dev = xyz.device
+    gA = torch.empty((G, basis.natm, 3), dtype=F64, device=dev)
+    gQ = torch.empty((G, M, 3), dtype=F64, device=dev)
+    if G == 0:
+        return gA, gQ
+    lib = _lib.load()
+    t = basis.device_tables(dev)
+    d1 = dm1.to(device=dev, dtype=F64).contiguous()
+    work = point_charge_gradient_work(basis, dev, G, M)
+    check(lib.oovqe_gto_point_charge_gradient_batch(
+        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+        dptr(t.charges), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(d1), int(bool(nuc)), dptr(gA), dptr(gQ),
+        dptr(work), stream_ptr()), "oovqe_gto_point_charge_gradient_batch")
+    return gA, gQ
+
+
+def point_charge_gradient_batch(basis, coords, charges, charge_coords, dm1, nuc=True):
+    """The derivatives of the embedding operator of ``point_charge_integrals_batch`` contracted with a one-particle
+    density on the device (``oovqe_gto_point_charge_gradient_batch``; no derivative integral is stored):
+
+        gA[g, A, :] = sum dm1[g] . dV_ext[g] / dR_A      (the basis functions move with atom A)
+        gQ[g, k, :] = sum dm1[g] . dV_ext[g] / dr_k      (the centre of the operator moves)
+
+    Args:
+        basis: GTOBasis (s and p shells; d shells raise NotImplementedError)
+        coords, charges, charge_coords: as for ``point_charge_integrals_batch`` (Angstrom)
+        dm1: [G, N, N] device tensor, taken as symmetric as ``gradient_batch`` takes it
+        nuc: add the derivatives of the classical term ``sum_{A, k} Z_A q_k / |R_A - r_k|`` to both (a charge ON a
+            nucleus then gives NaN; there is no charge-charge term)
+
+    Returns (gA [G, natm, 3], gQ [G, M, 3]) on the device, in Hartree / Bohr; the force on a charge is ``-gQ``.  Pairs of
+    functions on one atom contribute to both.  A geometry has the same bits wherever it stands in the stack."""
+    refuse_d_point_charge_gradient(basis)
+    xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
+    G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
+    q, r = point_charges_host(G, charges, charge_coords)
+    N = basis.nao
+    if not isinstance(dm1, torch.Tensor) or tuple(dm1.shape) != (G, N, N):
+        raise ValueError(f"dm1 has shape {tuple(getattr(dm1, 'shape', ()))}, expected {(G, N, N)}")
+    device = _lib.require_device()
+    return point_charge_gradient_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(q).to(device),
+                                      torch.as_tensor(r / BOHR).to(device), dm1, nuc)
+
+
 def sym_invsqrt_batch(S, out=None):
     """``S^-1/2`` (symmetric principal root) of a stack [G, n, n] of symmetric positive definite device matrices ->
     (X [G, n, n], info [G] int32 on the device: 0, or -1 where S has an eigenvalue below ``INVSQRT_MIN_EIG`` -- that

@@ -769,6 +769,28 @@ int oovqe_gto_overlap_connection_batch(int nshell, const int32_t* shells, int np
                                        const double* coefs, int natm, const double* charges, int batch,
                                        const double* coords, int nao, int nset, const double* dm, double* out,
                                        double* work, oovqe_stream_t stream);
+/* Point-charge embedding (csrc/gto_charges.hip): every geometry has its own ncharge classical charges q [batch][ncharge]
+ * at qxyz [batch][ncharge][3] (Bohr), 1 <= ncharge <= 65535, batch <= 65535; the other arguments are those of
+ * oovqe_gto_gradient_batch.  Charges may lie anywhere (on a nucleus, on a Gaussian product centre); q, qxyz and coords
+ * are taken as finite.
+ *   vext[g][mu][nu] = - sum_k q[g][k] <mu| 1 / |r - qxyz[g][k]| |nu>     (s, p, d shells, both d forms; exactly
+ * symmetric; work: oovqe_gto_work_size doubles);
+ *   grad_atoms[g][A][:] = sum d1[g] . d vext[g] / dR_A,  grad_charges[g][k][:] = sum d1[g] . d vext[g] / d qxyz[g][k]
+ * for a symmetric d1 [batch][nao][nao] (read as oovqe_gto_gradient_batch reads it), s and p shells only (a table with
+ * l = 2 is refused before any launch); with_nuc adds the derivatives of sum_{A,k} Z_A q_k / |R_A - r_k| to both (a
+ * charge ON a nucleus then gives NaN).  There is no charge-charge term.  No floating-point atomics, fixed orders of
+ * summation: a geometry has the same bits wherever it stands in the stack.  work:
+ * oovqe_gto_point_charge_gradient_work_size(...) doubles = the pair data + batch x ceil(ncharge / 64) x natm x 3. */
+int oovqe_gto_point_charge_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                 const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                                 int nao, int ncharge, const double* q, const double* qxyz, double* vext, double* work,
+                                 oovqe_stream_t stream);
+int64_t oovqe_gto_point_charge_gradient_work_size(int nshell, int max_nprim, int natm, int batch, int ncharge);
+int oovqe_gto_point_charge_gradient_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                          const double* coefs, int natm, const double* charges, int batch,
+                                          const double* coords, int nao, int ncharge, const double* q,
+                                          const double* qxyz, const double* d1, int with_nuc, double* grad_atoms,
+                                          double* grad_charges, double* work, oovqe_stream_t stream);
 /* AO densities of a CAS wave function for the calls above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
  * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
  * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
