@@ -270,6 +270,16 @@ SIGNATURES = {
     "oovqe_rhf_batch": (ctypes.c_int, [c_double_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_double,
                                                                               ctypes.c_int] + [c_double_p] * 5
                         + [c_int32_p, c_int32_p, c_double_p, ctypes.c_void_p, c_stream]),
+    "oovqe_fock_jk_sets_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                c_double_p, c_double_p, c_stream]),
+    "oovqe_zvector_work_size": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "oovqe_zvector_solve_batch": (ctypes.c_int, [c_double_p] * 3 + [ctypes.c_int] * 4 + [c_double_p, ctypes.c_double,
+                                                                                        ctypes.c_int, c_double_p,
+                                                                                        c_double_p, c_int32_p, c_int32_p,
+                                                                                        c_double_p, ctypes.c_void_p,
+                                                                                        c_stream]),
+    "oovqe_response_d2_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p,
+                                               ctypes.c_int64, c_stream]),
     "oovqe_spin_rdms": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                        c_double_p, c_stream]),
     "oovqe_debug_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),

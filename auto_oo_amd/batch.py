@@ -32,6 +32,8 @@ F64 = torch.float64
 
 CASCIGradients = namedtuple("CASCIGradients", "energies ci gradients")
 CASCICouplings = namedtuple("CASCICouplings", "energies ci gradients couplings ci_term orbital_term")
+CASCIRelaxedGradients = namedtuple("CASCIRelaxedGradients",
+                                   "energies ci gradients fixed_orbital z_info charge_gradients")
 
 
 def _host_point_charges(basis, coords, point_charges):
@@ -417,10 +419,17 @@ class OO_pqc_batch:
         sel = torch.as_tensor(rows, device=self.device)
         return CASCIGradients(e[sel], vecs[sel], out)
 
-    def _casci_gradient_pass(self, who, nroots, fix_singlet, index, chunk, tol, max_iter, after_solve=None):
+    def _casci_gradient_pass(self, who, nroots, fix_singlet, index, chunk, tol, max_iter, after_solve=None,
+                             interstate=True, relax=None):
         """The body of ``casci_nuclear_gradients`` -> (rows, energies [G, R], ci [G, R, Dc] of the WHOLE stack, gradients
         [len(rows), R, R, natm, 3]).  ``after_solve(rows, energies)`` is called between the CASCI solve and the pass over
-        the derivative integrals (what it raises leaves before that pass)."""
+        the derivative integrals (what it raises leaves before that pass).  ``interstate=False`` leaves the pair sets
+        out (the off-diagonal elements of the result are then not filled).  ``relax(rows, fock [G, R, N, N])``, called
+        once after the Fock matrices are made, returns the function ``per_chunk(k0, sel, d1, d2, wq, out)`` that is
+        given the fixed-orbital densities of the R states of the chunk ``sel = rows[k0:k0 + c]`` and the place ``out``
+        [c, R, N, N, N, N] for R more two-particle densities, and returns their (D1, WQ) [c, R, N, N]: the R extra sets
+        ride in the same pass over the derivative integrals, as states, and a fifth value is returned: ``(gradients of
+        the extra sets [len(rows), R, natm, 3], their point_charge_gradient [len(rows), R, M, 3] or None)``."""
         from . import ci
         rows = self._gradient_rows(index, who)
         if self.ncas > nucgrad.MAX_NCAS:
@@ -430,18 +439,26 @@ class OO_pqc_batch:
         if after_solve is not None:
             after_solve(rows, e)
         G, R, a, N, natm = self.G, int(nroots), self.ncas, self.nao, self.basis.natm
-        pairs = nucgrad.state_pairs(R)
+        pairs = nucgrad.state_pairs(R) if interstate else []
         P = len(pairs)
         n, K = R + 2 * P, R + P
+        X = 0 if relax is None else R                          # extra sets
+        if K + X > GTO.MAX_GRAD_SETS:
+            raise ValueError(f"{who}: {K + X} density sets per geometry (1 .. {GTO.MAX_GRAD_SETS})")
         # RDMs and generalised Fock matrices of the R states and the 2 P polarisation vectors, whole stack
-        stack = nucgrad.polarisation_vectors(vecs)
+        stack = nucgrad.polarisation_vectors(vecs) if interstate else vecs
         gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
         gamma = gamma.reshape(G, n, a, a)
         Gamma = Gamma.reshape((G, n) + (a,) * 4)
         fock = torch.empty((G, n, N, N), dtype=F64, device=self.device)
         for s in range(n):      # (the CAS path takes the RDMs of set 0 for the Fock matrix: one call per vector)
             fock[:, s] = self._cas_batch(gamma[:, s:s + 1], Gamma[:, s:s + 1], G, want_fock=True)[2]
-        fock = nucgrad.transition_sets(fock, R)
+        fock = nucgrad.transition_sets(fock, R) if interstate else fock
+        per_chunk = None if relax is None else relax(rows, fock[:, :R])
+        extra = torch.empty((len(rows), X, natm, 3), dtype=F64, device=self.device)
+        extra_q = None
+        if X and self.charge_q is not None:
+            extra_q = torch.empty((len(rows), X, int(self.charge_q.shape[1]), 3), dtype=F64, device=self.device)
         step = len(rows) if chunk is None else max(1, int(chunk))
         out = torch.empty((len(rows), R, R, natm, 3), dtype=F64, device=self.device)
         k = torch.arange(R, device=self.device)
@@ -453,9 +470,9 @@ class OO_pqc_batch:
             C = self.mo_coeff[sel]
             d1 = nucgrad.transition_sets(
                 nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel], Gamma[sel], want_d2=False)[0], R)
-            buf = self._dm2_buffer(c * (K + 2))
-            d2 = buf[:c * K].view((c, K) + (N,) * 4)
-            tmp = buf[c * K:c * (K + 2)]
+            buf = self._dm2_buffer(c * (K + X + 2))
+            d2 = buf[:c * (K + X)].view((c, K + X) + (N,) * 4)
+            tmp = buf[c * (K + X):c * (K + X + 2)]
             for s in range(R):
                 t = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel, s], Gamma[sel, s], out=tmp)[1]
                 d2[:, s].copy_(t)
@@ -464,18 +481,31 @@ class OO_pqc_batch:
                 t = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel][:, pm], Gamma[sel][:, pm], out=tmp)[1]
                 d2[:, R + p].copy_(t[:, 0].sub_(t[:, 1]).mul_(0.5))
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
-            val = GTO.gradient_sets_into(self.basis, self.coords_bohr[sel], d1, wq, d2, [True] * R + [False] * P)
+            if per_chunk is not None:
+                more = per_chunk(k0, sel, d1[:, :R], d2[:, :R], wq[:, :R], d2[:, K:])
+                d1, wq = torch.cat((d1, more[0]), dim=1), torch.cat((wq, more[1]), dim=1)
+            val = GTO.gradient_sets_into(self.basis, self.coords_bohr[sel], d1, wq, d2,
+                                         [True] * R + [False] * P + [True] * X)
             if self.charge_q is not None:
                 # the charges' pull on the atoms, one pass per set: with the nuclei's term for a state, without it
                 # for a transition density
                 for s in range(K):
                     val[:, s] += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
                                                                 self.charge_xyz_bohr[sel], d1[:, s], s < R)[0]
+            extra[k0:k0 + c] = val[:, K:]
+            if extra_q is not None:
+                for s in range(X):
+                    pull = GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                                          self.charge_xyz_bohr[sel], d1[:, K + s], True)
+                    extra[k0:k0 + c, s] += pull[0]
+                    extra_q[k0:k0 + c, s] = pull[1]
             blk = out[k0:k0 + c]
             blk[:, k, k] = val[:, :R]
             if P:
-                blk[:, ii, jj] = val[:, R:]
-                blk[:, jj, ii] = val[:, R:]
+                blk[:, ii, jj] = val[:, R:K]
+                blk[:, jj, ii] = val[:, R:K]
+        if relax is not None:
+            return rows, e, vecs, out, (extra, extra_q)
         return rows, e, vecs, out
 
     def casci_derivative_couplings(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200,
@@ -557,6 +587,104 @@ class OO_pqc_batch:
             ci_term[:, ii, jj] = cval
             ci_term[:, jj, ii] = -cval
         return CASCICouplings(e, vecs, grads, ci_term + orb, ci_term, orb)
+
+    def casci_relaxed_gradients(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200,
+                                z_tol=1e-10, z_max_iter=100, brillouin_tol=1e-8, min_gap=1e-6, small_gap="raise"):
+        """CASCI states of every geometry on its canonical RHF orbitals with their ORBITAL-RELAXED nuclear gradients:
+        the slope of the surface ``E_I(R)`` on which the orbitals are re-made by RHF at every geometry (``from_geometries(
+        ..., oao_mo_coeffs="rhf")``), which ``casci_nuclear_gradients`` -- the derivative at fixed ``oao_mo_coeff`` --
+        is not: a CASCI energy is not stationary with respect to the orbitals.  -> ``CASCIRelaxedGradients(energies
+        [G', R], ci [G', R, Dc], gradients [G', R, natm, 3], fixed_orbital [G', R, natm, 3], z_info [G', R],
+        charge_gradients [G', R, M, 3] or None)`` on the device, Hartree / Bohr.
+
+        ``gradients`` is the derivative at fixed ``oao_mo_coeff`` of the Lagrangian ``E_I - sum_{p>q} z_pq f_pq`` (``f``
+        the RHF Fock matrix in the MO basis, whose off-diagonal elements vanish at every geometry): one Z-vector solve
+        per state (``nucgrad.zvector``: conjugate gradients on the device to a residual ``z_tol``, at most
+        ``z_max_iter`` iterations), three corrected densities (``nucgrad.relaxed_densities``) and the same single pass
+        over the derivative integrals that gives ``fixed_orbital`` -- the diagonal of what ``casci_nuclear_gradients``
+        returns, bit for bit.  For an embedded batch the charges' pull on the atoms uses the relaxed one-particle
+        density, and ``charge_gradients`` is the relaxed derivative with respect to the charges' positions.
+
+        - The orbitals must be the canonical RHF orbitals of their geometry, wherever they came from: ``f = C^T (h +
+          G[D0]) C`` is formed from the batch's own orbitals and a geometry whose largest off-diagonal ``|f_pq|`` exceeds
+          ``brillouin_tol`` raises ValueError.  The Fermi level must lie inside the active space.
+        - A core / active-occupied or active-virtual / external pair of orbitals closer in energy than ``min_gap`` makes
+          the response diverge: ``small_gap="raise"``: ValueError naming the geometries and pairs, before the CASCI
+          solve; ``"nan"``: NaN in ``gradients`` (and ``charge_gradients``) for the states of those geometries only and
+          ``z_info = -4`` there, ``fixed_orbital`` still filled.
+        - Any other ``z_info != 0`` (``nucgrad.Z_INFO``) raises ``OovqeError`` naming geometry, state and code.
+
+        ``index``, ``chunk``, the other arguments, the scope and the errors are those of ``casci_nuclear_gradients``; the
+        same bits whatever ``index``, ``chunk`` and the stack around a geometry.  Not covered: relaxed interstate
+        elements and derivative couplings, orbitals other than RHF orbitals, d shells."""
+        from . import ci
+        who = "casci_relaxed_gradients"
+        if small_gap not in ("raise", "nan"):
+            raise ValueError(f"small_gap = {small_gap!r} ('raise' or 'nan')")
+        rows = self._gradient_rows(index, who)
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"{who} covers ncas <= {nucgrad.MAX_NCAS}")
+        ci.check_scope(self.ncas, self.nelecas, nroots)
+        scf.check_scope(self.nao, nelectron=self.nelectron)
+        R, a, N, n_core, n_occ = int(nroots), self.ncas, self.nao, self._n_occ, self.nelectron // 2
+        _, dg = nucgrad.response_pairs(N, n_core, a, n_occ)
+        if rows == list(range(rows[0], rows[0] + len(rows))):
+            take = slice(rows[0], rows[0] + len(rows))                # (a view: no copy of the integrals)
+        else:
+            take = torch.as_tensor(rows, device=self.device)
+        # the RHF Fock matrix of the batch's own orbitals: canonical? gaps?
+        g, h, C = self.int2e_ao[take], self.int1e_ao[take], self.mo_coeff[take].contiguous()
+        mm = ops.matmul_nn_batch
+        Co = C[:, :, :n_occ].contiguous()
+        D0 = 2.0 * mm(Co, Co.transpose(1, 2).contiguous())
+        J0, K0 = scf.fock_jk(g, D0)
+        fock_ao = h + J0 - 0.5 * K0
+        f = mm(mm(C.transpose(1, 2).contiguous(), fock_ao), C)
+        eps = torch.diagonal(f, dim1=1, dim2=2).contiguous()
+        off = (f - torch.diag_embed(eps)).abs().flatten(1).amax(dim=1).cpu().numpy()
+        bad = [(r, float(x)) for r, x in zip(rows, off) if not x <= float(brillouin_tol)]
+        if bad:
+            raise ValueError(f"{who}: the orbitals are not canonical RHF orbitals (largest off-diagonal |f_pq| > "
+                             f"{float(brillouin_tol):g}) for geometries " + ", ".join(f"{r} ({x:.3g})" for r, x in bad))
+        eh = eps.cpu().numpy()
+        pq = np.argwhere(dg)
+        close = [(r, int(p), int(q)) for k, r in enumerate(rows) for p, q in pq
+                 if abs(eh[k, p] - eh[k, q]) < float(min_gap)]
+        if close and small_gap == "raise":
+            raise ValueError(f"{who}: |eps_p - eps_q| < {float(min_gap):g} Ha for (geometry, p, q) = "
+                             + ", ".join(str(c) for c in close) + ": the orbital response diverges there "
+                             "(small_gap='nan' marks the states of these geometries instead)")
+        state = {}
+
+        def relax(rows_, fock):
+            w = nucgrad.orbital_gradient(fock[take])
+            res = nucgrad.zvector(g, C, eps, n_core, a, n_occ, w, z_tol, z_max_iter, min_gap)
+            codes = res.info.cpu().numpy()
+            wrong = [(r, i, int(codes[k, i])) for k, r in enumerate(rows_) for i in range(R) if codes[k, i] not in (0, -4)]
+            if wrong:
+                raise _lib.OovqeError(f"{who}: the Z-vector solve failed for (geometry, state: code) = " + ", ".join(
+                    f"({r}, {i}: {c} {nucgrad.Z_INFO.get(c, '')})" for r, i, c in wrong))
+            state["info"] = res.info
+            z = torch.where((res.info == -4)[:, :, None, None], torch.zeros_like(res.z), res.z)
+
+            def per_chunk(k0, sel, d1, d2, wq, out):
+                c = len(sel)
+                out.copy_(d2)
+                d1r, _, wqr = nucgrad.relaxed_densities(h[k0:k0 + c], g[k0:k0 + c], self.overlap[sel],
+                                                        self.oao_mo_coeff[sel], C[k0:k0 + c], n_occ, z[k0:k0 + c], d1,
+                                                        out, wq, fock_ao=fock_ao[k0:k0 + c])
+                return d1r, wqr
+            return per_chunk
+
+        rows, e, vecs, out, (grad, grad_q) = self._casci_gradient_pass(who, nroots, fix_singlet, index, chunk, tol,
+                                                                       max_iter, interstate=False, relax=relax)
+        sel = torch.as_tensor(rows, device=self.device)
+        k = torch.arange(R, device=self.device)
+        marked = (state["info"] == -4)[:, :, None, None]
+        grad = torch.where(marked, torch.full_like(grad, float("nan")), grad)
+        if grad_q is not None:
+            grad_q = torch.where(marked, torch.full_like(grad_q, float("nan")), grad_q)
+        return CASCIRelaxedGradients(e[sel], vecs[sel], grad, out[:, k, k], state["info"], grad_q)
 
     def rhf_nuclear_gradient(self, result=None, index=None):
         """Closed-shell Hartree-Fock gradient -> [G, natm, 3] (device, Hartree / Bohr) from a converged

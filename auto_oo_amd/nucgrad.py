@@ -12,6 +12,9 @@ exact at any circuit parameters and any ``U``, converged or not; the contraction
 energy-weighted density, which is what ``rhf_gradient`` uses.  The functions ending in ``_host`` are numpy twins of
 the device helpers (the oracle of the tests; the product path never calls them).
 """
+import ctypes
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -182,6 +185,152 @@ def branching_plane(result, i, j):
     return 0.5 * (grads[:, j, j] - grads[:, i, i]), grads[:, i, j]
 
 
+# ---- orbital response of CASCI states on canonical RHF orbitals (auto_oo_amd/csrc/zvector.hip) ------------------------
+ZVector = namedtuple("ZVector", "z info iterations residual")
+Z_INFO = {1: "max_iter reached", -2: "p^T A p <= 0: unstable RHF solution", -3: "NaN or Inf in the inputs",
+          -4: "orbital-energy gap below min_gap"}
+
+
+def orbital_gradient(fock):
+    """``w_pq = dE/dkappa_pq = 2 (F_qp - F_pq)``, p > q, of the rotation ``C exp(kappa)`` from the generalised Fock
+    matrix ``F`` [..., N, N] of the CAS path (``dE/dC = C^-T 2 F^T``) -> [..., N, N], the strictly lower triangle
+    filled."""
+    return torch.tril(2.0 * (fock.transpose(-1, -2) - fock), -1).contiguous()
+
+
+def _per_set(x, K):
+    """[G, N, M] -> [G K, N, M]: a geometry's matrix repeated for its K sets."""
+    G = int(x.shape[0])
+    return x[:, None].expand((G, K) + tuple(x.shape[1:])).reshape((G * K,) + tuple(x.shape[1:])).contiguous()
+
+
+def _mo_to_ao(C, m):
+    """``C m C^T`` for C [G, N, N], m [G, K, N, N] -> [G, K, N, N]"""
+    G, K, N = int(m.shape[0]), int(m.shape[1]), int(m.shape[-1])
+    Ck = _per_set(C, K)
+    return ops.matmul_nn_batch(ops.matmul_nn_batch(Ck, m.reshape(G * K, N, N).contiguous()), _t(Ck)).view(G, K, N, N)
+
+
+def _g_sets(int2e, dms):
+    J, K = scf.fock_jk_sets(int2e, dms)
+    return J - 0.5 * K
+
+
+def zvector(int2e, mo_coeff, mo_energy, n_core, ncas, n_occ, w, tol=1e-10, max_iter=100, min_gap=1e-6):
+    """The Z-vector of K states per geometry: ``L^T z = w`` over the orbital pairs of ``response_pairs`` (see
+    ``zvector_host``), for canonical RHF orbitals ``mo_coeff`` [G, N, N] with energies ``mo_energy`` [G, N] (``n_occ``
+    doubly occupied; the CASCI has ``n_core`` inactive and ``ncas`` active orbitals), the integrals ``int2e`` and the
+    orbital gradients ``w`` [G, K, N, N] of ``orbital_gradient``.  Block elimination: the pairs inside occ-occ and
+    virt-virt are ``z_pq = w_pq / (eps_p - eps_q)``; their density ``Z_d = C zt_d C^T`` (``zt`` symmetric, ``zt_pq =
+    z_pq / 2``) gives the right-hand side ``b_ai = w_ai - 4 [C^T G[Z_d] C]_ai`` of the symmetric virt-occ system,
+    which ``oovqe_zvector_solve_batch`` solves by preconditioned conjugate gradients to a residual 2-norm ``tol``.
+
+    -> ``ZVector(z [G, K, N, N] (strictly lower triangle), info [G, K], iterations [G, K], residual [G, K])`` on the
+    device.  ``info``: 0, or a key of ``Z_INFO``; -4 marks every state of a geometry with a pair of step one closer
+    than ``min_gap``.  ``z`` of a state with a negative code is NaN; nothing is read back."""
+    if w.dim() != 4:
+        raise ValueError(f"w has shape {tuple(w.shape)}, expected [G, K, N, N]")
+    G, K, N = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
+    vo, dg = response_pairs(N, n_core, ncas, n_occ)
+    if tuple(mo_coeff.shape) != (G, N, N) or tuple(mo_energy.shape) != (G, N):
+        raise ValueError(f"mo_coeff of shape {tuple(mo_coeff.shape)}, mo_energy of shape {tuple(mo_energy.shape)}: "
+                         f"expected {(G, N, N)}, {(G, N)}")
+    if not (tol > 0 and int(max_iter) >= 1):
+        raise ValueError(f"tol = {tol}, max_iter = {max_iter}")
+    lib = _lib.load()
+    dev = _lib.require_device()
+    C, eps, w = mo_coeff.contiguous(), mo_energy.contiguous(), w.contiguous()
+    no, nv = int(n_occ), N - int(n_occ)
+    # pairs inside occ-occ and virt-virt
+    delta = (eps[:, :, None] - eps[:, None, :])[:, None]
+    mask = torch.as_tensor(dg, device=dev)
+    small = ((delta.abs() < float(min_gap)) & mask).flatten(1).any(dim=1)               # [G]
+    use = mask & ~small[:, None, None, None]
+    zd = torch.where(use, w / torch.where(use, delta, torch.ones_like(delta)), torch.zeros_like(w))
+    # right-hand side of the virt-occ block
+    Zd = _mo_to_ao(C, 0.5 * (zd + zd.transpose(2, 3)))
+    Ck = _per_set(C, K)
+    gz = ops.matmul_nn_batch(ops.matmul_nn_batch(_t(Ck), _g_sets(int2e, Zd).reshape(G * K, N, N)), Ck).view(G, K, N, N)
+    b = (w - 4.0 * gz)[:, :, no:, :no].contiguous()
+    size = int(lib.oovqe_zvector_work_size(N, no, K, G))
+    if size < 0:
+        check(size, "oovqe_zvector_work_size")
+    work = torch.empty(size, dtype=F64, device=dev)
+    zvo = torch.empty((G, K, nv, no), dtype=F64, device=dev)
+    resid = torch.empty((G, K), dtype=F64, device=dev)
+    iters = torch.empty((G, K), dtype=torch.int32, device=dev)
+    info = torch.empty((G, K), dtype=torch.int32, device=dev)
+    verdict = scf._verdict_words(dev)
+    check(lib.oovqe_zvector_solve_batch(dptr(int2e.contiguous()), dptr(C), dptr(eps), N, no, K, G, dptr(b), float(tol),
+                                        int(max_iter), dptr(zvo), dptr(resid), dptr(iters, torch.int32),
+                                        dptr(info, torch.int32), dptr(work), ctypes.c_void_p(verdict.data_ptr()),
+                                        stream_ptr()), "oovqe_zvector_solve_batch")
+    z = zd
+    z[:, :, no:, :no] = zvo
+    nan = torch.full_like(z, float("nan"))
+    info = torch.where(small[:, None], torch.full_like(info, -4), info)
+    z = torch.where((info < 0)[:, :, None, None], nan, z)
+    return ZVector(z, info, iters, resid)
+
+
+def response_d2(Z, D0, d2):
+    """``d2 -= sym8[2 Z_pq D0_rs - Z_pr D0_qs]`` in place for symmetric ``Z``, ``D0`` [rows, N, N] and an 8-fold
+    symmetric ``d2`` [rows, N, N, N, N] (``oovqe_response_d2_batch``) -> ``d2``.  Each ``d2[row]`` must be contiguous;
+    the rows may lie any distance apart (a view ``x[:, k]`` of a [rows, K, N, N, N, N] tensor serves)."""
+    rows, N = int(d2.shape[0]), int(d2.shape[-1])
+    if tuple(d2.shape) != (rows,) + (N,) * 4 or tuple(Z.shape) != (rows, N, N) or tuple(D0.shape) != (rows, N, N):
+        raise ValueError(f"Z, D0, d2 of shapes {tuple(Z.shape)}, {tuple(D0.shape)}, {tuple(d2.shape)}: expected "
+                         "[rows, N, N] twice and [rows, N, N, N, N]")
+    if tuple(d2.stride()[1:]) != (N ** 3, N ** 2, N, 1) or (rows > 1 and d2.stride(0) < N ** 4) or not d2.is_cuda \
+            or d2.dtype != F64:
+        raise ValueError("every d2[row] must be a contiguous float64 device tensor: it is changed in place")
+    lib = _lib.load()
+    _lib.require_device()
+    stride = N ** 4 if rows <= 1 else int(d2.stride(0))
+    check(lib.oovqe_response_d2_batch(dptr(Z.contiguous()), dptr(D0.contiguous()), N, rows,
+                                      ctypes.c_void_p(d2.data_ptr()), stride, stream_ptr()), "oovqe_response_d2_batch")
+    return d2
+
+
+def relaxed_densities(int1e, int2e, overlap, oao_mo_coeff, mo_coeff, n_occ, z, d1, d2, wq, fock_ao=None):
+    """The densities of ``E_I - sum_{p>q} z_pq f_pq`` (``f = C^T (h + G[D0]) C`` the RHF Fock matrix, whose off-diagonal
+    elements vanish at every geometry) from those of ``E_I``, K states per geometry: with ``zt`` the symmetric matrix
+    ``zt_pq = z_pq / 2``, ``Z = C zt C^T`` and ``D0 = 2 C_o C_o^T``
+
+        D1_rel = D1 - Z,   D2_rel = D2 - sym8[2 Z_pq D0_rs - Z_pr D0_qs],   WQ_rel = WQ - pull_back(sym(dPhi/dC U^T)),
+        dPhi/dC = 2 (h + G[D0]) C zt, plus 4 G[Z] C_o on the occupied columns.
+
+    ``z``, ``d1``, ``wq`` [G, K, N, N]; ``d2`` [G, K, N, N, N, N] (every ``d2[g, k]`` contiguous), CHANGED IN PLACE; ``fock_ao`` = ``h +
+    G[D0]`` [G, N, N] when the caller has it.  -> (D1_rel, D2_rel (``d2`` itself), WQ_rel)."""
+    G, K, N = int(z.shape[0]), int(z.shape[1]), int(z.shape[-1])
+    mm = ops.matmul_nn_batch
+    C = mo_coeff.contiguous()
+    Co = C[:, :, :n_occ].contiguous()
+    D0 = 2.0 * mm(Co, _t(Co))
+    D0 = (0.5 * (D0 + D0.transpose(1, 2))).contiguous()
+    if fock_ao is None:
+        J0, K0 = scf.fock_jk(int2e, D0)
+        fock_ao = int1e + J0 - 0.5 * K0
+    zt = (0.5 * (z + z.transpose(2, 3))).reshape(G * K, N, N).contiguous()
+    Ck = _per_set(C, K)
+    Czt = mm(Ck, zt)
+    Z = mm(Czt, _t(Ck))
+    Z = (0.5 * (Z + Z.transpose(1, 2))).contiguous()
+    dphi = 2.0 * mm(_per_set(fock_ao, K), Czt)
+    gz = _g_sets(int2e, Z.view(G, K, N, N)).reshape(G * K, N, N)
+    dphi[:, :, :n_occ] += 4.0 * mm(gz, _per_set(Co, K))
+    U = _per_set(oao_mo_coeff, K)
+    gx = mm(dphi, _t(U))
+    gx = 0.5 * (gx + gx.transpose(1, 2))
+    sw, V, _ = scf.sym_eigh_batch(overlap.contiguous())
+    sq, V = _per_set(torch.sqrt(sw), K), _per_set(V, K)
+    wq_rel = wq - _pull_back(gx, sq, V, _t(V)).view(G, K, N, N)
+    Zs = Z.view(G, K, N, N)
+    for k in range(K):
+        response_d2(Zs[:, k], D0, d2[:, k])
+    return d1 - Z.view(G, K, N, N), d2, wq_rel
+
+
 # ---- numpy twins (tests) ----------------------------------------------------------------------------------------------
 def sym8_host(t):
     """Average of a [N, N, N, N] array over the 8 index permutations of (pq|rs)."""
@@ -222,3 +371,99 @@ def connection_pullback_host(overlap, oao_mo_coeff, a):
     U = np.asarray(oao_mo_coeff)
     x_inv = (V * np.sqrt(s)) @ V.T
     return overlap_pullback_host(overlap, x_inv @ U @ np.asarray(a) @ U.T)
+
+
+# ---- orbital response of CASCI states on RHF orbitals: numpy twins (tests) ----------------------------------------------
+def _g_host(int2e, dm):
+    """``G[D] = J[D] - K[D] / 2`` on the host."""
+    return np.einsum("pqrs,rs->pq", int2e, dm) - 0.5 * np.einsum("prqs,rs->pq", int2e, dm)
+
+
+def generalised_fock_host(int1e, int2e, overlap, mo_coeff, d1, d2):
+    """The generalised Fock matrix ``F`` (MO basis, ``dE/dC = C^-T 2 F^T``) of a wave function with the AO densities
+    ``d1``, ``d2`` of ``cas_ao_densities_host``: ``F^T = C^T (h D1 + T) S C``, ``T_mn = sum g_mlrs D2_nlrs``."""
+    C = np.asarray(mo_coeff)
+    y = C.T @ (np.asarray(int1e) @ d1 + np.einsum("mlrs,nlrs->mn", int2e, d2)) @ np.asarray(overlap) @ C
+    return y.T
+
+
+def orbital_gradient_host(fock):
+    """numpy twin of ``orbital_gradient``."""
+    F = np.asarray(fock)
+    return np.tril(2.0 * (F.T - F), -1)
+
+
+def response_pairs(n, n_core, ncas, n_occ):
+    """The pairs p > q of ``n`` canonical RHF orbitals (``n_occ`` doubly occupied) that carry an orbital response of a
+    CASCI with ``n_core`` inactive and ``ncas`` active orbitals -> boolean [n, n] masks ``(vo, diag)``: the virt-occ
+    block, and the pairs inside occ-occ and virt-virt that join two classes (core x active-occupied, active-virtual x
+    external).  The CASCI energy does not change under a rotation inside a class."""
+    n, n_core, ncas, n_occ = int(n), int(n_core), int(ncas), int(n_occ)
+    if not 0 <= n_core <= n_occ <= n_core + ncas <= n or not 0 < n_occ < n:
+        raise ValueError(f"n = {n}, n_core = {n_core}, ncas = {ncas}, n_occ = {n_occ}: the Fermi level must lie inside "
+                         "the active space, 0 <= n_core <= n_occ <= n_core + ncas <= n, 0 < n_occ < n")
+    vo = np.zeros((n, n), dtype=bool)
+    vo[n_occ:, :n_occ] = True
+    diag = np.zeros((n, n), dtype=bool)
+    diag[n_core:n_occ, :n_core] = True
+    diag[n_core + ncas:, n_occ:n_core + ncas] = True
+    return vo, diag
+
+
+def zvector_host(int2e, mo_coeff, mo_energy, n_core, ncas, n_occ, w, eliminate=False):
+    """numpy twin of ``zvector`` for ONE geometry and ONE state: ``z`` [N, N] (strictly lower triangle) with ``L^T z =
+    w`` over the pairs of ``response_pairs``, ``(L kappa)_pq = (eps_p - eps_q) kappa_pq + [C^T G[dD(kappa)] C]_pq``,
+    ``dD(kappa) = C (kappa n - n kappa) C^T``, ``n = diag(2 .. 2, 0 .. 0)``: the explicit matrix and a dense solve.
+    ``eliminate``: the block elimination the device runs instead (the occ-occ and virt-virt pairs first, then the
+    symmetric virt-occ system ``A z_vo = b``, dense) -> ``(z, A, b)``."""
+    C, eps, w = np.asarray(mo_coeff), np.asarray(mo_energy), np.asarray(w)
+    N = C.shape[0]
+    vo, dg = response_pairs(N, n_core, ncas, n_occ)
+    occ = np.zeros(N)
+    occ[:n_occ] = 2.0
+    delta = eps[:, None] - eps[None, :]
+
+    def apply(kappa):
+        dD = C @ (kappa * occ[None, :] - occ[:, None] * kappa) @ C.T
+        return delta * kappa + C.T @ _g_host(int2e, dD) @ C
+
+    def unit(p, q):
+        k = np.zeros((N, N))
+        k[p, q], k[q, p] = 1.0, -1.0
+        return k
+
+    z = np.zeros((N, N))
+    if not eliminate:
+        idx = np.argwhere(vo | dg)
+        L = np.stack([apply(unit(p, q))[idx[:, 0], idx[:, 1]] for p, q in idx], axis=1)
+        z[idx[:, 0], idx[:, 1]] = np.linalg.solve(L.T, w[idx[:, 0], idx[:, 1]])
+        return z
+    z[dg] = w[dg] / delta[dg]
+    zt = 0.5 * (z + z.T)
+    nv = N - n_occ
+    b = (w - 4.0 * C.T @ _g_host(int2e, C @ zt @ C.T) @ C)[n_occ:, :n_occ]
+    idx = np.argwhere(vo)
+    A = np.stack([apply(unit(p, q))[vo] for p, q in idx], axis=1)
+    z[n_occ:, :n_occ] = np.linalg.solve(A, b.reshape(-1)).reshape(nv, n_occ)
+    return z, A, b
+
+
+def response_d2_host(Z, D0):
+    """``sym8[2 Z_pq D0_rs - Z_pr D0_qs]``: what the Lagrangian term ``sum z_pq f_pq`` adds to the AO two-particle
+    density (twin of ``response_d2``, which subtracts it)."""
+    return sym8_host(2.0 * np.einsum("pq,rs->pqrs", Z, D0) - np.einsum("pr,qs->pqrs", Z, D0))
+
+
+def relaxed_densities_host(int1e, int2e, overlap, mo_coeff, n_occ, z, d1, d2, wq):
+    """numpy twin of ``relaxed_densities`` for ONE geometry and ONE state: the densities of ``E_I - sum_{p>q} z_pq
+    f_pq`` at fixed ``U``, from those of ``E_I`` -> ``(D1_rel, D2_rel, WQ_rel)``."""
+    C, S = np.asarray(mo_coeff), np.asarray(overlap)
+    zt = 0.5 * (z + z.T)
+    Z = C @ zt @ C.T
+    Co = C[:, :n_occ]
+    D0 = 2.0 * Co @ Co.T
+    dphi = 2.0 * (np.asarray(int1e) + _g_host(int2e, D0)) @ C @ zt
+    dphi[:, :n_occ] += 4.0 * _g_host(int2e, Z) @ Co
+    s, V = np.linalg.eigh(S)
+    U = (V * np.sqrt(s)) @ V.T @ C                       # U = X^-1 C
+    return d1 - Z, d2 - response_d2_host(Z, D0), wq - overlap_pullback_host(S, dphi @ U.T)

@@ -16,6 +16,7 @@ from ._lib import check, dptr, stream_ptr
 
 F64 = torch.float64
 MAX_N = 64                      # OOVQE_INVSQRT_MAX_N
+MAX_SETS = 10                   # OOVQE_ZVECTOR_MAX_SETS
 
 _RHF_FIELDS = ("mo_coeff", "oao_mo_coeff", "mo_energy", "e_elec", "converged", "iterations", "diis_error", "info")
 
@@ -128,6 +129,32 @@ def fock_jk(int2e, dm):
     J, K = torch.empty_like(D), torch.empty_like(D)
     check(lib.oovqe_fock_jk_batch(dptr(g), dptr(D), n, int(D.shape[0]), dptr(J), dptr(K), stream_ptr()),
           "oovqe_fock_jk_batch")
+    return (J[0], K[0]) if single else (J, K)
+
+
+def fock_jk_sets(int2e, dms):
+    """``fock_jk`` for K densities per geometry in ONE pass over ``int2e``: ``dms`` [G, K, N, N] (or [K, N, N] with
+    ``int2e`` [N, N, N, N]), K = 1 .. ``MAX_SETS`` -> (J, K) of the shape of ``dms``.  A set has the same bits whatever
+    the stack, the other sets, their number and its place among them (``oovqe_fock_jk_sets_batch``)."""
+    if not isinstance(dms, torch.Tensor) or dms.dim() not in (3, 4):
+        raise TypeError("dms must be a torch tensor [G, K, N, N] or [K, N, N]")
+    n, nset = int(dms.shape[-1]), int(dms.shape[-3])
+    if not 1 <= n <= MAX_N:
+        raise ValueError(f"N = {n}: fock_jk_sets covers 1 .. {MAX_N}")
+    if not 1 <= nset <= MAX_SETS:
+        raise ValueError(f"{nset} densities per geometry (1 .. {MAX_SETS})")
+    if int(dms.shape[-2]) != n:
+        raise ValueError(f"dms has shape {tuple(dms.shape)}, expected [G, K, N, N] or [K, N, N]")
+    single = dms.dim() == 3
+    D = (dms[None] if single else dms).contiguous()
+    g = _stack("int2e", int2e, n, 4).contiguous()
+    if g.shape[0] != D.shape[0]:
+        raise ValueError("int2e and dms must hold the same number of geometries")
+    lib = _lib.load()
+    _lib.require_device()
+    J, K = torch.empty_like(D), torch.empty_like(D)
+    check(lib.oovqe_fock_jk_sets_batch(dptr(g), dptr(D), n, nset, int(D.shape[0]), dptr(J), dptr(K), stream_ptr()),
+          "oovqe_fock_jk_sets_batch")
     return (J[0], K[0]) if single else (J, K)
 
 

@@ -833,6 +833,35 @@ int oovqe_rhf_batch(const double* h, const double* g, const double* s, const dou
                     double* mo_energy, double* e_elec, double* diis_error, int32_t* iterations, int32_t* info,
                     double* work, int32_t* verdict_host, oovqe_stream_t stream);
 
+/* ---- orbital response of CASCI states on RHF orbitals (auto_oo_amd/csrc/zvector.hip) -------------------------------
+ * oovqe_fock_jk_batch for nset densities per geometry in ONE pass over g: d, j, k [batch][nset][n][n],
+ * 1 <= nset <= OOVQE_ZVECTOR_MAX_SETS.  A set has the same bits whatever the stack, the other sets of the call, their
+ * number and its place among them. */
+#define OOVQE_ZVECTOR_MAX_SETS 10
+int oovqe_fock_jk_sets_batch(const double* g, const double* d, int n, int nset, int batch, double* j, double* k,
+                             oovqe_stream_t stream);
+/* The Z-vector equations A z = b of nset right-hand sides per geometry, b and z [batch][nset][n - n_occ][n_occ]:
+ *   (A k)_ai = (eps_a - eps_i) k_ai + [C^T (J - K / 2)[dD(k)] C]_ai,  dD(k) = 2 (C_v k C_o^T + C_o k^T C_v^T)
+ * for canonical closed-shell orbitals mo_coeff [batch][n][n] (AO x MO, the first n_occ doubly occupied) with energies
+ * mo_energy [batch][n] and the integrals g [batch][n]^4, by conjugate gradients preconditioned with 1 / (eps_a - eps_i)
+ * from z = 0; a set has converged when the 2-norm of its residual b - A z is <= tol.  Every sum runs in a fixed order
+ * and a (geometry, set) has the same bits whatever the stack and the sets around it.  Outputs per (geometry, set), on
+ * the device: z, resid (the last residual norm), iterations (Fock contractions) and info: 0 converged, 1 max_iter
+ * reached (z is the last iterate), -2 p^T A p <= 0 or an occupied orbital not below a virtual one (the RHF solution is
+ * unstable), -3 NaN or Inf in the inputs; for a negative code z and resid are NaN and the other sets are unaffected.
+ * work: oovqe_zvector_work_size(...) doubles.  verdict_host: null, or two ints of pinned host memory through which the
+ * call watches the count of finished sets without draining the stream (as oovqe_rhf_batch). */
+int64_t oovqe_zvector_work_size(int n, int n_occ, int nset, int batch);
+int oovqe_zvector_solve_batch(const double* g, const double* mo_coeff, const double* mo_energy, int n, int n_occ,
+                              int nset, int batch, const double* b, double tol, int max_iter, double* z, double* resid,
+                              int32_t* iterations, int32_t* info, double* work, int32_t* verdict_host,
+                              oovqe_stream_t stream);
+/* d2[row] -= sym8[2 z_pq d0_rs - z_pr d0_qs] in place for symmetric z, d0 [rows][n][n] and 8-fold symmetric d2[row]
+ * [n]^4, row_stride >= n^4 doubles apart (sym8: the average over the 8 index permutations of (pq|rs)): the element of each canonical quadruple is
+ * read once and the result stored to its (up to 8) places, so the symmetry of the result is exact. */
+int oovqe_response_d2_batch(const double* z, const double* d0, int n, int64_t rows, double* d2, int64_t row_stride,
+                            oovqe_stream_t stream);
+
 /* ---- overlaps between the states of two geometries (gto_cross.hip, overlap.hip) -------------------------------------
  * AO overlap between two geometries: out[p][mu][nu] = <chi_mu at coords_a[p] | chi_nu at coords_b[p]> for npair pairs,
  * coords_a, coords_b [npair][natm][3] in Bohr, out [npair][nao][nao] (not symmetric: every one of the nshell^2 ordered
