@@ -2838,16 +2838,20 @@ void cas_final_kernel(const double* __restrict__ Fcol, const double* __restrict_
 // ------------------------------------------------------------------------------------------
 // The whole tail of a batched call in ONE workgroup per geometry ("tail" kernel; packed-triangle
 // path with p <-> q and r <-> s symmetric integrals, W = C^T h_ao left by the circuit launch):
-//   q -> x, p -> n   sym_gm_kernel's two MFMA steps, one 16-wide tile of (y <= z) at a time, the
-//                    result kept in LDS instead of written to memory -- and of g_mo[n, x, y, z] only
-//                    the entries stage 3 reads (tail_needed: 210 of 405 per n at M = 9, no = 6)
+//   q -> x           sym_gm_kernel's first MFMA step for the 16-wide tiles of (y <= z) back to back, no
+//                    barrier between them; of T3[p][x][yz] only the entries (x, yz) that stage 3 reads
+//                    of g_mo[n] (tail_needed: 210 of 405 at M = 9, no = 6) are stored, packed:
+//                    Gc[p][tab(x, yz)], 4 KS rows (rows p >= N zero) of pitch 16 (ceil(NC / 16) | 1)
+//   p -> n           its second step, once, over the ceil(NC / 16) column tiles of Gc: a wave reads the
+//                    4 KS rows of its tile, runs the chains of every 16-block of n and stores rows n of
+//                    the same columns over them (no other wave touches those columns)
 //   stage 3          cas_panel_kernel's arithmetic for every n of the geometry, Fock columns in LDS
 //   assembly         cas_final_kernel's
 // Every sum runs in the order of those kernels: the results are those of the three launches, bit
 // for bit.  It replaces sym_gm_kernel + cas_panel_kernel + cas_final_kernel (g_mo: 2 x 64 MB of
 // memory traffic at 256 geometries, three grids of short latency-bound workgroups) by one launch;
 // measured at N = 43, M = 9, 256 geometries: see DESIGN.md section 5.  KS is the kernel's own k-depth
-// (tail_depth: 11 steps and 44 rows of T3s for 41 <= N <= 44, else the ks of stage1_variant).
+// (tail_depth: 11 steps and 44 rows of Gc for 41 <= N <= 44, else the ks of stage1_variant).
 // ------------------------------------------------------------------------------------------
 constexpr int TAIL_THREADS = 512;
 
@@ -2860,6 +2864,9 @@ __host__ __device__ inline bool tail_needed(int x, int y, int z, int no)
     if (hi < no) return lo == hi || x == lo || x == hi;      // both core
     return x >= no || x == lo;                               // lo core, hi active
 }
+// row pitch of the packed array (doubles): the column tiles of NC kept entries, 16 mod 32 -- the operand reads of p -> n
+// (ds_read_b64, groups of 32 lanes = two rows x 16 columns) then meet 64 distinct banks
+__host__ __device__ inline int tail_pitch(int NC) { return 16 * (((NC + 15) / 16) | 1); }
 
 // OOVQE_TAIL_PROBE (measurement builds only, tools/tail_probe.py): every workgroup meets at a barrier at each phase
 // boundary and thread 0 stores the 100 MHz wall clock there; oovqe_tail_probe_read copies the readings out
@@ -2913,8 +2920,9 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         c2 += gi * out_stride;
         if (nuc_arr) nuc = nuc_arr[gi];
     }
-    double* Gc = lds;                                // [N][NC]   the kept entries of g_mo[n]
-    double* Cl = Gc + (size_t)N * NC;                // [N][M]    C[:, :M]
+    const int LDG = tail_pitch(NC), nct = (NC + 15) / 16;
+    double* Gc = lds;                                // [4 KS][LDG]  the kept entries of T3[p], then (rows n < N) of g_mo[n]
+    double* Cl = Gc + (size_t)4 * KS * LDG;          // [N][M]    C[:, :M]
     double* hn = Cl + (size_t)N * M;                 // [N][M]    h_mo
     double* FIn = hn + (size_t)N * M;                // [N][M]
     double* gml = FIn + (size_t)N * M;               // [nrdm][na2]
@@ -2924,29 +2932,16 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     int* wcnt = tab + M3;                            // [NW]
     int* krow = wcnt + NW;                           // [n_kappa]  kap_row
     int* kcol = krow + n_kappa;                      // [n_kappa]  kap_col
-    double* scr = Cp + N + (M3 + NW + 2 * n_kappa + 1) / 2;   // W [N][N], then T3s [4 KS][LDP], then Fcol, Epart, Ga, Dc
-    const int LDP = M * 16 + 8;
+    double* scr = Cp + N + (M3 + NW + 2 * n_kappa + 1) / 2;   // W [N][N] and tabp, then Fcol, Epart, Ga, Dc
+    int* tabp = reinterpret_cast<int*>(scr + (size_t)N * N);  // [M][ncol]  position in Gc[n] of (x, yz), yz = (y <= z)
 
-    // ---- q -> x, p -> n per tile of (y <= z) (sym_gm_kernel's arithmetic) ------------------------------
+    // ---- q -> x for the tiles of (y <= z) back to back (sym_gm_kernel's first step) ---------------------
     // A wave's rows p = wave + NW i of J come in groups of GR rows through two register sets in rotation: step
     // s = ty NG + g multiplies set s & 1 and at once reloads it with the rows of step s + 2, so the loads of a later
-    // group are in flight under every product, under the p -> n step of the tile and under the staging of the inputs
+    // group are in flight under every product, across the tile boundaries and under the staging of the inputs
     // below (the workgroup barriers wait for LDS only).  Rows p >= N are neither loaded (their loads go to a buffer of
-    // no bytes: no memory access) nor multiplied; their T3s rows are written as zeros.
+    // no bytes: no memory access) nor multiplied; their rows of Gc are written as zeros.
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    const __amdgpu_buffer_rsrc_t csrd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<double*>(C), 0, (int)((size_t)N * N * sizeof(double)), 0x00020000);
-    // the C^T operands of p -> n for every 16-block of n: the same for every tile
-    double cfa[NTN][KS];
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int pp = 4 * ks + lq, n = 16 * nt + lr;
-            const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
-                csrd, (pp < N && n < N) ? (unsigned)((pp * N + n) * (int)sizeof(double)) : 0x7fffffffu, 0, 0);
-            cfa[nt][ks] = __builtin_bit_cast(double, v);
-        }
     // byte offsets in a tile of J [tri][16] of the pair (p, q), q = 4 ks + lq: triangle row base(min) + max with
     // base(a) = a (2N - a + 1) / 2 - a.  q < p: colq[ks] + 128 p; else base(p) + lin0 + 512 ks (q >= N there meets
     // af = 0 and reads a later row or, past the end of the tile, the zero of the range check)
@@ -2994,8 +2989,8 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             }
         }
     };
-    double* T3s = scr;                               // [4 KS][LDP], rows p >= N are zero
-    auto mfma_group = [&](const double (&af)[KS], const double (&bf)[GR][KS], int g) {
+    // accumulator row j of a lane is (x = lq + 4 j, yz = 16 ty + lr): it goes to column tj[j] of row p of Gc, if kept
+    auto mfma_group = [&](const double (&af)[KS], const double (&bf)[GR][KS], const int (&tj)[4], int g) {
 #pragma unroll
         for (int r = 0; r < GR; ++r) {
             const int i = g * GR + r;
@@ -3011,10 +3006,10 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(af[ks], bf[r][ks], acc);
             }
-            double* row = T3s + (p * LDP + lq * 16 + lr);
+            double* row = Gc + p * LDG;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (lq + 4 * j < M) row[j * 64] = acc[j];
+                if (tj[j] >= 0) row[tj[j]] = acc[j];
         }
     };
     double bs[2][GR][KS];
@@ -3033,6 +3028,11 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     for (int idx = tid; idx < n_kappa; idx += TAIL_THREADS) {
         krow[idx] = kap_row[idx];
         kcol[idx] = kap_col[idx];
+    }
+    // the columns of Gc behind the kept ones: p -> n reads those of the last column tile
+    for (int idx = tid; idx < 4 * KS * (LDG - NC); idx += TAIL_THREADS) {
+        const int p = idx / (LDG - NC);
+        Gc[p * LDG + NC + (idx - p * (LDG - NC))] = 0.0;
     }
     TAIL_MARK(1);
     {
@@ -3061,6 +3061,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
                 const int v = need ? pre + below : -1;
                 tab[(x * M + y) * M + z] = v;
                 tab[(x * M + z) * M + y] = v;
+                tabp[i] = v;
             }
             __syncthreads();
             base += all;
@@ -3078,65 +3079,33 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     TAIL_MARK(3);
 
     {
-        const int ntn = (N + 15) / 16;
+        // the C operand of q -> x from the LDS copy, once: the same for every tile
+        double af[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int q = 4 * ks + lq;
+            const double c = Cl[(q < N ? q : N - 1) * M + (lr < M ? lr : 0)];
+            af[ks] = (q < N && lr < M) ? c : 0.0;
+        }
         // one tile; par = set of its first group (the parity of step ty NG)
         auto tail_tile = [&](auto par, int ty) {
             constexpr int P = decltype(par)::value;
-            // the C operand of q -> x from the LDS copy, tile by tile: its registers are free during p -> n
-            double af[KS];
-            int lqv = lq;                                               // (opaque: no address registers kept per k-step)
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+v"(lqv));
-#endif
+            // the packed columns of the lane's four accumulator rows: fixed for the tile
+            const int yz = 16 * ty + lr;
+            int tj[4];
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int q = 4 * ks + lqv;
-                const double c = Cl[(q < N ? q : N - 1) * M + (lr < M ? lr : 0)];
-                af[ks] = (q < N && lr < M) ? c : 0.0;
+            for (int j = 0; j < 4; ++j) {
+                const int x = lq + 4 * j;
+                tj[j] = (x < M && yz < ncol) ? tabp[x * ncol + yz] : -1;
             }
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-                mfma_group(af, bs[(P + g) & 1], g);
+                mfma_group(af, bs[(P + g) & 1], tj, g);
                 // (the loads stay behind the products that read the registers they fill: one set, not two, is live)
                 __builtin_amdgcn_sched_barrier(0);
                 load_group(bs[(P + g) & 1], ty + (g + 2) / NG, (g + 2) % NG);
                 __builtin_amdgcn_sched_barrier(0);
-                if (g == 0) TAIL_MARK(ty < 3 ? 4 + 3 * ty : 31);
             }
-            __syncthreads();
-            TAIL_MARK(ty < 3 ? 5 + 3 * ty : 31);
-            const int yz = 16 * ty + lr;
-            int off = 0;
-            if (yz < ncol) {
-                int y, z;
-                tri_decode(yz, M, y, z);
-                off = y * M + z;
-            }
-            // 16 x 16 tiles (nt, x) of g_mo[n, x, yz], tile = nt M + x, dealt to the waves in turn
-#pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) {
-                if (nt >= ntn) continue;
-                const int t0 = nt * M;
-                for (int tile = t0 + (wave - t0 % NW + NW) % NW; tile < t0 + M; tile += NW) {
-                    const int x = tile - t0;
-                    double tf[KS];
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) tf[ks] = T3s[(size_t)(4 * ks + lq) * LDP + x * 16 + lr];
-                    d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(cfa[nt][ks], tf[ks], acc);
-                    const int ci = yz < ncol ? tab[x * M2 + off] : -1;
-                    if (ci >= 0) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int n = 16 * nt + lq + 4 * j;
-                            if (n < N) Gc[(size_t)n * NC + ci] = acc[j];
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            TAIL_MARK(ty < 3 ? 6 + 3 * ty : 31);
         };
         for (int ty = 0; ty < nty; ty += 2) {
             tail_tile(std::integral_constant<int, 0>{}, ty);
@@ -3144,15 +3113,57 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         }
     }
 
+    // ---- p -> n over the column tiles of Gc, in place (sym_gm_kernel's second step) ---------------------
+    // A = C[p, n] from L2 (loaded here, where the registers of the J sets are free), B = Gc[p][column] from LDS;
+    // D rows n = 16 nt + lq + 4 j, columns 16 ct + lr
+    {
+        const __amdgpu_buffer_rsrc_t csrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(C), 0, (int)((size_t)N * N * sizeof(double)), 0x00020000);
+        double cfa[NTN][KS];
+#pragma unroll
+        for (int nt = 0; nt < NTN; ++nt)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int pp = 4 * ks + lq, n = 16 * nt + lr;
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(
+                    csrd, (pp < N && n < N) ? (unsigned)((pp * N + n) * (int)sizeof(double)) : 0x7fffffffu, 0, 0);
+                cfa[nt][ks] = __builtin_bit_cast(double, v);
+            }
+        __syncthreads();                             // every row of Gc is written
+        TAIL_MARK(4);
+        const int ntn = (N + 15) / 16;
+        for (int ct = wave; ct < nct; ct += NW) {
+            double* col = Gc + (16 * ct + lr);
+            double tf[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) tf[ks] = col[(4 * ks + lq) * LDG];
+#pragma unroll
+            for (int nt = 0; nt < NTN; ++nt) {
+                if (nt >= ntn) continue;
+                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) acc = mfma_f64(cfa[nt][ks], tf[ks], acc);
+                // (rows n of the wave's own columns: their operands are in tf)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int n = 16 * nt + lq + 4 * j;
+                    if (n < N) col[n * LDG] = acc[j];
+                }
+            }
+        }
+        __syncthreads();
+        TAIL_MARK(5);
+    }
+
     // ---- stage 3 (cas_panel_kernel with one panel of all N general indices) -----------------------
-#define TAIL_G(n, a, b, c) Gc[(size_t)(n) * NC + tab[((a) * M + (b)) * M + (c)]]
+#define TAIL_G(n, a, b, c) Gc[(n) * LDG + tab[((a) * M + (b)) * M + (c)]]
     for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
         const int n = idx / M, x = idx - n * M;
         double fi = hn[idx];
         for (int i = 0; i < no; ++i) fi += 2.0 * TAIL_G(n, x, i, i) - TAIL_G(n, i, i, x);
         FIn[idx] = fi;
     }
-    TAIL_MARK(13);
+    TAIL_MARK(6);
     double* Fl = scr;                                // [nrdm][M][N]  Fock columns
     double* El = Fl + (size_t)nrdm * M * N;          // [nrdm][N]     Epart
     double* Ga = El + (size_t)nrdm * N;              // [N][na3]      g_mo[n, no + w, no + x, no + y]
@@ -3170,7 +3181,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         Dc[idx] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
     }
     __syncthreads();
-    TAIL_MARK(14);
+    TAIL_MARK(7);
     for (int n = tid; n < N; n += TAIL_THREADS) Cp[n] = n < no ? hn[n * M + n] + FIn[n * M + n] : 0.0;
     for (int idx = tid; idx < na * (na + na3); idx += TAIL_THREADS) {
         const int pl = idx / (na + na3), r0 = idx - pl * (na + na3);
@@ -3186,7 +3197,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             c2[(size_t)pl * na3 + i3] = 0.5 * TAIL_G(n, no + q, no + r, no + s);
         }
     }
-    TAIL_MARK(15);
+    TAIL_MARK(8);
     // Fock columns: one thread per (n, set k, row m), the core rows first (waves without divergent rows)
     const int ncore = N * nrdm * no;
     for (int idx = tid; idx < N * nrdm * M; idx += TAIL_THREADS) {
@@ -3225,7 +3236,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         }
         Fl[((size_t)k * M + m) * N + n] = val;
     }
-    TAIL_MARK(16);
+    TAIL_MARK(9);
     // E_k contribution of row p = n - no (active n only), serial per (n, set)
     for (int idx = tid; idx < N * nrdm; idx += TAIL_THREADS) {
         const int n = idx / nrdm, k = idx - n * nrdm;
@@ -3245,7 +3256,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     }
 #undef TAIL_G
     __syncthreads();
-    TAIL_MARK(17);
+    TAIL_MARK(10);
 
     // ---- assembly (cas_final_kernel) ----------------------------------------------------------------
     for (int idx = tid; idx < nrdm * n_kappa; idx += TAIL_THREADS) {
@@ -3269,7 +3280,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             dE[k - 1] = acc;
         }
     }
-    TAIL_MARK(18);
+    TAIL_MARK(11);
 }
 
 }  // namespace
@@ -3601,13 +3612,12 @@ static size_t tail_lds_bytes(int N, int no, int na, int nrdm, int n_kappa, int* 
             for (int z = y; z < M; ++z) nc += tail_needed(x, y, z, no) ? 1 : 0;
     *NC = nc;
     const size_t na2 = (size_t)na * na, na4 = na2 * na2;
-    size_t scr = (size_t)N * N;                                           // W
-    const size_t t3 = (size_t)4 * tail_depth(N, v) * (M * 16 + 8);        // T3s
+    size_t scr = (size_t)N * N + ((size_t)M * (M * (M + 1) / 2) + 1) / 2; // W and the table by (x, yz)
+    const size_t gc = (size_t)4 * tail_depth(N, v) * tail_pitch(nc);      // Gc
     const size_t fe = (size_t)nrdm * M * N + (size_t)nrdm * N +           // Fcol + Epart + Ga + Dc
                       (size_t)N * na * na * na + (size_t)N * no * na2;
-    if (t3 > scr) scr = t3;
     if (fe > scr) scr = fe;
-    const size_t doubles = (size_t)N * nc + 3 * (size_t)N * M + (size_t)nrdm * (na2 + na4) + N +
+    const size_t doubles = gc + 3 * (size_t)N * M + (size_t)nrdm * (na2 + na4) + N +
                            ((size_t)M3 + TAIL_THREADS / 64 + 2 * (size_t)n_kappa + 1) / 2 + scr;
     const size_t bytes = doubles * sizeof(double);
     return bytes <= 160 * 1024 ? bytes : 0;

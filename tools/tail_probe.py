@@ -21,11 +21,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 NCAS, NELECAS, NELEC = 3, 4, 16
 WGS, MARKS = 512, 32
 PHASES = [(0, 1, "inputs staged (first J loads issued)"), (1, 2, "position table"), (2, 3, "h_mo"),
-          (3, 4, "tile 0: q->x first part"), (4, 5, "tile 0: q->x rest"), (5, 6, "tile 0: p->n"),
-          (6, 7, "tile 1: q->x first part"), (7, 8, "tile 1: q->x rest"), (8, 9, "tile 1: p->n"),
-          (9, 10, "tile 2: q->x first part"), (10, 11, "tile 2: q->x rest"), (11, 12, "tile 2: p->n"),
-          (12, 13, "FI"), (13, 14, "gathers (Ga, Dc)"), (14, 15, "Cpart, c1, c2"), (15, 16, "Fock columns"),
-          (16, 17, "energy parts"), (17, 18, "assembly"), (0, 18, "whole workgroup")]
+          (3, 4, "q->x, all tiles of (y <= z)"), (4, 5, "p->n over the packed columns"),
+          (5, 6, "FI"), (6, 7, "gathers (Ga, Dc)"), (7, 8, "Cpart, c1, c2"), (8, 9, "Fock columns"),
+          (9, 10, "energy parts"), (10, 11, "assembly"), (0, 11, "whole workgroup")]
+LAST = PHASES[-1][1]
 
 
 def main():
@@ -58,7 +57,7 @@ def main():
     for a, b, name in PHASES:
         d = t[:, b] - t[:, a]
         lines.append(f"{name:40s} {d.mean():8.2f} {d.min():7.2f} {d.max():7.2f}")
-    lines.append(f"first start to last end over the grid: {t[:, 18].max() - t[:, 0].min():.2f} us")
+    lines.append(f"first start to last end over the grid: {t[:, LAST].max() - t[:, 0].min():.2f} us")
     text = "\n".join(lines)
     print(text)
     if out:
