@@ -28,6 +28,7 @@
 #define CHG_NW (CHG_NT / 64)
 #define CHG_GL 64                // charges per chunk of the gradient kernel (one wave)
 #define CHG_MAX 65535            // charges per geometry
+#define CHG_LDS_MAX (160 * 1024) // bytes of LDS a workgroup of the gradient kernel may ask for: natm <= 106
 
 // ---- operator ---------------------------------------------------------------------------------------------------------
 template <int LA, int LB> struct gto_chg_lds_t {
@@ -278,6 +279,16 @@ int chg_check(const char* who, int batch, int ncharge)
     return 0;
 }
 
+// the gradient kernel keeps the atoms' shares of a chunk in dynamic LDS [natm][3][CHG_GL]: refused before anything is
+// launched where that exceeds what a workgroup can have
+int chg_check_atoms(const char* who, int natm)
+{
+    const size_t lds = (size_t)(natm > 0 ? natm : 0) * 3 * CHG_GL * sizeof(double);
+    OOVQE_REQUIRE(lds <= CHG_LDS_MAX, "%s: natm = %d (the atoms' shares of a chunk need %zu bytes of LDS, at most %d)", who,
+                  natm, lds, CHG_LDS_MAX);
+    return 0;
+}
+
 template <int LA, int LB>
 int chg_launch_op(const gto_prep_t& p, const int32_t* shells, int nshell, int natm, const double* coords, int batch,
                   int nao, int ncharge, const double* q, const double* qxyz, double* vext, hipStream_t st)
@@ -319,6 +330,7 @@ extern "C" int64_t oovqe_gto_point_charge_gradient_work_size(int nshell, int max
     if (gto_check_sizes(who, nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(natm >= 1, "%s: natm = %d", who, natm);
     if (chg_check(who, batch, ncharge) != 0) return OOVQE_ERR_ARG;
+    if (chg_check_atoms(who, natm) != 0) return OOVQE_ERR_ARG;
     const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
     const int64_t nchunk = (ncharge + CHG_GL - 1) / CHG_GL;
     return gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW
@@ -337,13 +349,13 @@ extern "C" int oovqe_gto_point_charge_gradient_batch(int nshell, const int32_t* 
     hipStream_t st = (hipStream_t)stream;
     int rc = chg_check(who, batch, ncharge);
     if (rc != 0) return rc;
+    if ((rc = chg_check_atoms(who, natm)) != 0) return rc;
     gto_prep_t p;
     rc = gto_prepare(who, 1, nshell, shells, nprim_total, exps, coefs, natm, charges, batch, coords, nao, nullptr, work,
                      st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(q && qxyz && d1 && grad_atoms && grad_charges, "%s: null pointer", who);
     const size_t lds = (size_t)natm * 3 * CHG_GL * sizeof(double);
-    OOVQE_REQUIRE(lds <= 160 * 1024, "%s: natm = %d (the atoms' shares of a chunk need %zu bytes of LDS)", who, natm, lds);
     if (oovqe_ensure_dynamic_lds(reinterpret_cast<const void*>(&gto_charge_grad_kernel), lds) != 0) return OOVQE_ERR_HIP;
     const long npair = (long)nshell * (nshell + 1) / 2;
     const int nchunk = (ncharge + CHG_GL - 1) / CHG_GL;

@@ -660,6 +660,8 @@ def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
     if not isinstance(dm1, torch.Tensor) or tuple(dm1.shape) != (G, N, N):
         raise ValueError(f"dm1 has shape {tuple(getattr(dm1, 'shape', ()))}, expected {(G, N, N)}")
     dev = xyz.device
+    # (the size of the work buffer is asked for first: a molecule the entry refuses raises here, before any allocation)
+    work = point_charge_gradient_work(basis, dev, G, M)
     gA = torch.empty((G, basis.natm, 3), dtype=F64, device=dev)
     gQ = torch.empty((G, M, 3), dtype=F64, device=dev)
     if G == 0:
@@ -667,7 +669,6 @@ def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
     lib = _lib.load()
     t = basis.device_tables(dev)
     d1 = dm1.to(device=dev, dtype=F64).contiguous()
-    work = point_charge_gradient_work(basis, dev, G, M)
     check(lib.oovqe_gto_point_charge_gradient_batch(
         basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
         dptr(t.charges), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(d1), int(bool(nuc)), dptr(gA), dptr(gQ),

@@ -777,7 +777,8 @@ int oovqe_gto_overlap_connection_batch(int nshell, const int32_t* shells, int np
  * symmetric; work: oovqe_gto_work_size doubles);
  *   grad_atoms[g][A][:] = sum d1[g] . d vext[g] / dR_A,  grad_charges[g][k][:] = sum d1[g] . d vext[g] / d qxyz[g][k]
  * for a symmetric d1 [batch][nao][nao] (read as oovqe_gto_gradient_batch reads it), s and p shells only (a table with
- * l = 2 is refused before any launch); with_nuc adds the derivatives of sum_{A,k} Z_A q_k / |R_A - r_k| to both (a
+ * l = 2 is refused before any launch, and so is natm > 106: the atoms' shares of a chunk of 64 charges, natm x 1536
+ * bytes of LDS, must fit 160 KB -- by the work-size function too); with_nuc adds the derivatives of sum_{A,k} Z_A q_k / |R_A - r_k| to both (a
  * charge ON a nucleus then gives NaN).  There is no charge-charge term.  No floating-point atomics, fixed orders of
  * summation: a geometry has the same bits wherever it stands in the stack.  work:
  * oovqe_gto_point_charge_gradient_work_size(...) doubles = the pair data + batch x ceil(ncharge / 64) x natm x 3. */
