@@ -2,6 +2,8 @@
 // (gto_grad.hip): constants, static_for, the Boys function, Hermite expansion coefficients, Hermite Coulomb
 // integrals, the layout of the work buffer and the readers of the pair data of gto_pair_kernel.  l is a template
 // parameter everywhere: the derivative kernels instantiate gto_herm / gto_boys / gto_R_fill one order higher.
+// Behind them the host side every entry point of the gto*.hip files shares: gto_prep_t, the grid of a launch, the lists
+// of pair and quartet classes.
 #pragma once
 #include "common.h"
 #include "jacobi.h"
@@ -264,22 +266,82 @@ static inline int gto_check_sizes(const char* who, int nshell, int max_nprim, in
     return 0;
 }
 
-struct gto_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
-    const double* coords; int batch; const double* pairs; int kp; int nao; double* overlap; double* h_ao;
-    double* g_ao; hipStream_t st;
-};
-// the classes with a d shell (gto_d.hip)
-int gto_d_launch_one_electron(const gto_launch_t& a);
-int gto_d_launch_two_electron(const gto_launch_t& a);
+// The work buffer of every entry: int part | pair data of the stack | the entry's own records.  This is the size of the
+// first two; a *_work_size export adds its records, and gto_prep_t::rec is where they begin.
+static inline int64_t gto_work_base(int nshell, int max_nprim, int batch)
+{
+    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
+    return gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
+}
 
+// What every launcher of an entry needs: what gto_prepare made of the shell table and the work buffer, and the entry's
+// arguments it received.  A launcher takes this and the arguments of its own kernel.
 struct gto_prep_t {
     int cnt[GTO_NCLS];          // shell pairs per class
     int kp;                     // slots per shell pair of the pair data (largest primitive count squared)
     int batch;
     int* iw;                    // ao_off | class lists
     double* pairs;              // pair data [batch][npair][kp][GTO_PW]
+    double* rec;                // the entry's own records, behind the pair data
+    const char* who;            // the entry, as its messages name it
+    const int32_t* shells; int nshell; const double* charges; int natm; const double* coords; int nao; hipStream_t st;
+    long npair() const { return (long)nshell * (nshell + 1) / 2; }
 };
 int gto_prepare(const char* who, int max_l, int nshell, const int32_t* shells, int nprim_total, const double* exps,
                 const double* coefs, int natm, const double* charges, int batch, const double* coords, int nao,
                 double* nuc, double* work, hipStream_t st, gto_prep_t* p);
+// The read-back of the shell table (16 bytes per shell, once per call) and the checks of every shell against the
+// limits, in the order and with the messages of gto_prepare, which uses it; so does the cross overlap, which has no work
+// buffer.  tab receives the table [nshell][4].
+int gto_read_shells(const char* who, int max_l, int nshell, const int32_t* shells, int nprim_total, int natm, int nao,
+                    hipStream_t st, std::vector<int32_t>* tab);
+// the classes with a d shell (gto_d.hip)
+int gto_d_launch_one_electron(const gto_prep_t& p, double* overlap, double* h_ao);
+int gto_d_launch_two_electron(const gto_prep_t& p, double* g_ao);
+
+// ---- grid of a launch ---------------------------------------------------------------------------------------------
+// one workgroup per item (the kernels of the d classes) ...
+static inline int gto_grid_wg(const char* who, long items, unsigned* grid)
+{
+    OOVQE_REQUIRE(items < (1L << 31), "%s: %ld workgroups in one launch", who, items);
+    *grid = (unsigned)items;
+    return 0;
+}
+// ... or GTO_SPLIT lanes per item in workgroups of GTO_NT (the s/p kernels)
+static inline int gto_grid_split(const char* who, long items, unsigned* grid)
+{
+    return gto_grid_wg(who, (items * GTO_SPLIT + GTO_NT - 1) / GTO_NT, grid);
+}
+// quartets of a bra class of nbra pairs and a ket class of nket pairs (bra pair >= ket pair within one class)
+static inline long gto_quartets(bool same, long nbra, long nket) { return same ? nbra * (nbra + 1) / 2 : nbra * nket; }
+
+// ---- the class lists, in launch order -------------------------------------------------------------------------------
+// A pair class <la, lb> or a quartet class <la, lb, lc, ld> as a value: a launcher deduces its template arguments from it.
+template <int... L> struct gto_cls_t {};
+// f(class) for every class in turn, up to the first return code that is not 0
+template <class F, class... C> int gto_each(F&& f, C... c)
+{
+    int rc = 0;
+    (void)(((rc = f(c)) == 0) && ...);
+    return rc;
+}
+template <class F> int gto_sp_pairs(F&& f) { return gto_each(f, gto_cls_t<0, 0>{}, gto_cls_t<1, 0>{}, gto_cls_t<1, 1>{}); }
+template <class F> int gto_d_pairs(F&& f) { return gto_each(f, gto_cls_t<2, 2>{}, gto_cls_t<2, 1>{}, gto_cls_t<2, 0>{}); }
+// all pair classes, the long workgroups of the d classes first (moments, cross overlap) ...
+template <class F> int gto_pairs_d_first(F&& f)
+{
+    const int rc = gto_d_pairs(f);
+    return rc != 0 ? rc : gto_sp_pairs(f);
+}
+// ... or descending (point charges)
+template <class F> int gto_pairs_descending(F&& f)
+{
+    const int rc = gto_d_pairs(f);
+    return rc != 0 ? rc : gto_each(f, gto_cls_t<1, 1>{}, gto_cls_t<1, 0>{}, gto_cls_t<0, 0>{});
+}
+// the s/p quartets: bra class >= ket class; the long threads of (pp|pp) first, the most numerous (and cheapest) last
+template <class F> int gto_sp_quartets(F&& f)
+{
+    return gto_each(f, gto_cls_t<1, 1, 1, 1>{}, gto_cls_t<1, 1, 1, 0>{}, gto_cls_t<1, 1, 0, 0>{}, gto_cls_t<1, 0, 1, 0>{},
+                    gto_cls_t<1, 0, 0, 0>{}, gto_cls_t<0, 0, 0, 0>{});
+}

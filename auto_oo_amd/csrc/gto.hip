@@ -445,37 +445,65 @@ __global__ __launch_bounds__(INVSQRT_NT) void sym_invsqrt_kernel(const double* _
 extern "C" int64_t oovqe_gto_work_size(int nshell, int max_nprim, int batch)
 {
     if (gto_check_sizes("oovqe_gto_work_size", nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
-    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
-    return gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
+    return gto_work_base(nshell, max_nprim, batch);
 }
 
 namespace {
-template <int LA, int LB> int gto_launch_one(const gto_launch_t& a)
+template <int LA, int LB> int gto_launch_one(gto_cls_t<LA, LB>, const gto_prep_t& p, double* overlap, double* h_ao)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    const long total = (long)count * a.batch * GTO_SPLIT;
-    hipLaunchKernelGGL((gto_one_kernel<LA, LB>), dim3((unsigned)((total + GTO_NT - 1) / GTO_NT)), dim3(GTO_NT), 0,
-                       a.st, a.iw, a.shells, a.nshell, count, a.charges, a.natm, a.coords, a.batch, a.pairs, a.kp,
-                       a.nao, a.overlap, a.h_ao);
+    unsigned grid;
+    if (const int rc = gto_grid_split(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_one_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                       p.charges, p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, overlap, h_ao);
     OOVQE_CHECK_LAUNCH("gto_one_kernel");
     return 0;
 }
 
-template <int LA, int LB, int LC, int LD> int gto_launch_eri(const gto_launch_t& a)
+template <int LA, int LB, int LC, int LD>
+int gto_launch_eri(gto_cls_t<LA, LB, LC, LD>, const gto_prep_t& p, double* g_ao)
 {
-    const int nbra = a.cnt[gto_cls(LA, LB)], nket = a.cnt[gto_cls(LC, LD)];
-    const bool same = (LA == LC && LB == LD);
-    const long nq = same ? (long)nbra * (nbra + 1) / 2 : (long)nbra * nket;
+    const int nbra = p.cnt[gto_cls(LA, LB)], nket = p.cnt[gto_cls(LC, LD)];
+    const long nq = gto_quartets(LA == LC && LB == LD, nbra, nket);
     if (nq == 0) return 0;
-    const long blocks = (nq * a.batch * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
-    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_integrals_batch: %ld workgroups in one launch", blocks);
-    hipLaunchKernelGGL((gto_eri_kernel<LA, LB, LC, LD>), dim3((unsigned)blocks), dim3(GTO_NT), 0, a.st, a.iw,
-                       a.shells, a.nshell, nbra, nket, nq, a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao, a.g_ao);
+    unsigned grid;
+    if (const int rc = gto_grid_split(p.who, nq * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_eri_kernel<LA, LB, LC, LD>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell,
+                       nbra, nket, nq, p.coords, p.natm, p.batch, p.pairs, p.kp, p.nao, g_ao);
     OOVQE_CHECK_LAUNCH("gto_eri_kernel");
     return 0;
 }
 }  // namespace
+
+int gto_read_shells(const char* who, int max_l, int nshell, const int32_t* shells, int nprim_total, int natm, int nao,
+                    hipStream_t st, std::vector<int32_t>* table)
+{
+    // the shell table is read back once per call (16 bytes per shell): the limits below are enforced here, with a
+    // return code, and the launches are sized from it
+    std::vector<int32_t>& tab = *table;
+    tab.resize((size_t)nshell * 4);
+    OOVQE_CHECK_HIP(hipMemcpyAsync(tab.data(), shells, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st), who);
+    OOVQE_CHECK_HIP(hipStreamSynchronize(st), who);
+    int ao = 0;
+    for (int s = 0; s < nshell; ++s) {
+        const int atom = tab[4 * s], field = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
+        const int l = gto_l_of(field);
+        OOVQE_REQUIRE(field >= 0 && l <= OOVQE_GTO_MAX_L && (field == l || (l == 2 && field == (2 | OOVQE_GTO_CARTESIAN))),
+                      "%s: shell %d has the l field %d (l <= %d; OOVQE_GTO_CARTESIAN on a d shell only)", who, s, field,
+                      OOVQE_GTO_MAX_L);
+        OOVQE_REQUIRE(l <= max_l, "%s: shell %d has l = %d: this entry serves s and p shells only (l <= %d)", who, s, l,
+                      max_l);
+        OOVQE_REQUIRE(np >= 1 && np <= OOVQE_GTO_MAX_PRIM, "%s: shell %d has %d primitives (1 .. %d)", who, s, np,
+                      OOVQE_GTO_MAX_PRIM);
+        OOVQE_REQUIRE(atom >= 0 && atom < natm, "%s: shell %d sits on atom %d of %d", who, s, atom, natm);
+        OOVQE_REQUIRE(off >= 0 && off + np <= nprim_total, "%s: shell %d reads primitives %d .. %d of %d", who, s,
+                      off, off + np - 1, nprim_total);
+        ao += gto_nfunc(field);
+    }
+    OOVQE_REQUIRE(ao == nao, "%s: the shell table has %d functions, nao = %d", who, ao, nao);
+    return 0;
+}
 
 // What every entry point that consumes pair data does first: the shell table is checked against the limits, the pair
 // classes counted, ao_off / class lists (gto_setup_kernel) and the pair data of every geometry (gto_pair_kernel; nuc
@@ -491,41 +519,28 @@ int gto_prepare(const char* who, int max_l, int nshell, const int32_t* shells, i
     p->batch = batch;
     if (batch == 0) return 0;
     OOVQE_REQUIRE(shells && exps && coefs && charges && coords && work, "%s: null pointer", who);
-    // the shell table is read back once per call (16 bytes per shell): the limits below are enforced here, with a
-    // return code, and the launches are sized from it
-    std::vector<int32_t> tab((size_t)nshell * 4);
-    OOVQE_CHECK_HIP(hipMemcpyAsync(tab.data(), shells, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st), who);
-    OOVQE_CHECK_HIP(hipStreamSynchronize(st), who);
+    std::vector<int32_t> tab;
+    const int rc = gto_read_shells(who, max_l, nshell, shells, nprim_total, natm, nao, st, &tab);
+    if (rc != 0) return rc;
     int* cnt = p->cnt;
     for (int c = 0; c < GTO_NCLS; ++c) cnt[c] = 0;
-    int ao = 0, kp = 0;
-    for (int s = 0; s < nshell; ++s) {
-        const int atom = tab[4 * s], field = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
-        const int l = gto_l_of(field);
-        OOVQE_REQUIRE(field >= 0 && l <= OOVQE_GTO_MAX_L && (field == l || (l == 2 && field == (2 | OOVQE_GTO_CARTESIAN))),
-                      "%s: shell %d has the l field %d (l <= %d; OOVQE_GTO_CARTESIAN on a d shell only)", who, s, field,
-                      OOVQE_GTO_MAX_L);
-        OOVQE_REQUIRE(l <= max_l, "%s: shell %d has l = %d: this entry serves s and p shells only (l <= %d)", who, s, l,
-                      max_l);
-        OOVQE_REQUIRE(np >= 1 && np <= OOVQE_GTO_MAX_PRIM, "%s: shell %d has %d primitives (1 .. %d)", who, s, np,
-                      OOVQE_GTO_MAX_PRIM);
-        OOVQE_REQUIRE(atom >= 0 && atom < natm, "%s: shell %d sits on atom %d of %d", who, s, atom, natm);
-        OOVQE_REQUIRE(off >= 0 && off + np <= nprim_total, "%s: shell %d reads primitives %d .. %d of %d", who, s,
-                      off, off + np - 1, nprim_total);
-        ao += gto_nfunc(field);
-        kp = np > kp ? np : kp;
-    }
-    OOVQE_REQUIRE(ao == nao, "%s: the shell table has %d functions, nao = %d", who, ao, nao);
-    for (int i = 0; i < nshell; ++i)
+    int kp = 0;
+    for (int i = 0; i < nshell; ++i) {
+        kp = tab[4 * i + 2] > kp ? tab[4 * i + 2] : kp;
         for (int j = 0; j <= i; ++j) {
             const int li = gto_l_of(tab[4 * i + 1]), lj = gto_l_of(tab[4 * j + 1]);
             cnt[gto_cls(li >= lj ? li : lj, li >= lj ? lj : li)] += 1;
         }
+    }
     kp *= kp;
     const long npair = (long)nshell * (nshell + 1) / 2;
+    // the layout of the work buffer: int part | pair data of the stack | the entry's own records
     int* iw = p->iw = reinterpret_cast<int*>(work);
     double* pairs = p->pairs = work + gto_int_doubles(nshell);
+    p->rec = pairs + (size_t)batch * npair * kp * GTO_PW;
     p->kp = kp;
+    p->who = who; p->shells = shells; p->nshell = nshell; p->charges = charges; p->natm = natm; p->coords = coords;
+    p->nao = nao; p->st = st;
     hipLaunchKernelGGL(gto_setup_kernel, dim3(1), dim3(64), 0, st, shells, nshell, iw);
     OOVQE_CHECK_LAUNCH("gto_setup_kernel");
     const long pt = npair * kp * batch;
@@ -546,28 +561,15 @@ extern "C" int oovqe_gto_integrals_batch(int nshell, const int32_t* shells, int 
     int rc = gto_prepare("oovqe_gto_integrals_batch", OOVQE_GTO_MAX_L, nshell, shells, nprim_total, exps, coefs, natm, charges, batch,
                          coords, nao, nuc, work, st, &p);
     if (rc != 0 || batch == 0) return rc;
-    const int* cnt = p.cnt;
-    const int* iw = p.iw;
-    const double* pairs = p.pairs;
-    const int kp = p.kp;
-    const gto_launch_t a = {iw, shells, nshell, cnt, charges, natm, coords, batch, pairs, kp, nao, overlap, h_ao,
-                            g_ao, st};
     if (overlap || h_ao) {
-        if ((rc = gto_d_launch_one_electron(a)) != 0) return rc;
-        if ((rc = gto_launch_one<0, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_one<1, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_one<1, 1>(a)) != 0) return rc;
+        if ((rc = gto_d_launch_one_electron(p, overlap, h_ao)) != 0) return rc;
+        if ((rc = gto_sp_pairs([&](auto c) { return gto_launch_one(c, p, overlap, h_ao); })) != 0) return rc;
     }
     if (g_ao) {
         // bra class >= ket class; the most numerous (and cheapest) classes last, behind the classes with a d shell
         // (gto_d.hip) and the long threads of (pp|pp)
-        if ((rc = gto_d_launch_two_electron(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<1, 1, 1, 1>(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<1, 1, 1, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<1, 1, 0, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<1, 0, 1, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<1, 0, 0, 0>(a)) != 0) return rc;
-        if ((rc = gto_launch_eri<0, 0, 0, 0>(a)) != 0) return rc;
+        if ((rc = gto_d_launch_two_electron(p, g_ao)) != 0) return rc;
+        if ((rc = gto_sp_quartets([&](auto c) { return gto_launch_eri(c, p, g_ao); })) != 0) return rc;
     }
     return 0;
 }

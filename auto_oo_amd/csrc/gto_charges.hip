@@ -290,13 +290,14 @@ int chg_check_atoms(const char* who, int natm)
 }
 
 template <int LA, int LB>
-int chg_launch_op(const gto_prep_t& p, const int32_t* shells, int nshell, int natm, const double* coords, int batch,
-                  int nao, int ncharge, const double* q, const double* qxyz, double* vext, hipStream_t st)
+int chg_launch_op(gto_cls_t<LA, LB>, const gto_prep_t& p, int ncharge, const double* q, const double* qxyz, double* vext)
 {
     const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    hipLaunchKernelGGL((gto_charge_op_kernel<LA, LB>), dim3((unsigned)((long)count * batch)), dim3(CHG_NT), 0, st, p.iw,
-                       shells, nshell, count, natm, coords, batch, p.pairs, p.kp, nao, ncharge, q, qxyz, vext);
+    unsigned grid;
+    if (const int rc = gto_grid_wg(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_charge_op_kernel<LA, LB>), dim3(grid), dim3(CHG_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                       p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, ncharge, q, qxyz, vext);
     OOVQE_CHECK_LAUNCH("gto_charge_op_kernel");
     return 0;
 }
@@ -316,12 +317,7 @@ extern "C" int oovqe_gto_point_charge_batch(int nshell, const int32_t* shells, i
                      nullptr, work, st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(q && qxyz && vext, "%s: null pointer", who);
-    if ((rc = chg_launch_op<2, 2>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st)) != 0) return rc;
-    if ((rc = chg_launch_op<2, 1>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st)) != 0) return rc;
-    if ((rc = chg_launch_op<2, 0>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st)) != 0) return rc;
-    if ((rc = chg_launch_op<1, 1>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st)) != 0) return rc;
-    if ((rc = chg_launch_op<1, 0>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st)) != 0) return rc;
-    return chg_launch_op<0, 0>(p, shells, nshell, natm, coords, batch, nao, ncharge, q, qxyz, vext, st);
+    return gto_pairs_descending([&](auto c) { return chg_launch_op(c, p, ncharge, q, qxyz, vext); });
 }
 
 extern "C" int64_t oovqe_gto_point_charge_gradient_work_size(int nshell, int max_nprim, int natm, int batch, int ncharge)
@@ -331,10 +327,8 @@ extern "C" int64_t oovqe_gto_point_charge_gradient_work_size(int nshell, int max
     OOVQE_REQUIRE(natm >= 1, "%s: natm = %d", who, natm);
     if (chg_check(who, batch, ncharge) != 0) return OOVQE_ERR_ARG;
     if (chg_check_atoms(who, natm) != 0) return OOVQE_ERR_ARG;
-    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
     const int64_t nchunk = (ncharge + CHG_GL - 1) / CHG_GL;
-    return gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW
-           + (int64_t)batch * nchunk * natm * 3;
+    return gto_work_base(nshell, max_nprim, batch) + (int64_t)batch * nchunk * natm * 3;
 }
 
 extern "C" int oovqe_gto_point_charge_gradient_batch(int nshell, const int32_t* shells, int nprim_total,
@@ -357,9 +351,8 @@ extern "C" int oovqe_gto_point_charge_gradient_batch(int nshell, const int32_t* 
     OOVQE_REQUIRE(q && qxyz && d1 && grad_atoms && grad_charges, "%s: null pointer", who);
     const size_t lds = (size_t)natm * 3 * CHG_GL * sizeof(double);
     if (oovqe_ensure_dynamic_lds(reinterpret_cast<const void*>(&gto_charge_grad_kernel), lds) != 0) return OOVQE_ERR_HIP;
-    const long npair = (long)nshell * (nshell + 1) / 2;
     const int nchunk = (ncharge + CHG_GL - 1) / CHG_GL;
-    double* rec = p.pairs + (size_t)batch * npair * p.kp * GTO_PW;
+    double* rec = p.rec;
     hipLaunchKernelGGL(gto_charge_grad_kernel, dim3(nchunk, batch), dim3(CHG_GL), lds, st, p.iw, shells, nshell,
                        p.cnt[gto_cls(0, 0)], p.cnt[gto_cls(1, 0)], p.cnt[gto_cls(1, 1)], charges, natm, coords, p.pairs,
                        p.kp, nao, ncharge, q, qxyz, d1, with_nuc ? 1 : 0, grad_charges, rec);

@@ -108,28 +108,21 @@ extern "C" int64_t oovqe_gto_overlap_connection_work_size(int nshell, int max_np
     const char* who = "oovqe_gto_overlap_connection_work_size";
     if (gto_check_sizes(who, nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(natm >= 1, "%s: natm = %d", who, natm);
-    OOVQE_REQUIRE(nset >= 1 && nset <= OOVQE_GTO_GRAD_MAX_SETS, "%s: nset = %d (1 .. %d)", who, nset,
-                  OOVQE_GTO_GRAD_MAX_SETS);
+    if (grad_check_nset(who, nset) != 0) return OOVQE_ERR_ARG;
     const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
-    const int64_t base = gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
-    return base + (int64_t)batch * nset * npair * GRAD_REC;
+    return gto_work_base(nshell, max_nprim, batch) + (int64_t)batch * nset * npair * GRAD_REC;
 }
 
 namespace {
-struct conn_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; int natm; const double* coords; int batch;
-    const double* pairs; int kp; int nao; int nset; int k0; int nk; const double* dm; double* rec; long nrec;
-    hipStream_t st;
-};
-
-template <int LA, int LB> int conn_launch(const conn_launch_t& a, long& off)
+template <int LA, int LB>
+int conn_launch(gto_cls_t<LA, LB>, const gto_prep_t& p, int nset, int k0, int nk, const double* dm, long& off)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    const long total = (long)count * a.batch * GTO_SPLIT;
-    hipLaunchKernelGGL((gto_connection_kernel<LA, LB>), dim3((unsigned)((total + GTO_NT - 1) / GTO_NT)), dim3(GTO_NT), 0,
-                       a.st, a.iw, a.shells, a.nshell, count, a.natm, a.coords, a.batch, a.pairs, a.kp, a.nao, a.nset,
-                       a.k0, a.nk, a.dm, a.rec, off, a.nrec);
+    unsigned grid;
+    if (const int rc = gto_grid_split(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_connection_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                       p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, nset, k0, nk, dm, p.rec, off, p.npair());
     OOVQE_CHECK_LAUNCH("gto_connection_kernel");
     off += count;
     return 0;
@@ -144,32 +137,25 @@ extern "C" int oovqe_gto_overlap_connection_batch(int nshell, const int32_t* she
     const char* who = "oovqe_gto_overlap_connection_batch";
     hipStream_t st = (hipStream_t)stream;
     gto_prep_t p;
-    OOVQE_REQUIRE(nset >= 1 && nset <= OOVQE_GTO_GRAD_MAX_SETS, "%s: nset = %d (1 .. %d)", who, nset,
-                  OOVQE_GTO_GRAD_MAX_SETS);
+    if (grad_check_nset(who, nset) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(batch <= 65535, "%s: batch = %d (at most 65535 geometries per call)", who, batch);
     // (a table with l = 2 is refused here, before any launch, as by oovqe_gto_gradient_batch)
     int rc = gto_prepare(who, 1, nshell, shells, nprim_total, exps, coefs, natm, charges, batch, coords, nao, nullptr, work,
                          st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(dm && out, "%s: null pointer", who);
-    const long npair = (long)nshell * (nshell + 1) / 2;
-    double* rec = p.pairs + (size_t)batch * npair * p.kp * GTO_PW;
+    const long npair = p.npair();
     // the sets spread evenly over the fewest tiles, as in oovqe_gto_gradient_sets_batch
-    const int ntile = (nset + CONN_SETS_TILE - 1) / CONN_SETS_TILE;
-    for (int t = 0, k0 = 0; t < ntile; ++t) {
-        const int nk = (nset - k0 + (ntile - t) - 1) / (ntile - t);
-        const conn_launch_t a = {p.iw, shells, nshell, p.cnt, natm, coords, batch, p.pairs, p.kp, nao, nset, k0, nk, dm,
-                                 rec, npair, st};
+    rc = grad_for_tiles(nset, CONN_SETS_TILE, [&](int k0, int nk) {
         long off = 0;
-        if ((rc = conn_launch<0, 0>(a, off)) != 0) return rc;
-        if ((rc = conn_launch<1, 0>(a, off)) != 0) return rc;
-        if ((rc = conn_launch<1, 1>(a, off)) != 0) return rc;
-        if (off != npair) {
+        const int rt = gto_sp_pairs([&](auto c) { return conn_launch(c, p, nset, k0, nk, dm, off); });
+        if (rt == 0 && off != npair) {
             oovqe_set_error("%s: %ld pair records of %ld", who, off, npair);
-            return OOVQE_ERR_SIZE;
+            return (int)OOVQE_ERR_SIZE;
         }
-        k0 += nk;
-    }
+        return rt;
+    });
+    if (rc != 0) return rc;
     // every (geometry, set) is a row of gto_grad_reduce_kernel: its records summed in that kernel's fixed order
-    return gto_grad_reduce_launch(rec, npair, charges, natm, coords, 0, (long)batch * nset, out, st);
+    return gto_grad_reduce_launch(p.rec, npair, charges, natm, coords, 0, (long)batch * nset, out, st);
 }

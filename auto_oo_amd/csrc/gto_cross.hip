@@ -237,24 +237,24 @@ __global__ __launch_bounds__(GTO_CROSS_NT) void gto_cross_d_kernel(const int* __
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
 struct gto_cross_launch_t {
-    const int* shells; int nshell; const int* cnt; const double* exps; const double* coefs; int natm; int npair;
-    const double* coords_a; const double* coords_b; int nao; double* out; hipStream_t st;
+    const char* who; const int* shells; int nshell; const int* cnt; const double* exps; const double* coefs; int natm;
+    int npair; const double* coords_a; const double* coords_b; int nao; double* out; hipStream_t st;
 };
 
-template <int LA, int LB> int gto_cross_launch(const gto_cross_launch_t& a)
+template <int LA, int LB> int gto_cross_launch(gto_cls_t<LA, LB>, const gto_cross_launch_t& a)
 {
     if (a.cnt[gto_cls(LA, LB)] == 0) return 0;
     const long items = (long)a.npair * a.nshell * a.nshell;
+    unsigned grid;
     if constexpr (LA == 2) {
-        OOVQE_REQUIRE(items < (1L << 31), "oovqe_gto_cross_overlap_batch: %ld workgroups in one launch", items);
-        hipLaunchKernelGGL((gto_cross_d_kernel<LA, LB>), dim3((unsigned)items), dim3(GTO_CROSS_NT), 0, a.st, a.shells,
-                           a.nshell, a.exps, a.coefs, a.natm, a.npair, a.coords_a, a.coords_b, a.nao, a.out);
+        if (const int rc = gto_grid_wg(a.who, items, &grid)) return rc;
+        hipLaunchKernelGGL((gto_cross_d_kernel<LA, LB>), dim3(grid), dim3(GTO_CROSS_NT), 0, a.st, a.shells, a.nshell,
+                           a.exps, a.coefs, a.natm, a.npair, a.coords_a, a.coords_b, a.nao, a.out);
         OOVQE_CHECK_LAUNCH("gto_cross_d_kernel");
     } else {
-        const long blocks = (items * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
-        OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_cross_overlap_batch: %ld workgroups in one launch", blocks);
-        hipLaunchKernelGGL((gto_cross_kernel<LA, LB>), dim3((unsigned)blocks), dim3(GTO_NT), 0, a.st, a.shells,
-                           a.nshell, a.exps, a.coefs, a.natm, a.npair, a.coords_a, a.coords_b, a.nao, a.out);
+        if (const int rc = gto_grid_split(a.who, items, &grid)) return rc;
+        hipLaunchKernelGGL((gto_cross_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, a.st, a.shells, a.nshell, a.exps,
+                           a.coefs, a.natm, a.npair, a.coords_a, a.coords_b, a.nao, a.out);
         OOVQE_CHECK_LAUNCH("gto_cross_kernel");
     }
     return 0;
@@ -273,36 +273,16 @@ extern "C" int oovqe_gto_cross_overlap_batch(int nshell, const int32_t* shells, 
                   npair, natm, nprim_total);
     if (npair == 0) return 0;
     OOVQE_REQUIRE(shells && exps && coefs && coords_a && coords_b && out, "%s: null pointer", who);
-    // the shell table is read back once per call (16 bytes per shell), as gto_prepare does: the limits are enforced
-    // here, with a return code, before anything is launched
-    std::vector<int32_t> tab((size_t)nshell * 4);
-    OOVQE_CHECK_HIP(hipMemcpyAsync(tab.data(), shells, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st), who);
-    OOVQE_CHECK_HIP(hipStreamSynchronize(st), who);
-    int cnt[GTO_NCLS], nl[GTO_LMAX + 1] = {0, 0, 0}, ao = 0;
-    for (int s = 0; s < nshell; ++s) {
-        const int atom = tab[4 * s], field = tab[4 * s + 1], np = tab[4 * s + 2], off = tab[4 * s + 3];
-        const int l = gto_l_of(field);
-        OOVQE_REQUIRE(field >= 0 && l <= OOVQE_GTO_MAX_L && (field == l || (l == 2 && field == (2 | OOVQE_GTO_CARTESIAN))),
-                      "%s: shell %d has the l field %d (l <= %d; OOVQE_GTO_CARTESIAN on a d shell only)", who, s, field,
-                      OOVQE_GTO_MAX_L);
-        OOVQE_REQUIRE(np >= 1 && np <= OOVQE_GTO_MAX_PRIM, "%s: shell %d has %d primitives (1 .. %d)", who, s, np,
-                      OOVQE_GTO_MAX_PRIM);
-        OOVQE_REQUIRE(atom >= 0 && atom < natm, "%s: shell %d sits on atom %d of %d", who, s, atom, natm);
-        OOVQE_REQUIRE(off >= 0 && off + np <= nprim_total, "%s: shell %d reads primitives %d .. %d of %d", who, s,
-                      off, off + np - 1, nprim_total);
-        ao += gto_nfunc(field);
-        nl[l] += 1;
-    }
-    OOVQE_REQUIRE(ao == nao, "%s: the shell table has %d functions, nao = %d", who, ao, nao);
+    // the shell table is read back and checked as gto_prepare does it (every l this library has is served here): the
+    // limits are enforced with a return code, before anything is launched
+    std::vector<int32_t> tab;
+    const int rc = gto_read_shells(who, OOVQE_GTO_MAX_L, nshell, shells, nprim_total, natm, nao, st, &tab);
+    if (rc != 0) return rc;
+    int cnt[GTO_NCLS], nl[GTO_LMAX + 1] = {0, 0, 0};
+    for (int s = 0; s < nshell; ++s) nl[gto_l_of(tab[4 * s + 1])] += 1;
     for (int la = 0; la <= GTO_LMAX; ++la)
         for (int lb = 0; lb <= la; ++lb) cnt[gto_cls(la, lb)] = nl[la] * nl[lb];
-    const gto_cross_launch_t a = {shells, nshell, cnt, exps, coefs, natm, npair, coords_a, coords_b, nao, out, st};
-    int rc;
-    if ((rc = gto_cross_launch<2, 2>(a)) != 0) return rc;
-    if ((rc = gto_cross_launch<2, 1>(a)) != 0) return rc;
-    if ((rc = gto_cross_launch<2, 0>(a)) != 0) return rc;
-    if ((rc = gto_cross_launch<0, 0>(a)) != 0) return rc;
-    if ((rc = gto_cross_launch<1, 0>(a)) != 0) return rc;
-    return gto_cross_launch<1, 1>(a);
+    const gto_cross_launch_t a = {who, shells, nshell, cnt, exps, coefs, natm, npair, coords_a, coords_b, nao, out, st};
+    return gto_pairs_d_first([&](auto c) { return gto_cross_launch(c, a); });
 }
 #endif  // GTO_CROSS_BODIES_ONLY

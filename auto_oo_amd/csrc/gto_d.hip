@@ -397,48 +397,43 @@ __global__ __launch_bounds__((gto_dq_lds_t<LA, LB, LC, LD>::NT)) void gto_d_eri_
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
-template <int LA, int LB> int gto_d_launch_one(const gto_launch_t& a)
+template <int LA, int LB> int gto_d_launch_one(gto_cls_t<LA, LB>, const gto_prep_t& p, double* overlap, double* h_ao)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    const long blocks = (long)count * a.batch;
-    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_integrals_batch: %ld workgroups in one launch", blocks);
-    hipLaunchKernelGGL((gto_d_one_kernel<LA, LB>), dim3((unsigned)blocks), dim3(GTO_D1_NT), 0, a.st, a.iw, a.shells,
-                       a.nshell, count, a.charges, a.natm, a.coords, a.batch, a.pairs, a.kp, a.nao, a.overlap, a.h_ao);
+    unsigned grid;
+    if (const int rc = gto_grid_wg(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_d_one_kernel<LA, LB>), dim3(grid), dim3(GTO_D1_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                       p.charges, p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, overlap, h_ao);
     OOVQE_CHECK_LAUNCH("gto_d_one_kernel");
     return 0;
 }
 
-template <int LA, int LB, int LC, int LD> int gto_d_launch_eri(const gto_launch_t& a)
+template <int LA, int LB, int LC, int LD> int gto_d_launch_eri(const gto_prep_t& p, double* g_ao)
 {
-    const int nbra = a.cnt[gto_cls(LA, LB)], nket = a.cnt[gto_cls(LC, LD)];
-    const bool same = (LA == LC && LB == LD);
-    const long nq = same ? (long)nbra * (nbra + 1) / 2 : (long)nbra * nket;
+    const int nbra = p.cnt[gto_cls(LA, LB)], nket = p.cnt[gto_cls(LC, LD)];
+    const long nq = gto_quartets(LA == LC && LB == LD, nbra, nket);
     if (nq == 0) return 0;
-    const long blocks = nq * a.batch;
-    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_integrals_batch: %ld workgroups in one launch", blocks);
-    hipLaunchKernelGGL((gto_d_eri_kernel<LA, LB, LC, LD>), dim3((unsigned)blocks),
-                       dim3(gto_dq_lds_t<LA, LB, LC, LD>::NT), 0, a.st, a.iw, a.shells, a.nshell, nbra, nket, nq,
-                       a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao, a.g_ao);
+    unsigned grid;
+    if (const int rc = gto_grid_wg(p.who, nq * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_d_eri_kernel<LA, LB, LC, LD>), dim3(grid), dim3(gto_dq_lds_t<LA, LB, LC, LD>::NT), 0, p.st,
+                       p.iw, p.shells, p.nshell, nbra, nket, nq, p.coords, p.natm, p.batch, p.pairs, p.kp, p.nao, g_ao);
     OOVQE_CHECK_LAUNCH("gto_d_eri_kernel");
     return 0;
 }
 }  // namespace
 
-int gto_d_launch_one_electron(const gto_launch_t& a)
+int gto_d_launch_one_electron(const gto_prep_t& p, double* overlap, double* h_ao)
 {
-    int rc;
-    if ((rc = gto_d_launch_one<2, 2>(a)) != 0) return rc;
-    if ((rc = gto_d_launch_one<2, 1>(a)) != 0) return rc;
-    return gto_d_launch_one<2, 0>(a);
+    return gto_d_pairs([&](auto c) { return gto_d_launch_one(c, p, overlap, h_ao); });
 }
 
 // bra class >= ket class, the longest workgroups first
-int gto_d_launch_two_electron(const gto_launch_t& a)
+int gto_d_launch_two_electron(const gto_prep_t& p, double* g_ao)
 {
     int rc;
 #define GTO_D_ERI(la, lb, lc, ld) \
-    if ((rc = gto_d_launch_eri<la, lb, lc, ld>(a)) != 0) return rc
+    if ((rc = gto_d_launch_eri<la, lb, lc, ld>(p, g_ao)) != 0) return rc
     GTO_D_ERI(2, 2, 2, 2); GTO_D_ERI(2, 2, 2, 1); GTO_D_ERI(2, 2, 2, 0); GTO_D_ERI(2, 2, 1, 1); GTO_D_ERI(2, 2, 1, 0);
     GTO_D_ERI(2, 2, 0, 0);
     GTO_D_ERI(2, 1, 2, 1); GTO_D_ERI(2, 1, 2, 0); GTO_D_ERI(2, 1, 1, 1); GTO_D_ERI(2, 1, 1, 0); GTO_D_ERI(2, 1, 0, 0);

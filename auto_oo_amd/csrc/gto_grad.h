@@ -1,5 +1,7 @@
 // Shared by the nuclear-derivative kernels of gto_grad.hip and gto_grad_sets.hip: the record of a pair / quartet, the
-// small sums over Hermite indices, derivative coefficients, and the count of records of a call.
+// small sums over Hermite indices, derivative coefficients, and the count of records of a call; and the host code the
+// derivative entries (those two, gto_connection.hip) share: the nset check, the fork onto the internal stream, the split
+// of the sets into tiles and the ladder over the quartet classes and their sides.
 #pragma once
 #include "gto.h"
 
@@ -114,4 +116,96 @@ int gto_grad_reduce_launch(const double* rec, long nrec, const double* charges, 
 template <int LA, int LB, int LC, int LD> constexpr int grad_parts()
 {
     return (LA + LB + LC + LD == 4) ? GRAD_PPPP_PARTS : 1;
+}
+
+// ---- host side shared by the derivative entries -----------------------------------------------------------------------
+static inline int grad_check_nset(const char* who, int nset)
+{
+    OOVQE_REQUIRE(nset >= 1 && nset <= OOVQE_GTO_GRAD_MAX_SETS, "%s: nset = %d (1 .. %d)", who, nset,
+                  OOVQE_GTO_GRAD_MAX_SETS);
+    return 0;
+}
+
+// the records of the terms asked for, one-electron pairs first
+static inline long grad_nrec(const gto_prep_t& p, bool one, bool two)
+{
+    const long npair = p.npair(), npp = p.cnt[gto_cls(1, 1)];
+    return (one ? npair * (p.natm + 1) : 0) + (two ? npair * (npair + 1) + (GRAD_PPPP_PARTS - 1) * npp * (npp + 1) : 0);
+}
+
+// The launches of a call are independent of each other up to the reduction, and each lasts as long as one lane's chain
+// of primitive quartets while filling a fraction of the chip: the second sides of the quartets run on the library's
+// internal stream, forked from the caller's stream behind the pair data and joined in front of the reduction.  Every
+// launch writes its own records, so the result does not depend on how they overlap.
+// fork() leaves side = st where no fork is wanted or the library has no second stream; join() is called on the one way
+// out of the launches, whatever they returned, and the destructor joins on any other: the caller's stream never runs
+// ahead of the fork.  (gto_grad.hip)
+struct grad_fork_t {
+    const char* who = nullptr;
+    hipStream_t st = nullptr, side = nullptr;
+    hipEvent_t ev_join = nullptr;
+    int fork(const char* who, hipStream_t st, bool wanted);
+    int join();
+    ~grad_fork_t() { (void)join(); }
+};
+
+// the sets spread evenly over the fewest tiles of at most `tile`: 10 -> 5 + 5, 6 -> 3 + 3 (a set's bits do not depend on
+// the split); f(k0, nk) for every tile, up to the first return code that is not 0
+template <class F> int grad_for_tiles(int nset, int tile, F&& f)
+{
+    const int ntile = (nset + tile - 1) / tile;
+    int rc = 0;
+    for (int t = 0, k0 = 0; t < ntile && rc == 0; ++t) {
+        const int nk = (nset - k0 + (ntile - t) - 1) / (ntile - t);
+        rc = f(k0, nk);
+        k0 += nk;
+    }
+    return rc;
+}
+
+// One side of the quartets of a bra class and a ket class of the enumeration, the other side's first shell restricted
+// to component PART of NPART, as a value (gto_cls_t): the launcher of an entry deduces its kernel from it.
+template <int LA, int LB, int LC, int LD, bool SWAP, int PART, int NPART> struct grad_side_t {};
+
+// both sides of the quartets of bra class (LA, LB) and ket class (LC, LD): side(grad_side_t, grid, nbra, nket, nq, off)
+// launches one
+template <int LA, int LB, int LC, int LD, class S>
+int grad_launch_eri(gto_cls_t<LA, LB, LC, LD>, const gto_prep_t& p, long& off, S&& side)
+{
+    const int nbra = p.cnt[gto_cls(LA, LB)], nket = p.cnt[gto_cls(LC, LD)];
+    const long nq = gto_quartets(LA == LC && LB == LD, nbra, nket);
+    if (nq == 0) return 0;
+    constexpr int NP = grad_parts<LA, LB, LC, LD>();
+    unsigned grid;
+    int rc = gto_grid_split(p.who, nq * p.batch, &grid);
+    static_for<NP>([&](auto part) {
+        if (rc == 0) rc = side(grad_side_t<LA, LB, LC, LD, false, decltype(part)::value, NP>{}, grid, nbra, nket, nq, off);
+    });
+    static_for<NP>([&](auto part) {
+        if (rc == 0) rc = side(grad_side_t<LC, LD, LA, LB, true, decltype(part)::value, NP>{}, grid, nbra, nket, nq, off);
+    });
+    if (rc == 0) off += 2 * nq * NP;
+    return rc;
+}
+
+// The launches of one call (of one tile of sets): the quartets (`two`) through side(...) as above, the long threads of
+// (pp|pp) first, as in oovqe_gto_integrals_batch; their records lie behind the pairs'.  Then the pairs (`one`) through
+// pair(gto_cls_t, off), which launches a class and advances off by its records.
+template <class S, class O> int grad_launch_all(const gto_prep_t& p, bool one, bool two, long nrec, S&& side, O&& pair)
+{
+    long off = 0;
+    int rc = 0;
+    if (two) {
+        off = one ? p.npair() * (p.natm + 1) : 0;
+        rc = gto_sp_quartets([&](auto c) { return grad_launch_eri(c, p, off, side); });
+        if (rc == 0 && off != nrec) {
+            oovqe_set_error("%s: %ld quartet records of %ld", p.who, off, nrec);
+            rc = OOVQE_ERR_SIZE;
+        }
+    }
+    if (one && rc == 0) {
+        off = 0;
+        rc = gto_sp_pairs([&](auto c) { return pair(c, off); });
+    }
+    return rc;
 }

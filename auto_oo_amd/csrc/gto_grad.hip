@@ -458,67 +458,62 @@ extern "C" int64_t oovqe_gto_gradient_work_size(int nshell, int max_nprim, int n
     const char* who = "oovqe_gto_gradient_work_size";
     if (gto_check_sizes(who, nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(natm >= 1, "%s: natm = %d", who, natm);
-    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
-    const int64_t base = gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
-    return base + (int64_t)batch * grad_records(nshell, natm) * GRAD_REC;
+    return gto_work_base(nshell, max_nprim, batch) + (int64_t)batch * grad_records(nshell, natm) * GRAD_REC;
+}
+
+int grad_fork_t::fork(const char* who_, hipStream_t st_, bool wanted)
+{
+    who = who_;
+    st = side = st_;
+    if (!wanted) return 0;
+    hipStream_t si = oovqe_internal_stream(0);
+    hipEvent_t ev_fork = oovqe_internal_event();
+    ev_join = oovqe_internal_event();
+    if (si && si != st && ev_fork && ev_join) {
+        OOVQE_CHECK_HIP(hipEventRecord(ev_fork, st), who);
+        OOVQE_CHECK_HIP(hipStreamWaitEvent(si, ev_fork, 0), who);
+        side = si;
+    }
+    return 0;
+}
+
+int grad_fork_t::join()
+{
+    if (side == st) return 0;
+    hipStream_t forked = side;
+    side = st;
+    OOVQE_CHECK_HIP(hipEventRecord(ev_join, forked), who);
+    OOVQE_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0), who);
+    return 0;
 }
 
 namespace {
-struct grad_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
-    const double* coords; int batch; const double* pairs; int kp; int nao; const double* d1; const double* wq;
-    const double* d2; double* rec; long nrec; hipStream_t st;
-    hipStream_t st2;            // the launches of the quartets' second sides (st itself, or a stream forked from it)
+struct grad_args_t {
+    const double* d1; const double* wq; const double* d2; long nrec;
+    hipStream_t side;           // the launches of the quartets' second sides (grad_fork_t)
 };
 
-template <int LA, int LB> int grad_launch_one(const grad_launch_t& a, long& off)
+template <int LA, int LB> int grad_launch_one(gto_cls_t<LA, LB>, const gto_prep_t& p, const grad_args_t& a, long& off)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    const long total = (long)count * a.batch * GTO_SPLIT;
-    hipLaunchKernelGGL((gto_grad_one_kernel<LA, LB>), dim3((unsigned)((total + GTO_NT - 1) / GTO_NT)), dim3(GTO_NT), 0,
-                       a.st, a.iw, a.shells, a.nshell, count, a.charges, a.natm, a.coords, a.batch, a.pairs, a.kp,
-                       a.nao, a.d1, a.wq, a.rec, off, a.nrec);
+    unsigned grid;
+    if (const int rc = gto_grid_split(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_grad_one_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                       p.charges, p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, a.d1, a.wq, p.rec, off, a.nrec);
     OOVQE_CHECK_LAUNCH("gto_grad_one_kernel");
-    off += (long)count * (a.natm + 1);
+    off += (long)count * (p.natm + 1);
     return 0;
 }
 
-// One side of the quartets of bra class and ket class of the enumeration, the other side's first shell restricted to
-// component PART of NPART.
 template <int LA, int LB, int LC, int LD, bool SWAP, int PART, int NPART>
-int grad_launch_side(const grad_launch_t& a, long off, int nbra, int nket, long nq)
+int grad_launch_side(grad_side_t<LA, LB, LC, LD, SWAP, PART, NPART>, const gto_prep_t& p, const grad_args_t& a,
+                     unsigned grid, int nbra, int nket, long nq, long off)
 {
-    const long blocks = (nq * a.batch * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
-    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_gradient_batch: %ld workgroups in one launch", blocks);
-    hipLaunchKernelGGL((gto_grad_eri_kernel<LA, LB, LC, LD, SWAP, PART, NPART>), dim3((unsigned)blocks), dim3(GTO_NT), 0,
-                       SWAP ? a.st2 : a.st, a.iw, a.shells, a.nshell, nbra, nket, nq, a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao,
-                       a.d2, a.rec, off, a.nrec);
+    hipLaunchKernelGGL((gto_grad_eri_kernel<LA, LB, LC, LD, SWAP, PART, NPART>), dim3(grid), dim3(GTO_NT), 0,
+                       SWAP ? a.side : p.st, p.iw, p.shells, p.nshell, nbra, nket, nq, p.coords, p.natm, p.batch, p.pairs,
+                       p.kp, p.nao, a.d2, p.rec, off, a.nrec);
     OOVQE_CHECK_LAUNCH("gto_grad_eri_kernel");
-    return 0;
-}
-
-
-// both sides of the quartets of bra class (LA, LB) and ket class (LC, LD)
-template <int LA, int LB, int LC, int LD> int grad_launch_eri(const grad_launch_t& a, long& off)
-{
-    const int nbra = a.cnt[gto_cls(LA, LB)], nket = a.cnt[gto_cls(LC, LD)];
-    const bool same = (LA == LC && LB == LD);
-    const long nq = same ? (long)nbra * (nbra + 1) / 2 : (long)nbra * nket;
-    if (nq == 0) return 0;
-    int rc = 0;
-    if constexpr (grad_parts<LA, LB, LC, LD>() == 3) {
-        if ((rc = grad_launch_side<LA, LB, LC, LD, false, 0, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LA, LB, LC, LD, false, 1, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LA, LB, LC, LD, false, 2, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LC, LD, LA, LB, true, 0, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LC, LD, LA, LB, true, 1, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LC, LD, LA, LB, true, 2, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-    } else {
-        if ((rc = grad_launch_side<LA, LB, LC, LD, false, 0, 1>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = grad_launch_side<LC, LD, LA, LB, true, 0, 1>(a, off, nbra, nket, nq)) != 0) return rc;
-    }
-    off += 2 * nq * grad_parts<LA, LB, LC, LD>();
     return 0;
 }
 }  // namespace
@@ -538,65 +533,19 @@ extern "C" int oovqe_gto_gradient_batch(int nshell, const int32_t* shells, int n
                          st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(grad, "%s: null pointer", who);
-    const long npair = (long)nshell * (nshell + 1) / 2;
-    const bool one = d1 || wq;
-    // the records of the terms asked for, one-electron pairs first
-    long nrec = 0;
-    if (one) nrec += npair * (natm + 1);
-    if (d2) {
-        const long npp = p.cnt[gto_cls(1, 1)];
-        nrec += npair * (npair + 1) + (GRAD_PPPP_PARTS - 1) * npp * (npp + 1);
-    }
-    double* rec = p.pairs + (size_t)batch * npair * p.kp * GTO_PW;
-    // The launches of a call are independent of each other up to the reduction, and each lasts as long as one lane's
-    // chain of primitive quartets while filling a fraction of the chip: the second sides of the quartets run on the
-    // library's internal stream, forked from the caller's stream behind the pair data and joined in front of the
-    // reduction.  Every launch writes its own records, so the result does not depend on how they overlap.
-    hipStream_t st2 = st;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (d2) {
-        hipStream_t si = oovqe_internal_stream(0);
-        ev_fork = oovqe_internal_event();
-        ev_join = oovqe_internal_event();
-        if (si && si != st && ev_fork && ev_join) {
-            OOVQE_CHECK_HIP(hipEventRecord(ev_fork, st), who);
-            OOVQE_CHECK_HIP(hipStreamWaitEvent(si, ev_fork, 0), who);
-            st2 = si;
-        }
-    }
-    const grad_launch_t a = {p.iw, shells, nshell, p.cnt, charges, natm, coords, batch, p.pairs, p.kp, nao, d1, wq, d2,
-                             rec, nrec, st, st2};
-    long off = 0;
-    rc = 0;
-    if (d2) {
-        // the long threads of (pp|pp) first, as in oovqe_gto_integrals_batch; their records lie behind the pairs'
-        off = one ? npair * (natm + 1) : 0;
-        if (rc == 0) rc = grad_launch_eri<1, 1, 1, 1>(a, off);
-        if (rc == 0) rc = grad_launch_eri<1, 1, 1, 0>(a, off);
-        if (rc == 0) rc = grad_launch_eri<1, 1, 0, 0>(a, off);
-        if (rc == 0) rc = grad_launch_eri<1, 0, 1, 0>(a, off);
-        if (rc == 0) rc = grad_launch_eri<1, 0, 0, 0>(a, off);
-        if (rc == 0) rc = grad_launch_eri<0, 0, 0, 0>(a, off);
-        if (rc == 0 && off != nrec) {
-            oovqe_set_error("%s: %ld quartet records of %ld", who, off, nrec);
-            rc = OOVQE_ERR_SIZE;
-        }
-    }
-    if (one && rc == 0) {
-        off = 0;
-        if (rc == 0) rc = grad_launch_one<0, 0>(a, off);
-        if (rc == 0) rc = grad_launch_one<1, 0>(a, off);
-        if (rc == 0) rc = grad_launch_one<1, 1>(a, off);
-    }
-    if (st2 != st) {        // (joined whatever happened above: the caller's stream never runs ahead of the fork)
-        OOVQE_CHECK_HIP(hipEventRecord(ev_join, st2), who);
-        OOVQE_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0), who);
-    }
+    const bool one = d1 || wq, two = d2 != nullptr;
+    grad_fork_t fk;
+    if ((rc = fk.fork(who, st, two)) != 0) return rc;
+    const grad_args_t a = {d1, wq, d2, grad_nrec(p, one, two), fk.side};
+    rc = grad_launch_all(
+        p, one, two, a.nrec,
+        [&](auto s, unsigned grid, int nbra, int nket, long nq, long off) {
+            return grad_launch_side(s, p, a, grid, nbra, nket, nq, off);
+        },
+        [&](auto c, long& off) { return grad_launch_one(c, p, a, off); });
+    if (const int rj = fk.join()) return rj;        // (joined whatever happened above)
     if (rc != 0) return rc;
-    hipLaunchKernelGGL(gto_grad_reduce_kernel, dim3(natm, batch), dim3(GRAD_RT), 0, st, rec, nrec, charges, natm, coords,
-                       with_nuc ? 1 : 0, grad);
-    OOVQE_CHECK_LAUNCH("gto_grad_reduce_kernel");
-    return 0;
+    return gto_grad_reduce_launch(p.rec, a.nrec, charges, natm, coords, with_nuc, batch, grad, st);
 }
 
 extern "C" int oovqe_cas_ao_densities_batch(const double* mo_coeff, int n, int n_core, int ncas, const double* gamma,

@@ -372,108 +372,45 @@ __global__ __launch_bounds__(GRAD_RT) void gto_grad_sets_reduce_kernel(const dou
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-static int sets_check(const char* who, int nset)
-{
-    OOVQE_REQUIRE(nset >= 1 && nset <= OOVQE_GTO_GRAD_MAX_SETS, "%s: nset = %d (1 .. %d)", who, nset,
-                  OOVQE_GTO_GRAD_MAX_SETS);
-    return 0;
-}
-
 // (for nset = 1 the size of oovqe_gto_gradient_work_size: the records of a set are those of the single-set entry)
 extern "C" int64_t oovqe_gto_gradient_sets_work_size(int nshell, int max_nprim, int natm, int batch, int nset)
 {
     const char* who = "oovqe_gto_gradient_sets_work_size";
     if (gto_check_sizes(who, nshell, max_nprim, batch) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(natm >= 1, "%s: natm = %d", who, natm);
-    if (sets_check(who, nset) != 0) return OOVQE_ERR_ARG;
-    const int64_t npair = (int64_t)nshell * (nshell + 1) / 2;
-    const int64_t base = gto_int_doubles(nshell) + (int64_t)batch * npair * max_nprim * max_nprim * GTO_PW;
-    return base + (int64_t)batch * nset * grad_records(nshell, natm) * GRAD_REC;
+    if (grad_check_nset(who, nset) != 0) return OOVQE_ERR_ARG;
+    return gto_work_base(nshell, max_nprim, batch) + (int64_t)batch * nset * grad_records(nshell, natm) * GRAD_REC;
 }
 
 namespace {
-struct sets_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; const double* charges; int natm;
-    const double* coords; int batch; const double* pairs; int kp; int nao; int nset; int k0; int nk;
-    const double* d1; const double* wq; const double* d2; double* rec; long nrec; hipStream_t st;
-    hipStream_t st2;            // the launches of the quartets' second sides (st itself, or a stream forked from it)
+struct sets_args_t {
+    int nset; int k0; int nk; const double* d1; const double* wq; const double* d2; long nrec;
+    hipStream_t side;           // the launches of the quartets' second sides (grad_fork_t)
 };
 
-template <int LA, int LB> int sets_launch_one(const sets_launch_t& a, long& off)
+template <int LA, int LB> int sets_launch_one(gto_cls_t<LA, LB>, const gto_prep_t& p, const sets_args_t& a, long& off)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
-    const long total = (long)count * a.batch * GTO_SPLIT;
-    hipLaunchKernelGGL((gto_grad_sets_one_kernel<LA, LB>), dim3((unsigned)((total + GTO_NT - 1) / GTO_NT)), dim3(GTO_NT),
-                       0, a.st, a.iw, a.shells, a.nshell, count, a.charges, a.natm, a.coords, a.batch, a.pairs, a.kp,
-                       a.nao, a.nset, a.k0, a.nk, a.d1, a.wq, a.rec, off, a.nrec);
+    unsigned grid;
+    if (const int rc = gto_grid_split(p.who, (long)count * p.batch, &grid)) return rc;
+    hipLaunchKernelGGL((gto_grad_sets_one_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell,
+                       count, p.charges, p.natm, p.coords, p.batch, p.pairs, p.kp, p.nao, a.nset, a.k0, a.nk, a.d1, a.wq,
+                       p.rec, off, a.nrec);
     OOVQE_CHECK_LAUNCH("gto_grad_sets_one_kernel");
-    off += (long)count * (a.natm + 1);
+    off += (long)count * (p.natm + 1);
     return 0;
 }
 
 template <int LA, int LB, int LC, int LD, bool SWAP, int PART, int NPART>
-int sets_launch_side(const sets_launch_t& a, long off, int nbra, int nket, long nq)
+int sets_launch_side(grad_side_t<LA, LB, LC, LD, SWAP, PART, NPART>, const gto_prep_t& p, const sets_args_t& a,
+                     unsigned grid, int nbra, int nket, long nq, long off)
 {
-    const long blocks = (nq * a.batch * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
-    OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_gradient_sets_batch: %ld workgroups in one launch", blocks);
-    hipLaunchKernelGGL((gto_grad_sets_eri_kernel<LA, LB, LC, LD, SWAP, PART, NPART>), dim3((unsigned)blocks),
-                       dim3(GTO_NT), 0, SWAP ? a.st2 : a.st, a.iw, a.shells, a.nshell, nbra, nket, nq, a.coords, a.natm,
-                       a.batch, a.pairs, a.kp, a.nao, a.nset, a.k0, a.nk, a.d2, a.rec, off, a.nrec);
+    hipLaunchKernelGGL((gto_grad_sets_eri_kernel<LA, LB, LC, LD, SWAP, PART, NPART>), dim3(grid), dim3(GTO_NT), 0,
+                       SWAP ? a.side : p.st, p.iw, p.shells, p.nshell, nbra, nket, nq, p.coords, p.natm, p.batch, p.pairs,
+                       p.kp, p.nao, a.nset, a.k0, a.nk, a.d2, p.rec, off, a.nrec);
     OOVQE_CHECK_LAUNCH("gto_grad_sets_eri_kernel");
     return 0;
-}
-
-// both sides of the quartets of bra class (LA, LB) and ket class (LC, LD)
-template <int LA, int LB, int LC, int LD> int sets_launch_eri(const sets_launch_t& a, long& off)
-{
-    const int nbra = a.cnt[gto_cls(LA, LB)], nket = a.cnt[gto_cls(LC, LD)];
-    const bool same = (LA == LC && LB == LD);
-    const long nq = same ? (long)nbra * (nbra + 1) / 2 : (long)nbra * nket;
-    if (nq == 0) return 0;
-    int rc = 0;
-    if constexpr (grad_parts<LA, LB, LC, LD>() == 3) {
-        if ((rc = sets_launch_side<LA, LB, LC, LD, false, 0, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LA, LB, LC, LD, false, 1, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LA, LB, LC, LD, false, 2, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LC, LD, LA, LB, true, 0, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LC, LD, LA, LB, true, 1, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LC, LD, LA, LB, true, 2, 3>(a, off, nbra, nket, nq)) != 0) return rc;
-    } else {
-        if ((rc = sets_launch_side<LA, LB, LC, LD, false, 0, 1>(a, off, nbra, nket, nq)) != 0) return rc;
-        if ((rc = sets_launch_side<LC, LD, LA, LB, true, 0, 1>(a, off, nbra, nket, nq)) != 0) return rc;
-    }
-    off += 2 * nq * grad_parts<LA, LB, LC, LD>();
-    return 0;
-}
-
-// the launches of one tile of sets
-int sets_launch_tile(sets_launch_t a, const char* who, long npair)
-{
-    const bool one = a.d1 || a.wq;
-    long off = 0;
-    int rc = 0;
-    if (a.d2) {
-        // the long threads of (pp|pp) first; their records lie behind the pairs'
-        off = one ? npair * (a.natm + 1) : 0;
-        if (rc == 0) rc = sets_launch_eri<1, 1, 1, 1>(a, off);
-        if (rc == 0) rc = sets_launch_eri<1, 1, 1, 0>(a, off);
-        if (rc == 0) rc = sets_launch_eri<1, 1, 0, 0>(a, off);
-        if (rc == 0) rc = sets_launch_eri<1, 0, 1, 0>(a, off);
-        if (rc == 0) rc = sets_launch_eri<1, 0, 0, 0>(a, off);
-        if (rc == 0) rc = sets_launch_eri<0, 0, 0, 0>(a, off);
-        if (rc == 0 && off != a.nrec) {
-            oovqe_set_error("%s: %ld quartet records of %ld", who, off, a.nrec);
-            rc = OOVQE_ERR_SIZE;
-        }
-    }
-    if (one && rc == 0) {
-        off = 0;
-        if (rc == 0) rc = sets_launch_one<0, 0>(a, off);
-        if (rc == 0) rc = sets_launch_one<1, 0>(a, off);
-        if (rc == 0) rc = sets_launch_one<1, 1>(a, off);
-    }
-    return rc;
 }
 }  // namespace
 
@@ -486,51 +423,30 @@ extern "C" int oovqe_gto_gradient_sets_batch(int nshell, const int32_t* shells, 
     const char* who = "oovqe_gto_gradient_sets_batch";
     hipStream_t st = (hipStream_t)stream;
     gto_prep_t p;
-    if (sets_check(who, nset) != 0) return OOVQE_ERR_ARG;
+    if (grad_check_nset(who, nset) != 0) return OOVQE_ERR_ARG;
     OOVQE_REQUIRE(batch <= 65535, "%s: batch = %d (at most 65535 geometries per call)", who, batch);
     // (a table with l = 2 is refused here, before any launch, as by oovqe_gto_gradient_batch)
     int rc = gto_prepare(who, 1, nshell, shells, nprim_total, exps, coefs, natm, charges, batch, coords, nao, nullptr, work,
                          st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(grad, "%s: null pointer", who);
-    const long npair = (long)nshell * (nshell + 1) / 2;
-    const bool one = d1 || wq;
-    long nrec = 0;
-    if (one) nrec += npair * (natm + 1);
-    if (d2) {
-        const long npp = p.cnt[gto_cls(1, 1)];
-        nrec += npair * (npair + 1) + (GRAD_PPPP_PARTS - 1) * npp * (npp + 1);
-    }
-    double* rec = p.pairs + (size_t)batch * npair * p.kp * GTO_PW;
+    const bool one = d1 || wq, two = d2 != nullptr;
+    const long nrec = grad_nrec(p, one, two);
     // second sides on the library's internal stream, as in oovqe_gto_gradient_batch
-    hipStream_t st2 = st;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (d2) {
-        hipStream_t si = oovqe_internal_stream(0);
-        ev_fork = oovqe_internal_event();
-        ev_join = oovqe_internal_event();
-        if (si && si != st && ev_fork && ev_join) {
-            OOVQE_CHECK_HIP(hipEventRecord(ev_fork, st), who);
-            OOVQE_CHECK_HIP(hipStreamWaitEvent(si, ev_fork, 0), who);
-            st2 = si;
-        }
-    }
-    // the sets spread evenly over the fewest tiles: 10 -> 5 + 5, 6 -> 3 + 3 (a set's bits do not depend on the split)
-    const int ntile = (nset + GRAD_SETS_TILE - 1) / GRAD_SETS_TILE;
-    rc = 0;
-    for (int t = 0, k0 = 0; t < ntile && rc == 0; ++t) {
-        const int nk = (nset - k0 + (ntile - t) - 1) / (ntile - t);
-        const sets_launch_t a = {p.iw, shells, nshell, p.cnt, charges, natm, coords, batch, p.pairs, p.kp, nao, nset, k0, nk,
-                                 d1, wq, d2, rec, nrec, st, st2};
-        rc = sets_launch_tile(a, who, npair);
-        k0 += nk;
-    }
-    if (st2 != st) {        // (joined whatever happened above: the caller's stream never runs ahead of the fork)
-        OOVQE_CHECK_HIP(hipEventRecord(ev_join, st2), who);
-        OOVQE_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0), who);
-    }
+    grad_fork_t fk;
+    if ((rc = fk.fork(who, st, two)) != 0) return rc;
+    rc = grad_for_tiles(nset, GRAD_SETS_TILE, [&](int k0, int nk) {
+        const sets_args_t a = {nset, k0, nk, d1, wq, d2, nrec, fk.side};
+        return grad_launch_all(
+            p, one, two, nrec,
+            [&](auto s, unsigned grid, int nbra, int nket, long nq, long off) {
+                return sets_launch_side(s, p, a, grid, nbra, nket, nq, off);
+            },
+            [&](auto c, long& off) { return sets_launch_one(c, p, a, off); });
+    });
+    if (const int rj = fk.join()) return rj;        // (joined whatever happened above)
     if (rc != 0) return rc;
-    hipLaunchKernelGGL(gto_grad_sets_reduce_kernel, dim3(natm, batch, nset), dim3(GRAD_RT), 0, st, rec, nrec, charges,
+    hipLaunchKernelGGL(gto_grad_sets_reduce_kernel, dim3(natm, batch, nset), dim3(GRAD_RT), 0, st, p.rec, nrec, charges,
                        natm, coords, nset, nuc_mask, grad);
     OOVQE_CHECK_LAUNCH("gto_grad_sets_reduce_kernel");
     return 0;

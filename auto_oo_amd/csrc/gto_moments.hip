@@ -281,28 +281,21 @@ __global__ __launch_bounds__(GTO_MOM_RT) void gto_mom_expect_kernel(const double
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
-struct gto_mom_launch_t {
-    const int* iw; const int* shells; int nshell; const int* cnt; const double* coords; int natm; int batch;
-    const double* pairs; int kp; int nao; int ncomp; const double* origin; double* moments; hipStream_t st;
-};
-
-template <int LA, int LB> int gto_mom_launch(const gto_mom_launch_t& a)
+template <int LA, int LB>
+int gto_mom_launch(gto_cls_t<LA, LB>, const gto_prep_t& p, int ncomp, const double* origin, double* moments)
 {
-    const int count = a.cnt[gto_cls(LA, LB)];
+    const int count = p.cnt[gto_cls(LA, LB)];
     if (count == 0) return 0;
+    unsigned grid;
     if constexpr (LA == 2) {
-        const long blocks = (long)count * a.batch;
-        OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_moments_batch: %ld workgroups in one launch", blocks);
-        hipLaunchKernelGGL((gto_mom_d_kernel<LA, LB>), dim3((unsigned)blocks), dim3(GTO_MOM_NT), 0, a.st, a.iw,
-                           a.shells, a.nshell, count, a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao, a.ncomp,
-                           a.origin, a.moments);
+        if (const int rc = gto_grid_wg(p.who, (long)count * p.batch, &grid)) return rc;
+        hipLaunchKernelGGL((gto_mom_d_kernel<LA, LB>), dim3(grid), dim3(GTO_MOM_NT), 0, p.st, p.iw, p.shells, p.nshell,
+                           count, p.coords, p.natm, p.batch, p.pairs, p.kp, p.nao, ncomp, origin, moments);
         OOVQE_CHECK_LAUNCH("gto_mom_d_kernel");
     } else {
-        const long blocks = ((long)count * a.batch * GTO_SPLIT + GTO_NT - 1) / GTO_NT;
-        OOVQE_REQUIRE(blocks < (1L << 31), "oovqe_gto_moments_batch: %ld workgroups in one launch", blocks);
-        hipLaunchKernelGGL((gto_mom_kernel<LA, LB>), dim3((unsigned)blocks), dim3(GTO_NT), 0, a.st, a.iw, a.shells,
-                           a.nshell, count, a.coords, a.natm, a.batch, a.pairs, a.kp, a.nao, a.ncomp, a.origin,
-                           a.moments);
+        if (const int rc = gto_grid_split(p.who, (long)count * p.batch, &grid)) return rc;
+        hipLaunchKernelGGL((gto_mom_kernel<LA, LB>), dim3(grid), dim3(GTO_NT), 0, p.st, p.iw, p.shells, p.nshell, count,
+                           p.coords, p.natm, p.batch, p.pairs, p.kp, p.nao, ncomp, origin, moments);
         OOVQE_CHECK_LAUNCH("gto_mom_kernel");
     }
     return 0;
@@ -323,14 +316,8 @@ extern "C" int oovqe_gto_moments_batch(int nshell, const int32_t* shells, int np
                          nao, nullptr, work, st, &p);
     if (rc != 0 || batch == 0) return rc;
     OOVQE_REQUIRE(moments, "%s: null pointer", who);
-    const gto_mom_launch_t a = {p.iw, shells, nshell, p.cnt, coords, natm, batch, p.pairs, p.kp, nao,
-                                order == 1 ? 3 : GTO_MOM_NC, origin, moments, st};
-    if ((rc = gto_mom_launch<2, 2>(a)) != 0) return rc;
-    if ((rc = gto_mom_launch<2, 1>(a)) != 0) return rc;
-    if ((rc = gto_mom_launch<2, 0>(a)) != 0) return rc;
-    if ((rc = gto_mom_launch<0, 0>(a)) != 0) return rc;
-    if ((rc = gto_mom_launch<1, 0>(a)) != 0) return rc;
-    return gto_mom_launch<1, 1>(a);
+    const int ncomp = order == 1 ? 3 : GTO_MOM_NC;
+    return gto_pairs_d_first([&](auto c) { return gto_mom_launch(c, p, ncomp, origin, moments); });
 }
 
 extern "C" int oovqe_gto_moments_expect_batch(const double* moments, int ncomp, int nao, int batch, const double* dens,

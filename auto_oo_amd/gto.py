@@ -169,50 +169,55 @@ class GTOBasis:
                 charges=torch.as_tensor(self.charges).to(device))
         return self._dev[key]
 
-    def work(self, device, G):
-        """Work buffer for G geometries, one per (device, stream): calls on different streams never share one."""
-        key = (str(device), torch.cuda.current_stream().cuda_stream)
+    def _work_for(self, kind, device, export, *args):
+        """The buffer of the ``*_work_size`` export ``export(nshell, max_nprim, *args)``: one per (kind, device, stream),
+        grown when the export asks for more; a refusal of the export raises."""
+        key = kind + (str(device), torch.cuda.current_stream().cuda_stream)
         buf = self._work.get(key)
-        size = int(_lib.load().oovqe_gto_work_size(self.nshell, self.max_nprim, G))
+        size = int(getattr(_lib.load(), export)(self.nshell, self.max_nprim, *args))
         if size < 0:
-            check(size, "oovqe_gto_work_size")
+            check(size, export)
         if buf is None or buf.numel() < size:
             buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
         return buf
+
+    def work(self, device, G):
+        """Work buffer for G geometries, one per (device, stream): calls on different streams never share one."""
+        return self._work_for((), device, "oovqe_gto_work_size", G)
 
     def gradient_work(self, device, G, nset=1):
         """Work buffer of ``oovqe_gto_gradient_batch`` for G geometries (``nset`` > 1: of
         ``oovqe_gto_gradient_sets_batch`` for that many density sets per geometry), one per (device, stream) like
         ``work``."""
-        key = ("gradient", str(device), torch.cuda.current_stream().cuda_stream)
-        buf = self._work.get(key)
-        lib = _lib.load()
         if nset > 1:
-            what = "oovqe_gto_gradient_sets_work_size"
-            size = int(lib.oovqe_gto_gradient_sets_work_size(self.nshell, self.max_nprim, self.natm, G, int(nset)))
-        else:
-            what = "oovqe_gto_gradient_work_size"
-            size = int(lib.oovqe_gto_gradient_work_size(self.nshell, self.max_nprim, self.natm, G))
-        if size < 0:
-            check(size, what)
-        if buf is None or buf.numel() < size:
-            buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
-        return buf
-
+            return self._work_for(("gradient",), device, "oovqe_gto_gradient_sets_work_size", self.natm, G, int(nset))
+        return self._work_for(("gradient",), device, "oovqe_gto_gradient_work_size", self.natm, G)
 
     def connection_work(self, device, G, nset):
         """Work buffer of ``oovqe_gto_overlap_connection_batch`` for G geometries of ``nset`` matrices, one per
         (device, stream) like ``work``."""
-        key = ("connection", str(device), torch.cuda.current_stream().cuda_stream)
-        buf = self._work.get(key)
-        what = "oovqe_gto_overlap_connection_work_size"
-        size = int(_lib.load().oovqe_gto_overlap_connection_work_size(self.nshell, self.max_nprim, self.natm, G,
-                                                                      int(nset)))
-        if size < 0:
-            check(size, what)
-        if buf is None or buf.numel() < size:
-            buf = self._work[key] = torch.empty(size, dtype=F64, device=device)
-        return buf
+        return self._work_for(("connection",), device, "oovqe_gto_overlap_connection_work_size", self.natm, G,
+                              int(nset))
+
+
+def _head(basis, device):
+    """The arguments every geometry-stack entry of the C ABI begins with: the shell table, its primitives, the atoms
+    and their charges (``oovqe_gto_cross_overlap_batch`` takes them without the charges)."""
+    t = basis.device_tables(device)
+    return (basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
+            dptr(t.charges))
+
+
+def _check_stack(basis, x, name="coordinates", stack="G"):
+    """``x`` must be a [G, natm, 3] tensor of geometries."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (basis.natm, 3):
+        raise ValueError(f"{name} of shape {tuple(getattr(x, 'shape', ()))}, expected [{stack}, {basis.natm}, 3]")
+
+
+def _check_shape(name, x, shape, tensor=False):
+    """``x`` must have the shape ``shape`` (``tensor``: and be a tensor)."""
+    if (tensor and not isinstance(x, torch.Tensor)) or tuple(getattr(x, "shape", ())) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(getattr(x, 'shape', ()))}, expected {shape}")
 
 
 def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=None, nuc=None):
@@ -221,16 +226,14 @@ def integrals_into(basis, coords_bohr, overlap=None, int1e_ao=None, int2e_ao=Non
     lib = _lib.load()
     G = int(coords_bohr.shape[0])
     dev = coords_bohr.device
-    t = basis.device_tables(dev)
     N = basis.nao
     for name, x, shape in (("overlap", overlap, (G, N, N)), ("int1e_ao", int1e_ao, (G, N, N)),
                            ("int2e_ao", int2e_ao, (G, N, N, N, N)), ("nuc", nuc, (G,))):
-        if x is not None and tuple(x.shape) != shape:
-            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {shape}")
+        if x is not None:
+            _check_shape(name, x, shape)
     work = basis.work(dev, G)
     check(lib.oovqe_gto_integrals_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(coords_bohr), N, dptr(overlap), dptr(int1e_ao), dptr(int2e_ao), dptr(nuc),
+        *_head(basis, dev), G, dptr(coords_bohr), N, dptr(overlap), dptr(int1e_ao), dptr(int2e_ao), dptr(nuc),
         dptr(work), stream_ptr()), "oovqe_gto_integrals_batch")
 
 
@@ -262,21 +265,15 @@ def moment_integrals_into(basis, coords_bohr, moments, order=1, origin_bohr=None
     tensor in Bohr, or None."""
     lib = _lib.load()
     ncomp = moment_components(order)
-    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
-            basis.natm, 3):
-        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
-                         f"[G, {basis.natm}, 3]")
+    _check_stack(basis, coords_bohr)
     G, N = int(coords_bohr.shape[0]), basis.nao
-    if tuple(moments.shape) != (G, ncomp, N, N):
-        raise ValueError(f"moments has shape {tuple(moments.shape)}, expected {(G, ncomp, N, N)}")
+    _check_shape("moments", moments, (G, ncomp, N, N))
     if origin_bohr is not None and tuple(origin_bohr.shape) != (G, 3):
         raise ValueError(f"origin of shape {tuple(origin_bohr.shape)}, expected [{G}, 3]")
     dev = coords_bohr.device
-    t = basis.device_tables(dev)
     work = basis.work(dev, G)
     check(lib.oovqe_gto_moments_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(coords_bohr), N, int(order), dptr(origin_bohr), dptr(moments), dptr(work),
+        *_head(basis, dev), G, dptr(coords_bohr), N, int(order), dptr(origin_bohr), dptr(moments), dptr(work),
         stream_ptr()), "oovqe_gto_moments_batch")
     return moments
 
@@ -307,23 +304,20 @@ def cross_overlap_into(basis, coords_a_bohr, coords_b_bohr, out=None):
     """``cross_overlap_batch`` for geometries that are already [P, natm, 3] device tensors in Bohr, written into the
     contiguous device tensor ``out`` [P, N, N] (made when None) on the current stream."""
     lib = _lib.load()
-    for name, x in (("coords_a_bohr", coords_a_bohr), ("coords_b_bohr", coords_b_bohr)):
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (basis.natm, 3):
-            raise ValueError(f"{name} of shape {tuple(getattr(x, 'shape', ()))}, expected [P, {basis.natm}, 3]")
+    _check_stack(basis, coords_a_bohr, "coords_a_bohr", "P")
+    _check_stack(basis, coords_b_bohr, "coords_b_bohr", "P")
     P, N = int(coords_a_bohr.shape[0]), basis.nao
     if int(coords_b_bohr.shape[0]) != P:
         raise ValueError(f"{P} bra geometries and {int(coords_b_bohr.shape[0])} ket geometries")
     dev = coords_a_bohr.device
     if out is None:
         out = torch.empty((P, N, N), dtype=F64, device=dev)
-    elif tuple(out.shape) != (P, N, N):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(P, N, N)}")
-    t = basis.device_tables(dev)
+    else:
+        _check_shape("out", out, (P, N, N))
     xa = coords_a_bohr.to(F64).contiguous()
     xb = coords_b_bohr.to(device=dev, dtype=F64).contiguous()
-    check(lib.oovqe_gto_cross_overlap_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm, P,
-        dptr(xa), dptr(xb), N, dptr(out), stream_ptr()), "oovqe_gto_cross_overlap_batch")
+    check(lib.oovqe_gto_cross_overlap_batch(       # (the head without the charges)
+        *_head(basis, dev)[:-1], P, dptr(xa), dptr(xb), N, dptr(out), stream_ptr()), "oovqe_gto_cross_overlap_batch")
     return out
 
 
@@ -355,18 +349,13 @@ def gradient_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True, wor
     ``work``: a buffer of ``oovqe_gto_gradient_work_size`` doubles to use instead of the basis' own."""
     refuse_d_gradient(basis)
     lib = _lib.load()
-    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
-            basis.natm, 3):
-        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
-                         f"[G, {basis.natm}, 3]")
+    _check_stack(basis, coords_bohr)
     G, N = int(coords_bohr.shape[0]), basis.nao
     dev = coords_bohr.device
-    t = basis.device_tables(dev)
     ins = []
     for name, x, shape in (("dm1", dm1, (G, N, N)), ("wq", wq, (G, N, N)), ("dm2", dm2, (G, N, N, N, N))):
         if x is not None:
-            if not isinstance(x, torch.Tensor) or tuple(x.shape) != shape:
-                raise ValueError(f"{name} has shape {tuple(getattr(x, 'shape', ()))}, expected {shape}")
+            _check_shape(name, x, shape, tensor=True)
             x = x.to(device=dev, dtype=F64).contiguous()
         ins.append(x)
     grad = torch.empty((G, basis.natm, 3), dtype=F64, device=dev)
@@ -376,8 +365,7 @@ def gradient_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True, wor
         work = basis.gradient_work(dev, G)
     xyz = coords_bohr.to(F64).contiguous()
     check(lib.oovqe_gto_gradient_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(xyz), N, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), int(bool(nuc)), dptr(grad),
+        *_head(basis, dev), G, dptr(xyz), N, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), int(bool(nuc)), dptr(grad),
         dptr(work), stream_ptr()), "oovqe_gto_gradient_batch")
     return grad
 
@@ -411,10 +399,7 @@ def gradient_sets_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True
     stream.  ``work``: a buffer of ``oovqe_gto_gradient_sets_work_size`` doubles to use instead of the basis' own."""
     refuse_d_gradient(basis)
     lib = _lib.load()
-    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
-            basis.natm, 3):
-        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
-                         f"[G, {basis.natm}, 3]")
+    _check_stack(basis, coords_bohr)
     G, N = int(coords_bohr.shape[0]), basis.nao
     given = [(name, x) for name, x in (("dm1", dm1), ("wq", wq), ("dm2", dm2)) if x is not None]
     if not given:
@@ -426,12 +411,10 @@ def gradient_sets_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True
     if not 1 <= K <= MAX_GRAD_SETS:
         raise ValueError(f"{K} density sets per geometry (1 .. {MAX_GRAD_SETS})")
     dev = coords_bohr.device
-    t = basis.device_tables(dev)
     ins = []
     for name, x, shape in (("dm1", dm1, (G, K, N, N)), ("wq", wq, (G, K, N, N)), ("dm2", dm2, (G, K, N, N, N, N))):
         if x is not None:
-            if tuple(x.shape) != shape:
-                raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {shape}")
+            _check_shape(name, x, shape)
             x = x.to(device=dev, dtype=F64).contiguous()
         ins.append(x)
     if isinstance(nuc, (bool, np.bool_)):
@@ -448,8 +431,7 @@ def gradient_sets_into(basis, coords_bohr, dm1=None, wq=None, dm2=None, nuc=True
         work = basis.gradient_work(dev, G, K)
     xyz = coords_bohr.to(F64).contiguous()
     check(lib.oovqe_gto_gradient_sets_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(xyz), N, K, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), ctypes.c_uint(mask), dptr(grad),
+        *_head(basis, dev), G, dptr(xyz), N, K, dptr(ins[0]), dptr(ins[1]), dptr(ins[2]), ctypes.c_uint(mask), dptr(grad),
         dptr(work), stream_ptr()), "oovqe_gto_gradient_sets_batch")
     return grad
 
@@ -479,20 +461,15 @@ def overlap_connection_into(basis, coords_bohr, D, work=None):
     own."""
     refuse_d_gradient(basis)
     lib = _lib.load()
-    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
-            basis.natm, 3):
-        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
-                         f"[G, {basis.natm}, 3]")
+    _check_stack(basis, coords_bohr)
     G, N = int(coords_bohr.shape[0]), basis.nao
     if not isinstance(D, torch.Tensor) or D.dim() != 4:
         raise ValueError(f"D has shape {tuple(getattr(D, 'shape', ()))}, expected [G, K, N, N]")
     K = int(D.shape[1])
     if not 1 <= K <= MAX_GRAD_SETS:
         raise ValueError(f"{K} matrices per geometry (1 .. {MAX_GRAD_SETS})")
-    if tuple(D.shape) != (G, K, N, N):
-        raise ValueError(f"D has shape {tuple(D.shape)}, expected {(G, K, N, N)}")
+    _check_shape("D", D, (G, K, N, N))
     dev = coords_bohr.device
-    t = basis.device_tables(dev)
     D = D.to(device=dev, dtype=F64).contiguous()
     out = torch.empty((G, K, basis.natm, 3), dtype=F64, device=dev)
     if G == 0:
@@ -501,8 +478,7 @@ def overlap_connection_into(basis, coords_bohr, D, work=None):
         work = basis.connection_work(dev, G, K)
     xyz = coords_bohr.to(F64).contiguous()
     check(lib.oovqe_gto_overlap_connection_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(xyz), N, K, dptr(D), dptr(out), dptr(work), stream_ptr()),
+        *_head(basis, dev), G, dptr(xyz), N, K, dptr(D), dptr(out), dptr(work), stream_ptr()),
         "oovqe_gto_overlap_connection_batch")
     return out
 
@@ -561,10 +537,7 @@ def point_charges_host(G, charges, charge_coords):
 
 def _check_point_charges(basis, coords_bohr, q, qxyz_bohr):
     """The device-tensor arguments of the ``point_charge_*_into`` functions -> (G, M, coords, q, qxyz) contiguous."""
-    if not isinstance(coords_bohr, torch.Tensor) or coords_bohr.dim() != 3 or tuple(coords_bohr.shape[1:]) != (
-            basis.natm, 3):
-        raise ValueError(f"coordinates of shape {tuple(getattr(coords_bohr, 'shape', ()))}, expected "
-                         f"[G, {basis.natm}, 3]")
+    _check_stack(basis, coords_bohr)
     G = int(coords_bohr.shape[0])
     if G > 65535:
         raise ValueError(f"{G} geometries in one call (at most 65535)")
@@ -594,16 +567,14 @@ def point_charge_integrals_into(basis, coords_bohr, q, qxyz_bohr, out=None):
     dev = xyz.device
     if out is None:
         out = torch.empty((G, N, N), dtype=F64, device=dev)
-    elif tuple(out.shape) != (G, N, N):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(G, N, N)}")
+    else:
+        _check_shape("out", out, (G, N, N))
     if G == 0:
         return out
     lib = _lib.load()
-    t = basis.device_tables(dev)
     work = basis.work(dev, G)
     check(lib.oovqe_gto_point_charge_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(out), dptr(work), stream_ptr()),
+        *_head(basis, dev), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(out), dptr(work), stream_ptr()),
         "oovqe_gto_point_charge_batch")
     return out
 
@@ -640,15 +611,7 @@ def refuse_d_point_charge_gradient(basis):
 
 def point_charge_gradient_work(basis, device, G, M):
     """Work buffer of ``oovqe_gto_point_charge_gradient_batch``, one per (device, stream) like ``GTOBasis.work``."""
-    key = ("point_charges", str(device), torch.cuda.current_stream().cuda_stream)
-    buf = basis._work.get(key)
-    what = "oovqe_gto_point_charge_gradient_work_size"
-    size = int(_lib.load().oovqe_gto_point_charge_gradient_work_size(basis.nshell, basis.max_nprim, basis.natm, G, M))
-    if size < 0:
-        check(size, what)
-    if buf is None or buf.numel() < size:
-        buf = basis._work[key] = torch.empty(size, dtype=F64, device=device)
-    return buf
+    return basis._work_for(("point_charges",), device, "oovqe_gto_point_charge_gradient_work_size", basis.natm, G, M)
 
 
 def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
@@ -657,8 +620,7 @@ def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
     refuse_d_point_charge_gradient(basis)
     G, M, xyz, q, r = _check_point_charges(basis, coords_bohr, q, qxyz_bohr)
     N = basis.nao
-    if not isinstance(dm1, torch.Tensor) or tuple(dm1.shape) != (G, N, N):
-        raise ValueError(f"dm1 has shape {tuple(getattr(dm1, 'shape', ()))}, expected {(G, N, N)}")
+    _check_shape("dm1", dm1, (G, N, N), tensor=True)
     dev = xyz.device
     # (the size of the work buffer is asked for first: a molecule the entry refuses raises here, before any allocation)
     work = point_charge_gradient_work(basis, dev, G, M)
@@ -667,11 +629,9 @@ def point_charge_gradient_into(basis, coords_bohr, q, qxyz_bohr, dm1, nuc=True):
     if G == 0:
         return gA, gQ
     lib = _lib.load()
-    t = basis.device_tables(dev)
     d1 = dm1.to(device=dev, dtype=F64).contiguous()
     check(lib.oovqe_gto_point_charge_gradient_batch(
-        basis.nshell, dptr(t.shells, torch.int32), int(basis.exps.size), dptr(t.exps), dptr(t.coefs), basis.natm,
-        dptr(t.charges), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(d1), int(bool(nuc)), dptr(gA), dptr(gQ),
+        *_head(basis, dev), G, dptr(xyz), N, M, dptr(q), dptr(r), dptr(d1), int(bool(nuc)), dptr(gA), dptr(gQ),
         dptr(work), stream_ptr()), "oovqe_gto_point_charge_gradient_batch")
     return gA, gQ
 
@@ -696,9 +656,7 @@ def point_charge_gradient_batch(basis, coords, charges, charge_coords, dm1, nuc=
     xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
     G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
     q, r = point_charges_host(G, charges, charge_coords)
-    N = basis.nao
-    if not isinstance(dm1, torch.Tensor) or tuple(dm1.shape) != (G, N, N):
-        raise ValueError(f"dm1 has shape {tuple(getattr(dm1, 'shape', ()))}, expected {(G, N, N)}")
+    _check_shape("dm1", dm1, (G, basis.nao, basis.nao), tensor=True)
     device = _lib.require_device()
     return point_charge_gradient_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(q).to(device),
                                       torch.as_tensor(r / BOHR).to(device), dm1, nuc)
@@ -735,8 +693,7 @@ def coords_to_device(basis, coords, device=None):
         xyz = coords.to(F64)
         if xyz.dim() == 2:
             xyz = xyz[None]
-        if tuple(xyz.shape[1:]) != (basis.natm, 3):
-            raise ValueError(f"coordinates of shape {tuple(xyz.shape)}, expected [G, {basis.natm}, 3]")
+        _check_stack(basis, xyz)
         return (xyz / BOHR).contiguous()
     return torch.as_tensor(basis.coordinates(coords) / BOHR).to(device)
 

@@ -10,7 +10,8 @@ and logs instead of launching; pointers passed here are never dereferenced on th
 
 Run on the build of two commits, the two out.json files compare launch for launch.  golden.json (optional) gets the
 rows of tests/golden/eval_plan_parent.json: the 18 table shapes and every 61st call of the sweep with at most 40
-launches -- that fixture was written this way from the commit before csrc/plan.h existed."""
+launches -- that fixture was written this way from the commit before csrc/plan.h existed.  record_gto.py, beside this
+file, records the geometry-stack integral entries (csrc/gto*.hip) with the same library."""
 import ctypes, json, os, re, sys
 from ctypes import c_void_p, c_int, c_uint, c_uint32, c_char_p
 
