@@ -2217,6 +2217,12 @@ extern "C" int oovqe_sector_geometry_coefficients_ok(int ncas, int na, int nb)
 {
     const int na2 = ncas * ncas;
     const int LAp = (na + 8) & ~7;
+    // (the matrices of a set and the tables live in the W region of the workspace: with one state per set -- the
+    // tightest case -- they must fit the region of that state; sectors of one alpha or one beta string do not)
+    const size_t Dc = (size_t)na * nb;
+    const size_t per_set = (size_t)na * na + (size_t)nb * nb + (size_t)na2 * na2;
+    const size_t shared = Dc + ((size_t)(na + nb) * na2 + 3) / 4 + ((size_t)nb * na2 + 1) / 2 + 2;
+    if (per_set + shared > (2 * (size_t)na2 + 1) * Dc) return 0;
     return (na2 == 16 || na2 == 64) && na < SEC_TAB_MAXSTR && nb < SEC_TAB_MAXSTR && LAp <= SEC_LCH &&
            sec_fused_lds_bytes(na, nb, ncas) <= 140 * 1024 && sec_lambda_lds_bytes(na, nb, ncas) <= 160 * 1024 &&
            oovqe_opt(OOVQE_OPT_SECTOR_UNFUSED) == 0 && na * nb <= 32767;
@@ -2381,9 +2387,12 @@ static int sector_adjoint_impl(const double* theta, int n_theta, const oovqe_gat
     if (fused && (size_t)(na + nb) * na2 * sizeof(uint16_t) <= ((size_t)na2 * na2 + na2) * sizeof(double))
         hipLaunchKernelGGL(sector_lambda_tab_kernel, dim3((Dc + 63) / 64, batch), dim3(256), 0, st, W12, tabs,
                            tabs + (size_t)na * na2, na, nb, ncas, lam);
-    else
-        hipLaunchKernelGGL(sector_lambda_kernel, dim3((Dc + 63) / 64, batch), dim3(256),
-                           256 * sizeof(double) + 2 * ((size_t)1 << ncas) * sizeof(int32_t), st, W12, s, lam);
+    else {
+        // (the two rank tables: 66 KB at 13 orbitals, past the 64 KB a kernel gets without asking)
+        const size_t rank_lds = 256 * sizeof(double) + 2 * ((size_t)1 << ncas) * sizeof(int32_t);
+        if ((rc = oovqe_ensure_dynamic_lds((const void*)sector_lambda_kernel, rank_lds))) return rc;
+        hipLaunchKernelGGL(sector_lambda_kernel, dim3((Dc + 63) / 64, batch), dim3(256), rank_lds, st, W12, s, lam);
+    }
     OOVQE_CHECK_LAUNCH("sector_adjoint/lambda");
     }
     if (lam_out) return 0;

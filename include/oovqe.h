@@ -452,8 +452,9 @@ int oovqe_sector_lambda(const double* vecs, int ncas, const uint32_t* unrank_a, 
  * geometry batch: ansatze/kUpCCD.py:36-154 under oo_pqc.py:64-148, one launch sequence for all geometries): state b
  * takes c1 + (b / group) * c_stride and c2 + (b / group) * c_stride (doubles; e.g. columns of the packed outputs of
  * oovqe_cas_eval_batch).  oovqe_sector_adjoint_pg: group = 1.  oovqe_sector_lambda_pg with group = 1 + n_theta: the
- * operator on psi and its first tangents of every geometry (theta-theta blocks).  Served for ncas = 4 and 8
- * (oovqe_sector_geometry_coefficients_ok); callers loop over the geometries otherwise. */
+ * operator on psi and its first tangents of every geometry (theta-theta blocks).  Served for ncas = 4 and 8, sectors
+ * of more than one alpha and more than one beta string (oovqe_sector_geometry_coefficients_ok: the coefficient
+ * matrices of a geometry must fit the workspace of one state); callers loop over the geometries otherwise. */
 int oovqe_sector_geometry_coefficients_ok(int ncas, int na, int nb);
 int oovqe_sector_adjoint_pg(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates, int ncas,
                             const uint32_t* unrank_a, const uint32_t* unrank_b, const int32_t* rank_a,
