@@ -38,6 +38,7 @@ from . import overlaps                                      # noqa: E402
 from .overlaps import sector_overlaps, state_overlaps_oao, track_roots, apply_tracking   # noqa: E402
 from .gto import cross_overlap_batch, overlap_connection_batch   # noqa: E402
 from .gto import point_charge_integrals_batch, point_charge_gradient_batch   # noqa: E402
+from .gto import potential_batch, potential_into   # noqa: E402
 
 __all__ = [
     "Parameterized_circuit", "Moldata", "Moldata_sto3g", "GTOBasis", "integrals_batch", "gto", "scf", "nucgrad", "RHFResult", "rhf_batch", "ao_to_oao", "get_formal_geo", "OO_pqc", "OO_pqc_batch", "OO_energy", "mo_ao_to_mo_oao",
@@ -47,4 +48,5 @@ __all__ = [
     "properties", "moment_integrals_batch", "multipole_moments", "traceless_quadrupole", "DEBYE",
     "overlaps", "sector_overlaps", "state_overlaps_oao", "track_roots", "apply_tracking", "cross_overlap_batch",
     "transition_rdm1", "overlap_connection_batch", "point_charge_integrals_batch", "point_charge_gradient_batch",
+    "potential_batch", "potential_into",
 ]

@@ -241,6 +241,11 @@ SIGNATURES = {
                                                              c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                                              c_double_p, ctypes.c_int, ctypes.c_int]
                                               + [c_double_p] * 3 + [ctypes.c_int] + [c_double_p] * 3 + [c_stream]),
+    "oovqe_gto_potential_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
+    "oovqe_gto_potential_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                                 ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                 ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_uint]
+                                  + [c_double_p] * 3 + [c_stream]),
     "oovqe_gto_overlap_connection_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
     "oovqe_gto_overlap_connection_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p,
                                                           c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,

@@ -819,6 +819,112 @@ class OO_pqc_batch:
             dip[:, jj, ii] = val[:, R:]
         return e, dip
 
+    # ---- electrostatic potential and field at arbitrary points (csrc/gto_potential.hip) ---------------------------------
+    def _potential_of(self, rows, dens, points, field, nuclear=True):
+        """``gto.potential_into`` of the densities ``dens`` [len(rows), nd, N, N] at the geometries ``rows``; ``points``
+        [M, 3] or [len(rows), M, 3] in Angstrom.  More than ``gto.MAX_GRAD_SETS`` densities go in several calls (a set has
+        the same bits whatever the other sets of its call)."""
+        sel = torch.as_tensor(rows, device=self.device)
+        r = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points
+        r = np.asarray(r, dtype=np.float64)
+        if r.ndim == 2:
+            r = np.broadcast_to(r, (len(rows),) + r.shape)
+        if r.ndim != 3 or r.shape[0] != len(rows) or r.shape[2] != 3:
+            raise ValueError(f"points of shape {np.shape(points)}, expected [M, 3] or [{len(rows)}, M, 3]")
+        if not 1 <= r.shape[1] <= GTO.MAX_POINTS:
+            raise ValueError(f"{r.shape[1]} points per geometry (1 .. {GTO.MAX_POINTS})")
+        if not np.isfinite(r).all():
+            raise ValueError("the points must be finite")
+        pts = torch.as_tensor(np.array(r / GTO.BOHR)).to(self.device)
+        nd = int(dens.shape[1])
+        flags = [bool(nuclear)] * nd if isinstance(nuclear, (bool, np.bool_)) else [bool(f) for f in nuclear]
+        xyz = self.coords_bohr[sel]
+        phis, fields = [], []
+        for a in range(0, nd, GTO.MAX_GRAD_SETS):
+            b = min(nd, a + GTO.MAX_GRAD_SETS)
+            out = GTO.potential_into(self.basis, xyz, pts, dens[:, a:b], flags[a:b], field)
+            phis.append(out[0] if field else out)
+            if field:
+                fields.append(out[1])
+        phi = phis[0] if len(phis) == 1 else torch.cat(phis, dim=1)
+        if not field:
+            return phi
+        return phi, (fields[0] if len(fields) == 1 else torch.cat(fields, dim=1))
+
+    def electrostatic_potential(self, thetas, points, index=None, field=False):
+        """The electrostatic potential every geometry's state at ``thetas`` [G, n_theta] and the batch's current orbitals
+        makes at ``points``, in atomic units: ``phi[g, m] = sum_A Z_A / |R_A - r_m| - tr(D1 <1 / |r - r_m|>)``
+        (``gto.potential_batch`` of the density of ``_state_density``).
+
+        Args:
+            points: [M, 3] shared by all rows, or one [M, 3] per row asked for, in Angstrom like the geometries
+            index: rows of the batch (default all); the result then has one entry per row asked for
+            field: also return ``F = -d phi / d r`` [G, M, 3] in Hartree / (e Bohr)
+
+        Returns ``phi`` [G, M] in Hartree / e on the device, or ``(phi, F)``.  For an embedded batch
+        (``from_geometries(point_charges=...)``) this is the potential of the POLARISED MOLECULE ALONE: the external
+        charges' own potential is not included.  Needs a batch made by ``from_geometries`` (RuntimeError otherwise);
+        ncas <= 8.  Same bits whatever ``index``."""
+        rows = self._moment_rows(index, "electrostatic_potential")
+        out = self._potential_of(rows, self._state_density(thetas, rows)[:, None], points, field)
+        return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]
+
+    def rhf_electrostatic_potential(self, points, result=None, index=None, field=False):
+        """Closed-shell Hartree-Fock electrostatic potential [G, M] (and field [G, M, 3]; device, atomic units) at
+        ``points`` from a ``scf.RHFResult`` of the rows ``index`` (default all; ``self.rhf(index=index)`` is run when none
+        is given): ``D = 2 C_o C_o^T``.  ``points``, ``field`` and the embedded case as for
+        ``electrostatic_potential``: with the orbitals of an embedded batch, ``phi`` at the position of charge k is
+        ``dE_RHF / dq_k``."""
+        rows = self._moment_rows(index, "rhf_electrostatic_potential")
+        if result is None:
+            result = self.rhf(index=index)
+            scf.raise_unless_converged(result.info, rows)
+        if int(result.mo_coeff.shape[0]) != len(rows):
+            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
+                             "for")
+        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+        out = self._potential_of(rows, d1[:, None], points, field)
+        return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]
+
+    def casci_electrostatic_potential(self, points, nroots=2, fix_singlet=True, field=False, tol=1e-9, max_iter=200):
+        """CASCI states of every geometry at its current orbitals (``casci``) and the matrix of their electrostatic
+        potentials at ``points`` -> (energies [G, nroots], phi [G, nroots, nroots, M]) on the device, atomic units; with
+        ``field`` also F [G, nroots, nroots, M, 3].
+
+        ``phi[g, I, I]`` is the potential of root I, nuclear part included.  ``phi[g, I, J]``, I != J, is the transition
+        potential ``-tr(D^IJ <1 / |r - r_m|>)`` with the ``D^IJ`` of ``casci_dipole_matrix`` (the same ``gamma^IJ``
+        construction): no nuclear term, exactly symmetric in (I, J), and with the sign convention described there
+        (``overlaps.apply_tracking`` works on it).  ``points`` and the embedded case as for
+        ``electrostatic_potential``."""
+        rows = self._moment_rows(None, "casci_electrostatic_potential")
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"casci_electrostatic_potential covers ncas <= {nucgrad.MAX_NCAS}")
+        from . import ci
+        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        G, R, a = self.G, int(nroots), self.ncas
+        pairs = [(i, j) for i in range(R) for j in range(i)]
+        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
+        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
+        r2 = 0.5 ** 0.5
+        stack = torch.cat((vecs, r2 * (vecs[:, ii] + vecs[:, jj]), r2 * (vecs[:, ii] - vecs[:, jj])), dim=1)
+        n, P = R + 2 * len(pairs), len(pairs)
+        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
+        C = self.mo_coeff[:, None].expand(G, n, self.nao, self.nao).reshape(G * n, self.nao, self.nao)
+        d1 = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma, Gamma, want_d2=False)[0]
+        d1 = d1.reshape(G, n, self.nao, self.nao)
+        dens = torch.cat((d1[:, :R], 0.5 * (d1[:, R:R + P] - d1[:, R + P:])), dim=1)
+        out = self._potential_of(rows, dens, points, field, nuclear=[True] * R + [False] * P)
+        k = torch.arange(R, device=self.device)
+        mats = []
+        for val in (out if field else (out,)):
+            mat = torch.empty((G, R, R) + tuple(val.shape[2:]), dtype=F64, device=self.device)
+            mat[:, k, k] = val[:, :R]
+            if P:
+                mat[:, ii, jj] = val[:, R:]
+                mat[:, jj, ii] = val[:, R:]
+            mats.append(mat)
+        return (e, *mats)
+
     # ---- overlaps between the states of different geometries (auto_oo_amd/overlaps.py, csrc/overlap.hip) --------------
     def _pair_rows(self, pairs, closed):
         """``pairs`` -> ([P] rows a, [P] rows b) on the host; the default is the loop (g, g + 1 mod G) when ``closed``,

@@ -289,6 +289,39 @@ def point_charge_energy(charges, coords_bohr, q, qxyz_bohr):
     return float(np.sum(Z[:, None] * q[None, :] / d))
 
 
+def potential_from_table(table, charges, coords_bohr, points_bohr, dm, d_functions, nuc=True, boys=None):
+    """``phi[..., m] = (nuc) sum_A Z_A / |R_A - r_m| - sum_{mu nu} dm[..., mu, nu] <mu| 1 / |r - r_m| |nu>`` at the points
+    ``points_bohr`` [M, 3], on the host: the twin of ``gto.potential_batch`` for one geometry.  ``dm`` is [N, N] or
+    [K, N, N] over the functions of ``integrals_from_table`` and is not taken as symmetric; the operators are those of
+    ``point_charge_integrals_from_table(..., per_charge=True)`` for unit charges on the points.  ``nuc``: a bool, or one
+    bool per set; a point ON a nucleus then gives inf.  ``boys``: a replacement of ``_boys`` for the duration of the
+    call (the accuracy bounds perturb it).  Returns [M] or [K, M] in Hartree / e; the field has no twin of its own (it is
+    minus the derivative of this in the point)."""
+    global _boys
+    R = np.asarray(coords_bohr, dtype=float).reshape(-1, 3)
+    Z = np.asarray(charges, dtype=float).reshape(-1)
+    C = np.asarray(points_bohr, dtype=float).reshape(-1, 3)
+    D = np.asarray(dm, dtype=float)
+    if R.shape[0] != Z.size:
+        raise ValueError(f"{Z.size} nuclear charges for {R.shape[0]} atoms")
+    keep = _boys
+    if boys is not None:
+        _boys = boys
+    try:
+        V = point_charge_integrals_from_table(table, R, np.ones(C.shape[0]), C, d_functions, per_charge=True)
+    finally:
+        _boys = keep
+    if D.ndim not in (2, 3) or D.shape[-2:] != V.shape[1:]:
+        raise ValueError(f"dm of shape {D.shape}, expected [{V.shape[1]}, {V.shape[2]}] or [K, {V.shape[1]}, {V.shape[2]}]")
+    phi = np.einsum("...pq,mpq->...m", D, V)
+    flags = np.broadcast_to(np.asarray(nuc, dtype=bool), phi.shape[:-1])
+    if flags.any():
+        with np.errstate(divide="ignore"):
+            pn = np.sum(Z[:, None] / np.linalg.norm(R[:, None, :] - C[None, :, :], axis=2), axis=0)
+        phi = phi + np.where(flags[..., None], pn, 0.0) if phi.ndim > 1 else phi + pn
+    return phi
+
+
 # powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
 MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
 

@@ -662,6 +662,119 @@ def point_charge_gradient_batch(basis, coords, charges, charge_coords, dm1, nuc=
                                       torch.as_tensor(r / BOHR).to(device), dm1, nuc)
 
 
+# ---- electrostatic potential and field at arbitrary points (csrc/gto_potential.hip) -------------------------------------
+MAX_POINTS = 65535             # per geometry
+
+
+def potential_work(basis, device, G, nset=1):
+    """Work buffer of ``oovqe_gto_potential_batch``, one per (device, stream) like ``GTOBasis.work``."""
+    return basis._work_for(("potential",), device, "oovqe_gto_potential_work_size", basis.natm, G, int(nset))
+
+
+def _nuc_mask(nuc, K):
+    """``nuc`` (a bool, or one bool per set) -> the bit mask of the sets that carry the nuclear term."""
+    if isinstance(nuc, (bool, np.bool_)):
+        bits = [bool(nuc)] * K
+    else:
+        bits = [bool(b) for b in nuc]
+        if len(bits) != K:
+            raise ValueError(f"nuc holds {len(bits)} flags for {K} sets")
+    return sum(1 << k for k, b in enumerate(bits) if b)
+
+
+def potential_into(basis, coords_bohr, points_bohr, dm, nuc=True, field=False, work=None):
+    """``potential_batch`` for device tensors in atomic units (geometries [G, natm, 3] and points [G, M, 3] in Bohr, ``dm``
+    [G, K, N, N]), on the current stream -> ``phi`` [G, K, M], or ``(phi, F [G, K, M, 3])`` with ``field``.  ``work``: a
+    buffer of ``oovqe_gto_potential_work_size`` doubles to use instead of the basis' own."""
+    _check_stack(basis, coords_bohr)
+    G, N = int(coords_bohr.shape[0]), basis.nao
+    if G > 65535:
+        raise ValueError(f"{G} geometries in one call (at most 65535)")
+    if not isinstance(points_bohr, torch.Tensor) or points_bohr.dim() != 3 or tuple(points_bohr.shape[::2]) != (G, 3):
+        raise ValueError(f"points of shape {tuple(getattr(points_bohr, 'shape', ()))}, expected [{G}, M, 3]")
+    M = int(points_bohr.shape[1])
+    if not 1 <= M <= MAX_POINTS:
+        raise ValueError(f"{M} points per geometry (1 .. {MAX_POINTS})")
+    if not isinstance(dm, torch.Tensor) or dm.dim() != 4:
+        raise ValueError(f"dm has shape {tuple(getattr(dm, 'shape', ()))}, expected [G, K, N, N]")
+    K = int(dm.shape[1])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} density sets per geometry (1 .. {MAX_GRAD_SETS})")
+    _check_shape("dm", dm, (G, K, N, N))
+    mask = _nuc_mask(nuc, K)
+    dev = coords_bohr.device
+    xyz = coords_bohr.to(F64).contiguous()
+    pts = points_bohr.to(device=dev, dtype=F64).contiguous()
+    dm = dm.to(device=dev, dtype=F64).contiguous()
+    if not (bool(torch.isfinite(xyz).all()) and bool(torch.isfinite(pts).all()) and bool(torch.isfinite(dm).all())):
+        raise ValueError("coordinates, points and densities must be finite")
+    phi = torch.empty((G, K, M), dtype=F64, device=dev)
+    F = torch.empty((G, K, M, 3), dtype=F64, device=dev) if field else None
+    if G > 0:
+        if work is None:
+            work = potential_work(basis, dev, G, K)
+        check(_lib.load().oovqe_gto_potential_batch(
+            *_head(basis, dev), G, dptr(xyz), N, K, dptr(dm), M, dptr(pts), ctypes.c_uint(mask), dptr(phi), dptr(F),
+            dptr(work), stream_ptr()), "oovqe_gto_potential_batch")
+    return (phi, F) if field else phi
+
+
+def potential_batch(basis, coords, points, dm, nuc=True, field=False):
+    """The electrostatic potential (and field) the molecule makes at M points, for G geometries and K densities per
+    geometry on the device (``oovqe_gto_potential_batch``, csrc/gto_potential.hip; no operator is stored):
+
+        phi[g, k, m]  = (nuc_k) sum_A Z_A / |R_A - r_m|  -  sum_{mu nu} dm[g, k, mu, nu] <mu| 1 / |r - r_m| |nu>
+        F[g, k, m, :] = - d phi[g, k, m] / d r_m
+
+    over the functions of ``integrals_batch`` (s, p and d shells, both d forms).
+
+    Args:
+        basis: GTOBasis
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        points: [M, 3] shared by all geometries, or [G, M, 3], in Angstrom, 1 <= M <= ``MAX_POINTS``; a point may lie
+            anywhere (on a nucleus, with ``nuc``, its own entries are inf / NaN and no other entry changes)
+        dm: [G, N, N] or [G, K, N, N] device tensor, K = 1 .. ``MAX_GRAD_SETS``; NOT taken as symmetric: both (mu, nu)
+            and (nu, mu) are read and only the symmetric part matters, so transition densities go in as they are
+        nuc: add the potential of the nuclei: a bool, or one bool per set
+        field: also return F
+
+    Returns ``phi`` [G, K, M] in Hartree / e, or ``(phi, F)`` with F [G, K, M, 3] in Hartree / (e Bohr), on the device;
+    the K axis is dropped for a 3-d ``dm``.  A (geometry, set, point) has the same bits wherever it stands in the stack,
+    whatever the other points and sets, and with or without the field
+    (``gaussian.potential_from_table`` is the host twin)."""
+    xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
+    G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
+    N = basis.nao
+    r = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points
+    r = np.asarray(r, dtype=np.float64)
+    if r.ndim == 2:
+        r = np.broadcast_to(r, (G,) + r.shape)
+    if r.ndim != 3 or r.shape[0] != G or r.shape[2] != 3:
+        raise ValueError(f"points of shape {np.shape(points)}, expected [M, 3] or [{G}, M, 3]")
+    M = int(r.shape[1])
+    if not 1 <= M <= MAX_POINTS:
+        raise ValueError(f"{M} points per geometry (1 .. {MAX_POINTS})")
+    if not np.isfinite(r).all():
+        raise ValueError("the points must be finite")
+    if not isinstance(dm, torch.Tensor) or dm.dim() not in (3, 4):
+        raise ValueError(f"dm has shape {tuple(getattr(dm, 'shape', ()))}, expected [{G}, {N}, {N}] or [{G}, K, {N}, {N}]")
+    squeeze = dm.dim() == 3
+    d4 = dm[:, None] if squeeze else dm
+    K = int(d4.shape[1])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} density sets per geometry (1 .. {MAX_GRAD_SETS})")
+    _check_shape("dm", d4, (G, K, N, N))
+    _nuc_mask(nuc, K)
+    if not bool(torch.isfinite(d4).all()):
+        raise ValueError("the densities must be finite")
+    device = _lib.require_device()
+    out = potential_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(np.array(r / BOHR)).to(device), d4,
+                         nuc, field)
+    if not squeeze:
+        return out
+    return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]
+
+
 def sym_invsqrt_batch(S, out=None):
     """``S^-1/2`` (symmetric principal root) of a stack [G, n, n] of symmetric positive definite device matrices ->
     (X [G, n, n], info [G] int32 on the device: 0, or -1 where S has an eigenvalue below ``INVSQRT_MIN_EIG`` -- that

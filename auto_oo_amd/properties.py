@@ -100,3 +100,44 @@ def traceless_quadrupole(second):
         eye = np.eye(3)
         trace = np.trace(second, axis1=-2, axis2=-1)
     return 1.5 * second - 0.5 * trace[..., None, None] * eye
+
+
+def fit_esp_charges(phi, points_bohr, coords_bohr, total_charge=0.0):
+    """Atomic charges fitted to an electrostatic potential: the ``q`` [..., natm] that minimise
+    ``sum_m (phi[..., m] - sum_A q_A / |r_m - R_A|)^2`` under ``sum_A q_A = total_charge`` (a Lagrange constraint), batched
+    over the leading axes of ``phi``.
+
+    Args:
+        phi: [..., M] potential at the points in Hartree / e (``gto.potential_batch``, the batch methods), tensor or array
+        points_bohr: [M, 3] or [..., M, 3] in Bohr, M >= natm, none of them on an atom
+        coords_bohr: [natm, 3] or [..., natm, 3] in Bohr
+        total_charge: a number, or one per leading index of ``phi``
+
+    No points are selected and no restraints applied: which points enter (a shell of van der Waals surfaces, a grid) is
+    the caller's business.  The constraint is eliminated (``q = total_charge / natm + Z y`` with the columns of Z orthogonal
+    to (1, .., 1)) and the rest solved by a QR factorisation, so the conditioning is that of the design matrix, not of
+    its square; the result is the solution of the normal equations with the multiplier.  Runs on the device of ``phi``."""
+    phi = torch.as_tensor(phi).to(F64)
+    dev = phi.device
+    r = torch.as_tensor(points_bohr).to(device=dev, dtype=F64)
+    R = torch.as_tensor(coords_bohr).to(device=dev, dtype=F64)
+    if r.dim() < 2 or R.dim() < 2 or r.shape[-1] != 3 or R.shape[-1] != 3 or phi.dim() < 1:
+        raise ValueError(f"phi {tuple(phi.shape)}, points {tuple(r.shape)}, atoms {tuple(R.shape)}: expected [..., M], "
+                         "[..., M, 3], [..., natm, 3]")
+    M, n = int(r.shape[-2]), int(R.shape[-2])
+    if int(phi.shape[-1]) != M or M < n or n < 1:
+        raise ValueError(f"{int(phi.shape[-1])} values of phi at {M} points for {n} atoms (M >= natm points, one value each)")
+    lead = tuple(phi.shape[:-1])
+    A = 1.0 / (r[..., :, None, :] - R[..., None, :, :]).norm(dim=-1)
+    if not (bool(torch.isfinite(A).all()) and bool(torch.isfinite(phi).all())):
+        raise ValueError("phi must be finite and no point may lie on an atom")
+    A = A.expand(lead + (M, n))
+    Q = torch.as_tensor(total_charge, dtype=F64, device=dev).expand(lead)
+    q0 = (Q / n)[..., None].expand(lead + (n,))
+    if n == 1:
+        return q0.clone()
+    Z = torch.linalg.qr(torch.ones((n, 1), dtype=F64, device=dev), mode="complete").Q[:, 1:]
+    rhs = phi - (A @ q0[..., None])[..., 0]
+    Qm, Rm = torch.linalg.qr(A @ Z)
+    y = torch.linalg.solve_triangular(Rm, Qm.transpose(-1, -2) @ rhs[..., None], upper=True)[..., 0]
+    return q0 + y @ Z.T

@@ -793,6 +793,24 @@ int oovqe_gto_point_charge_gradient_batch(int nshell, const int32_t* shells, int
                                           const double* coords, int nao, int ncharge, const double* q,
                                           const double* qxyz, const double* d1, int with_nuc, double* grad_atoms,
                                           double* grad_charges, double* work, oovqe_stream_t stream);
+/* Electrostatic potential and field of the molecule at arbitrary points (csrc/gto_potential.hip): every geometry has its
+ * own npoint points [batch][npoint][3] (Bohr), 1 <= npoint <= 65535, and nset density matrices dm
+ * [batch][nset][nao][nao], 1 <= nset <= OOVQE_GTO_GRAD_MAX_SETS, batch <= 65535; the other arguments are those of
+ * oovqe_gto_point_charge_batch (s, p, d shells, both d forms).  dm is NOT taken as symmetric: both (mu, nu) and (nu, mu)
+ * are read, the result is tr(dm V).
+ *   phi[g][k][m]      = (bit k of nuc_mask) sum_A Z_A / |R_A - r_m| - sum dm[g][k][mu][nu] <mu| 1 / |r - r_m| |nu>
+ *   field[g][k][m][:] = - d phi[g][k][m] / d r_m                               (null: not computed)
+ * A point ON a nucleus gives inf / NaN in its own entries of the sets with the nuclear term and nowhere else; the
+ * electronic part is finite everywhere.  points and coords are taken as finite.  No floating-point atomics, fixed orders
+ * of summation: a (geometry, set, point) has the same bits wherever it stands in the stack, whatever the other points and
+ * sets, their number and order, on any stream, with or without the field.  work:
+ * oovqe_gto_potential_work_size(nshell, largest number of primitives of a shell, natm, batch, nset) doubles (the pair
+ * data; answers without a device, a negative code beyond the limits). */
+int64_t oovqe_gto_potential_work_size(int nshell, int max_nprim, int natm, int batch, int nset);
+int oovqe_gto_potential_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                              const double* coefs, int natm, const double* charges, int batch, const double* coords,
+                              int nao, int nset, const double* dm, int npoint, const double* points, unsigned nuc_mask,
+                              double* phi, double* field, double* work, oovqe_stream_t stream);
 /* AO densities of a CAS wave function for the calls above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
  * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
  * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
