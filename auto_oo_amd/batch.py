@@ -51,6 +51,60 @@ def _host_point_charges(basis, coords, point_charges):
     return GTO.point_charges_host(G, point_charges[0], point_charges[1])
 
 
+# ---- shared steps of the stack properties; plain functions of values -----------------------------
+def stack_rows(G, index):
+    """``index`` of a property method (None: all; one row; a sequence of rows) -> the list of rows of a stack of ``G``
+    geometries, ValueError for a row outside it."""
+    if index is None:
+        return list(range(G))
+    rows = [int(i) for i in np.atleast_1d(index)]
+    if any(not 0 <= r < G for r in rows):
+        raise ValueError(f"index must hold rows in 0..{G - 1}")
+    return rows
+
+
+def rows_selector(rows, device=None):
+    """What takes the ``rows`` out of a stacked tensor: consecutive rows -> a slice (a view: no copy of the integrals),
+    anything else -> an index tensor on ``device``."""
+    if rows == list(range(rows[0], rows[0] + len(rows))):
+        return slice(rows[0], rows[0] + len(rows))
+    return torch.as_tensor(rows, device=device)
+
+
+def pair_matrix(values, R, sign=1):
+    """The values of the sets of ``R`` states -> the matrix [c, R, R, ...] over the states.  ``sign = 1``: ``values``
+    [c, R + P, ...], the R state values (the diagonal) and then those of the P pairs (I, J), I > J, in the order of
+    ``nucgrad.state_pairs``, each stored to (I, J) and (J, I): symmetric exactly.  ``sign = -1``: ``values`` [c, P, ...],
+    the pairs alone, stored to (I, J) and negated to (J, I): antisymmetric exactly, the diagonal exactly zero."""
+    R, states = int(R), (int(R) if sign > 0 else 0)
+    pairs = nucgrad.state_pairs(R)
+    P = int(values.shape[1]) - states
+    if sign not in (1, -1) or P != len(pairs):
+        raise ValueError(f"values of shape {tuple(values.shape)} for {R} states and sign {sign}")
+    mat = torch.empty((int(values.shape[0]), R, R) + tuple(values.shape[2:]), dtype=values.dtype, device=values.device)
+    k = torch.arange(R, device=values.device)
+    mat[:, k, k] = values[:, :R] if sign > 0 else 0.0
+    if P:
+        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=values.device)
+        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=values.device)
+        mat[:, ii, jj] = values[:, states:]
+        mat[:, jj, ii] = values[:, states:] if sign > 0 else -values[:, states:]
+    return mat
+
+
+def check_small_gap(small_gap):
+    """The ``small_gap`` argument of the methods that divide by a gap."""
+    if small_gap not in ("raise", "nan"):
+        raise ValueError(f"small_gap = {small_gap!r} ('raise' or 'nan')")
+
+
+# what the two steps of the CASCI gradient methods hand each other: the rows asked for; energies [G, R] and ci [G, R, Dc]
+# of the WHOLE stack; the RDMs [G, n, ...] of the n vectors (states, then the +, then the - polarisation vectors of
+# ``pairs``) and the generalised Fock matrices [G, R + P, N, N] of the sets; ``extra``: the number of density sets the
+# caller adds to the pass
+CASCISets = namedtuple("CASCISets", "rows energies ci nroots pairs extra gamma Gamma fock")
+
+
 class OO_pqc_batch:
     def __init__(self, pqc, mols, ncas, nelecas, oao_mo_coeffs=None, freeze_active=False):
         """
@@ -262,32 +316,68 @@ class OO_pqc_batch:
         if getattr(self, "overlap", None) is None:
             raise RuntimeError("OO_pqc_batch.rhf needs a batch made by OO_pqc_batch.from_geometries")
         scf.check_scope(self.nao, nelectron=self.nelectron)
-        if index is None:
-            sel = slice(None)
-        else:
-            rows = [int(i) for i in np.atleast_1d(index)]
-            if any(not 0 <= r < self.G for r in rows):
-                raise ValueError(f"index must hold rows in 0..{self.G - 1}")
-            if rows == list(range(rows[0], rows[0] + len(rows))):
-                sel = slice(rows[0], rows[0] + len(rows))             # (a view: no copy of the integrals)
-            else:
-                sel = torch.as_tensor(rows, device=self.device)
+        sel = rows_selector(stack_rows(self.G, index), self.device)
         res = scf.rhf_batch(self.int1e_ao[sel], self.int2e_ao[sel], self.overlap[sel], self.nelectron // 2,
                             oao_coeff=self.oao_coeff[sel], **kw)
         return res._replace(e_tot=res.e_elec + self.nuc[sel])
 
     # ---- forces (auto_oo_amd/nucgrad.py, csrc/gto_grad.hip) ----------------------------------------------------------
-    def _gradient_rows(self, index, who):
+    def _moment_rows(self, index, who):
+        """The rows ``index`` of a batch made by ``from_geometries`` (RuntimeError otherwise, under the name ``who``)."""
         if self.basis is None or self.coords_bohr is None:
             raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries")
-        if index is None:
-            rows = list(range(self.G))
-        else:
-            rows = [int(i) for i in np.atleast_1d(index)]
-            if any(not 0 <= r < self.G for r in rows):
-                raise ValueError(f"index must hold rows in 0..{self.G - 1}")
+        return stack_rows(self.G, index)
+
+    def _gradient_rows(self, index, who):
+        rows = self._moment_rows(index, who)
         GTO.refuse_d_gradient(self.basis)         # before anything is launched
         return rows
+
+    def _point_charge_rows(self, index, who):
+        rows = self._gradient_rows(index, who)
+        if self.charge_q is None:
+            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries(point_charges=...)")
+        return rows
+
+    def _charge_pull(self, sel, d1, nuc):
+        """``gto.point_charge_gradient_into`` of the density ``d1`` at the rows ``sel`` (an index tensor) of an embedded
+        batch -> (the charges' pull on the atoms [len(sel), natm, 3], the derivative with respect to the charges'
+        positions [len(sel), M, 3]); ``nuc``: with the nuclei's term."""
+        return GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
+                                              self.charge_xyz_bohr[sel], d1, nuc)
+
+    def _refuse_large_ncas(self, who, verb="covers"):
+        if self.ncas > nucgrad.MAX_NCAS:
+            raise NotImplementedError(f"{who} {verb} ncas <= {nucgrad.MAX_NCAS}")
+
+    def _circuit_rdms(self, thetas, who, verb="covers", sector=False):
+        """The RDMs gamma [G, a, a], Gamma [G, a, a, a, a] of the circuit states at ``thetas`` [G, n_theta], whole stack,
+        as the evaluation path makes them (dense register: ``ops.circuit_rdms``; sector engine: the RDMs of
+        ``_evaluate_sector``, served only with ``sector``: NotImplementedError otherwise)."""
+        pqc = self.pqc
+        in_sector = getattr(pqc, "_use_sector", False)
+        if in_sector and not sector:
+            raise NotImplementedError(f"{who} covers dense-register circuits; circuits in the sector engine "
+                                      "(more than 10 qubits) are not implemented")
+        self._refuse_large_ncas(who, verb)
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        if in_sector:
+            return pqc._sector.rdms(pqc._sector.state(thetas))
+        gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
+                                        pqc._init_index, tangents=False)
+        return gamma[:, 0], Gamma[:, 0]
+
+    def _rhf_density(self, result, index, rows):
+        """``(result, index, rows) -> (result, D1)``: the ``scf.RHFResult`` of the rows (``self.rhf(index=index)``, which
+        must converge, when none is given; ValueError for one of another number of geometries) and its closed-shell
+        ``D1 = 2 C_o C_o^T`` [len(rows), N, N]."""
+        if result is None:
+            result = self.rhf(index=index)
+            scf.raise_unless_converged(result.info, rows)
+        if int(result.mo_coeff.shape[0]) != len(rows):
+            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
+                             "for")
+        return result, nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
 
     def _dm2_buffer(self, n):
         """[n, N, N, N, N] for the AO two-particle density of a chunk: the size of ``int2e_ao`` per geometry, so it is
@@ -313,34 +403,19 @@ class OO_pqc_batch:
         ``from_geometries`` (RuntimeError otherwise).  Dense-register circuits only: a circuit in the sector engine
         (more than 10 qubits) raises NotImplementedError -- its RDMs would serve, that path has not been tested."""
         rows = self._gradient_rows(index, "nuclear_gradient")
-        if getattr(self.pqc, "_use_sector", False):
-            raise NotImplementedError("nuclear_gradient covers dense-register circuits; circuits in the sector engine "
-                                      "(more than 10 qubits) are not implemented")
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"nuclear_gradient covers ncas <= {nucgrad.MAX_NCAS}")
-        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
-        pqc = self.pqc
-        gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
-                                        pqc._init_index, tangents=False)
-        _, _, fock = self._cas_batch(gamma, Gamma, self.G, want_fock=True)
+        gamma, Gamma = self._circuit_rdms(thetas, "nuclear_gradient")
+        _, _, fock = self._cas_batch(gamma[:, None], Gamma[:, None], self.G, want_fock=True)
         step = len(rows) if chunk is None else max(1, int(chunk))
         out = torch.empty((len(rows), self.basis.natm, 3), dtype=F64, device=self.device)
         for k in range(0, len(rows), step):
             sel = torch.as_tensor(rows[k:k + step], device=self.device)
-            d1, d2 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel, 0],
-                                              Gamma[sel, 0], out=self._dm2_buffer(len(sel)))
+            d1, d2 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel], Gamma[sel],
+                                              out=self._dm2_buffer(len(sel)))
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
             out[k:k + step] = GTO.gradient_into(self.basis, self.coords_bohr[sel], d1, wq, d2, True)
             if self.charge_q is not None:
-                out[k:k + step] += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                                                  self.charge_xyz_bohr[sel], d1, True)[0]
+                out[k:k + step] += self._charge_pull(sel, d1, True)[0]
         return out
-
-    def _point_charge_rows(self, index, who):
-        rows = self._gradient_rows(index, who)
-        if self.charge_q is None:
-            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries(point_charges=...)")
-        return rows
 
     def point_charge_gradient(self, thetas, index=None):
         """dE/dr_k of every geometry of an embedded batch -> [G', M, 3] (device, Hartree / Bohr): the derivative of
@@ -350,35 +425,18 @@ class OO_pqc_batch:
         parameters.  ``index``, the scope and the errors are those of ``nuclear_gradient``; RuntimeError for a batch
         without point charges."""
         rows = self._point_charge_rows(index, "point_charge_gradient")
-        if getattr(self.pqc, "_use_sector", False):
-            raise NotImplementedError("point_charge_gradient covers dense-register circuits; circuits in the sector "
-                                      "engine (more than 10 qubits) are not implemented")
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"point_charge_gradient covers ncas <= {nucgrad.MAX_NCAS}")
-        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
-        pqc = self.pqc
-        gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
-                                        pqc._init_index, tangents=False)
+        gamma, Gamma = self._circuit_rdms(thetas, "point_charge_gradient")
         sel = torch.as_tensor(rows, device=self.device)
-        d1 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel, 0], Gamma[sel, 0],
+        d1 = nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel], Gamma[sel],
                                       want_d2=False)[0]
-        return GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                              self.charge_xyz_bohr[sel], d1, True)[1]
+        return self._charge_pull(sel, d1, True)[1]
 
     def rhf_point_charge_gradient(self, result=None, index=None):
         """dE_RHF/dr_k -> [G', M, 3] (device, Hartree / Bohr) of an embedded batch from a converged ``scf.RHFResult``
         of the rows ``index`` (``self.rhf(index=index)`` is run when none is given), as ``rhf_nuclear_gradient``."""
         rows = self._point_charge_rows(index, "rhf_point_charge_gradient")
-        if result is None:
-            result = self.rhf(index=index)
-            scf.raise_unless_converged(result.info, rows)
-        if int(result.mo_coeff.shape[0]) != len(rows):
-            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
-                             "for")
-        sel = torch.as_tensor(rows, device=self.device)
-        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
-        return GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                              self.charge_xyz_bohr[sel], d1, True)[1]
+        _, d1 = self._rhf_density(result, index, rows)
+        return self._charge_pull(torch.as_tensor(rows, device=self.device), d1, True)[1]
 
     def casci_nuclear_gradients(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200):
         """CASCI states of every geometry at its current orbitals (``casci``) with their state and interstate nuclear
@@ -414,37 +472,33 @@ class OO_pqc_batch:
         integrals are used).  Needs a batch made by ``from_geometries`` (RuntimeError otherwise); d shells and
         ``ncas > nucgrad.MAX_NCAS`` raise NotImplementedError, a CI problem out of scope ValueError
         (``ci.check_scope``)."""
-        rows, e, vecs, out = self._casci_gradient_pass("casci_nuclear_gradients", nroots, fix_singlet, index, chunk, tol,
-                                                       max_iter)
-        sel = torch.as_tensor(rows, device=self.device)
-        return CASCIGradients(e[sel], vecs[sel], out)
+        sets = self._casci_sets("casci_nuclear_gradients", nroots, fix_singlet, index, tol, max_iter)
+        values, _ = self._casci_derivative_pass(sets, chunk)
+        sel = torch.as_tensor(sets.rows, device=self.device)
+        return CASCIGradients(sets.energies[sel], sets.ci[sel], pair_matrix(values, sets.nroots))
 
-    def _casci_gradient_pass(self, who, nroots, fix_singlet, index, chunk, tol, max_iter, after_solve=None,
-                             interstate=True, relax=None):
-        """The body of ``casci_nuclear_gradients`` -> (rows, energies [G, R], ci [G, R, Dc] of the WHOLE stack, gradients
-        [len(rows), R, R, natm, 3]).  ``after_solve(rows, energies)`` is called between the CASCI solve and the pass over
-        the derivative integrals (what it raises leaves before that pass).  ``interstate=False`` leaves the pair sets
-        out (the off-diagonal elements of the result are then not filled).  ``relax(rows, fock [G, R, N, N])``, called
-        once after the Fock matrices are made, returns the function ``per_chunk(k0, sel, d1, d2, wq, out)`` that is
-        given the fixed-orbital densities of the R states of the chunk ``sel = rows[k0:k0 + c]`` and the place ``out``
-        [c, R, N, N, N, N] for R more two-particle densities, and returns their (D1, WQ) [c, R, N, N]: the R extra sets
-        ride in the same pass over the derivative integrals, as states, and a fifth value is returned: ``(gradients of
-        the extra sets [len(rows), R, natm, 3], their point_charge_gradient [len(rows), R, M, 3] or None)``."""
+    def _casci_gradient_scope(self, who, nroots, index):
+        """The rows ``index`` and the refusals the CASCI gradient methods share, in their order."""
         from . import ci
         rows = self._gradient_rows(index, who)
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"{who} covers ncas <= {nucgrad.MAX_NCAS}")
+        self._refuse_large_ncas(who)
         ci.check_scope(self.ncas, self.nelecas, nroots)
+        return rows
+
+    def _casci_sets(self, who, nroots, fix_singlet, index, tol, max_iter, interstate=True, extra=0):
+        """Step one of the CASCI gradient methods -> ``CASCISets``: the CASCI solve of the whole stack, then the RDMs of
+        the R states and of the 2 P polarisation vectors of their pairs and the generalised Fock matrices of the R + P
+        sets.  ``interstate=False`` leaves the pair sets out.  ``extra``: the number of further density sets the caller
+        will add to the pass (they count towards ``gto.MAX_GRAD_SETS``)."""
+        from . import ci
+        rows = self._casci_gradient_scope(who, nroots, index)
         e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
-        if after_solve is not None:
-            after_solve(rows, e)
-        G, R, a, N, natm = self.G, int(nroots), self.ncas, self.nao, self.basis.natm
+        G, R, a, N = self.G, int(nroots), self.ncas, self.nao
         pairs = nucgrad.state_pairs(R) if interstate else []
         P = len(pairs)
         n, K = R + 2 * P, R + P
-        X = 0 if relax is None else R                          # extra sets
-        if K + X > GTO.MAX_GRAD_SETS:
-            raise ValueError(f"{who}: {K + X} density sets per geometry (1 .. {GTO.MAX_GRAD_SETS})")
+        if K + extra > GTO.MAX_GRAD_SETS:
+            raise ValueError(f"{who}: {K + extra} density sets per geometry (1 .. {GTO.MAX_GRAD_SETS})")
         # RDMs and generalised Fock matrices of the R states and the 2 P polarisation vectors, whole stack
         stack = nucgrad.polarisation_vectors(vecs) if interstate else vecs
         gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
@@ -454,16 +508,27 @@ class OO_pqc_batch:
         for s in range(n):      # (the CAS path takes the RDMs of set 0 for the Fock matrix: one call per vector)
             fock[:, s] = self._cas_batch(gamma[:, s:s + 1], Gamma[:, s:s + 1], G, want_fock=True)[2]
         fock = nucgrad.transition_sets(fock, R) if interstate else fock
-        per_chunk = None if relax is None else relax(rows, fock[:, :R])
-        extra = torch.empty((len(rows), X, natm, 3), dtype=F64, device=self.device)
-        extra_q = None
+        return CASCISets(rows, e, vecs, R, pairs, int(extra), gamma, Gamma, fock)
+
+    def _casci_derivative_pass(self, sets, chunk, more_sets=None):
+        """Step two: the chunked pass over the derivative integrals for the ``CASCISets`` of step one -> ``(values
+        [len(rows), R + P + extra, natm, 3], charge_values)``: the nuclear gradients of the R states, the P interstate
+        elements and the extra sets, the charges' pull on the atoms included for an embedded batch.
+
+        ``more_sets(k0, sel, d1, d2, wq, out)`` provides ``sets.extra`` more density sets per geometry: it is given the
+        fixed-orbital densities of the R states of the chunk ``sel = rows[k0:k0 + c]`` and the place ``out`` [c, extra,
+        N, N, N, N] for their two-particle densities, and returns their (D1, WQ) [c, extra, N, N]; they ride in the same
+        pass, as states, and ``charge_values`` [len(rows), extra, M, 3] is their ``point_charge_gradient`` (None without
+        extra sets or point charges)."""
+        rows, R, pairs, gamma, Gamma, fock = sets.rows, sets.nroots, sets.pairs, sets.gamma, sets.Gamma, sets.fock
+        a, N, natm = self.ncas, self.nao, self.basis.natm
+        P, X = len(pairs), sets.extra
+        K = R + P
+        values = torch.empty((len(rows), K + X, natm, 3), dtype=F64, device=self.device)
+        charge_values = None
         if X and self.charge_q is not None:
-            extra_q = torch.empty((len(rows), X, int(self.charge_q.shape[1]), 3), dtype=F64, device=self.device)
+            charge_values = torch.empty((len(rows), X, int(self.charge_q.shape[1]), 3), dtype=F64, device=self.device)
         step = len(rows) if chunk is None else max(1, int(chunk))
-        out = torch.empty((len(rows), R, R, natm, 3), dtype=F64, device=self.device)
-        k = torch.arange(R, device=self.device)
-        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
-        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
         for k0 in range(0, len(rows), step):
             sel = torch.as_tensor(rows[k0:k0 + step], device=self.device)
             c = len(sel)
@@ -481,32 +546,21 @@ class OO_pqc_batch:
                 t = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma[sel][:, pm], Gamma[sel][:, pm], out=tmp)[1]
                 d2[:, R + p].copy_(t[:, 0].sub_(t[:, 1]).mul_(0.5))
             wq = nucgrad.overlap_pullback(self.overlap[sel], self.oao_mo_coeff[sel], fock[sel])
-            if per_chunk is not None:
-                more = per_chunk(k0, sel, d1[:, :R], d2[:, :R], wq[:, :R], d2[:, K:])
+            if more_sets is not None:
+                more = more_sets(k0, sel, d1[:, :R], d2[:, :R], wq[:, :R], d2[:, K:])
                 d1, wq = torch.cat((d1, more[0]), dim=1), torch.cat((wq, more[1]), dim=1)
             val = GTO.gradient_sets_into(self.basis, self.coords_bohr[sel], d1, wq, d2,
                                          [True] * R + [False] * P + [True] * X)
             if self.charge_q is not None:
-                # the charges' pull on the atoms, one pass per set: with the nuclei's term for a state, without it
-                # for a transition density
-                for s in range(K):
-                    val[:, s] += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                                                self.charge_xyz_bohr[sel], d1[:, s], s < R)[0]
-            extra[k0:k0 + c] = val[:, K:]
-            if extra_q is not None:
-                for s in range(X):
-                    pull = GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                                          self.charge_xyz_bohr[sel], d1[:, K + s], True)
-                    extra[k0:k0 + c, s] += pull[0]
-                    extra_q[k0:k0 + c, s] = pull[1]
-            blk = out[k0:k0 + c]
-            blk[:, k, k] = val[:, :R]
-            if P:
-                blk[:, ii, jj] = val[:, R:K]
-                blk[:, jj, ii] = val[:, R:K]
-        if relax is not None:
-            return rows, e, vecs, out, (extra, extra_q)
-        return rows, e, vecs, out
+                # the charges' pull on the atoms, one pass per set: with the nuclei's term for a state (or an extra set),
+                # without it for a transition density
+                for s in range(K + X):
+                    pull = self._charge_pull(sel, d1[:, s], s < R or s >= K)
+                    val[:, s] += pull[0]
+                    if s >= K:
+                        charge_values[k0:k0 + c, s - K] = pull[1]
+            values[k0:k0 + c] = val
+        return values, charge_values
 
     def casci_derivative_couplings(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200,
                                    min_gap=1e-6, small_gap="raise"):
@@ -538,31 +592,27 @@ class OO_pqc_batch:
         ``index``, ``chunk``, the scope and the errors are those of ``casci_nuclear_gradients``; the same bits whatever
         ``index`` and ``chunk``."""
         from . import ci
-        if small_gap not in ("raise", "nan"):
-            raise ValueError(f"small_gap = {small_gap!r} ('raise' or 'nan')")
+        check_small_gap(small_gap)
         who = "casci_derivative_couplings"
-        R, a, N = int(nroots), self.ncas, self.nao
-        pairs = nucgrad.state_pairs(R)
         min_gap = float(min_gap)
-
-        def gaps_ok(rows, e):
-            if small_gap != "raise" or not pairs:
-                return
-            eh = e.detach().cpu().numpy()
+        sets = self._casci_sets(who, nroots, fix_singlet, index, tol, max_iter)
+        rows, R, pairs, a, N = sets.rows, sets.nroots, sets.pairs, self.ncas, self.nao
+        if small_gap == "raise" and pairs:
+            # (before the pass over the derivative integrals)
+            eh = sets.energies.detach().cpu().numpy()
             bad = [(g, i, j) for g in rows for i, j in pairs if abs(eh[g, i] - eh[g, j]) < min_gap]
             if bad:
                 raise ValueError(f"{who}: |E_J - E_I| < {min_gap:g} Ha for (geometry, I, J) = "
                                  + ", ".join(str(b) for b in bad) + ": the coupling diverges there "
                                  "(small_gap='nan' marks these elements instead)")
-
-        rows, e, vecs, grads = self._casci_gradient_pass(who, nroots, fix_singlet, index, chunk, tol, max_iter, gaps_ok)
+        grads = pair_matrix(self._casci_derivative_pass(sets, chunk)[0], R)
         natm = self.basis.natm
         sel = torch.as_tensor(rows, device=self.device)
         c, P = len(rows), len(pairs)
-        e, vecs = e[sel], vecs[sel]
-        ci_term = torch.zeros((c, R, R, natm, 3), dtype=F64, device=self.device)
-        orb = torch.zeros_like(ci_term)
-        if P and c:
+        e, vecs = sets.energies[sel], sets.ci[sel]
+        if not (P and c):       # no pair or no row: nothing to compute, the matrices are zero
+            orb_val = ci_val = torch.empty((c, P, natm, 3), dtype=F64, device=self.device)
+        else:
             ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
             jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
             # transition 1-RDMs <c_I|E_pq|c_J> of the pairs (I > J) and their antisymmetric parts
@@ -576,16 +626,14 @@ class OO_pqc_batch:
             a_mo[:, self._n_occ:self._n_occ + a, self._n_occ:self._n_occ + a] = asym
             wqc = nucgrad.connection_pullback(self.overlap[sel], self.oao_mo_coeff[sel], a_mo.view(c, P, N, N))
             xyz = self.coords_bohr[sel]
-            val = GTO.overlap_connection_into(self.basis, xyz, Da.view(c, P, N, N))
-            val = val + GTO.gradient_sets_into(self.basis, xyz, None, wqc, None, False)
-            orb[:, ii, jj] = val
-            orb[:, jj, ii] = -val
+            orb_val = GTO.overlap_connection_into(self.basis, xyz, Da.view(c, P, N, N))
+            orb_val = orb_val + GTO.gradient_sets_into(self.basis, xyz, None, wqc, None, False)
             gap = e[:, jj] - e[:, ii]                                    # E_J - E_I of element (I, J)
-            cval = grads[:, ii, jj] / gap[:, :, None, None]
+            ci_val = grads[:, ii, jj] / gap[:, :, None, None]
             if small_gap == "nan":
-                cval = torch.where((gap.abs() < min_gap)[:, :, None, None], torch.full_like(cval, float("nan")), cval)
-            ci_term[:, ii, jj] = cval
-            ci_term[:, jj, ii] = -cval
+                ci_val = torch.where((gap.abs() < min_gap)[:, :, None, None], torch.full_like(ci_val, float("nan")),
+                                     ci_val)
+        ci_term, orb = pair_matrix(ci_val, R, -1), pair_matrix(orb_val, R, -1)
         return CASCICouplings(e, vecs, grads, ci_term + orb, ci_term, orb)
 
     def casci_relaxed_gradients(self, nroots=2, fix_singlet=True, index=None, chunk=None, tol=1e-9, max_iter=200,
@@ -617,21 +665,13 @@ class OO_pqc_batch:
         ``index``, ``chunk``, the other arguments, the scope and the errors are those of ``casci_nuclear_gradients``; the
         same bits whatever ``index``, ``chunk`` and the stack around a geometry.  Not covered: relaxed interstate
         elements and derivative couplings, orbitals other than RHF orbitals, d shells."""
-        from . import ci
         who = "casci_relaxed_gradients"
-        if small_gap not in ("raise", "nan"):
-            raise ValueError(f"small_gap = {small_gap!r} ('raise' or 'nan')")
-        rows = self._gradient_rows(index, who)
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"{who} covers ncas <= {nucgrad.MAX_NCAS}")
-        ci.check_scope(self.ncas, self.nelecas, nroots)
+        check_small_gap(small_gap)
+        rows = self._casci_gradient_scope(who, nroots, index)
         scf.check_scope(self.nao, nelectron=self.nelectron)
         R, a, N, n_core, n_occ = int(nroots), self.ncas, self.nao, self._n_occ, self.nelectron // 2
         _, dg = nucgrad.response_pairs(N, n_core, a, n_occ)
-        if rows == list(range(rows[0], rows[0] + len(rows))):
-            take = slice(rows[0], rows[0] + len(rows))                # (a view: no copy of the integrals)
-        else:
-            take = torch.as_tensor(rows, device=self.device)
+        take = rows_selector(rows, self.device)
         # the RHF Fock matrix of the batch's own orbitals: canonical? gaps?
         g, h, C = self.int2e_ao[take], self.int1e_ao[take], self.mo_coeff[take].contiguous()
         mm = ops.matmul_nn_batch
@@ -654,37 +694,34 @@ class OO_pqc_batch:
             raise ValueError(f"{who}: |eps_p - eps_q| < {float(min_gap):g} Ha for (geometry, p, q) = "
                              + ", ".join(str(c) for c in close) + ": the orbital response diverges there "
                              "(small_gap='nan' marks the states of these geometries instead)")
-        state = {}
+        # the states alone, and R more sets in the pass: the relaxed densities
+        sets = self._casci_sets(who, nroots, fix_singlet, index, tol, max_iter, interstate=False, extra=R)
+        # one Z-vector solve per state, from the orbital gradient of its generalised Fock matrix
+        w = nucgrad.orbital_gradient(sets.fock[take])
+        res = nucgrad.zvector(g, C, eps, n_core, a, n_occ, w, z_tol, z_max_iter, min_gap)
+        z_info = res.info
+        codes = z_info.cpu().numpy()
+        wrong = [(r, i, int(codes[k, i])) for k, r in enumerate(rows) for i in range(R) if codes[k, i] not in (0, -4)]
+        if wrong:
+            raise _lib.OovqeError(f"{who}: the Z-vector solve failed for (geometry, state: code) = " + ", ".join(
+                f"({r}, {i}: {c} {nucgrad.Z_INFO.get(c, '')})" for r, i, c in wrong))
+        z = torch.where((z_info == -4)[:, :, None, None], torch.zeros_like(res.z), res.z)
 
-        def relax(rows_, fock):
-            w = nucgrad.orbital_gradient(fock[take])
-            res = nucgrad.zvector(g, C, eps, n_core, a, n_occ, w, z_tol, z_max_iter, min_gap)
-            codes = res.info.cpu().numpy()
-            wrong = [(r, i, int(codes[k, i])) for k, r in enumerate(rows_) for i in range(R) if codes[k, i] not in (0, -4)]
-            if wrong:
-                raise _lib.OovqeError(f"{who}: the Z-vector solve failed for (geometry, state: code) = " + ", ".join(
-                    f"({r}, {i}: {c} {nucgrad.Z_INFO.get(c, '')})" for r, i, c in wrong))
-            state["info"] = res.info
-            z = torch.where((res.info == -4)[:, :, None, None], torch.zeros_like(res.z), res.z)
+        def relaxed_sets(k0, sel, d1, d2, wq, out):
+            c = len(sel)
+            out.copy_(d2)
+            d1r, _, wqr = nucgrad.relaxed_densities(h[k0:k0 + c], g[k0:k0 + c], self.overlap[sel],
+                                                    self.oao_mo_coeff[sel], C[k0:k0 + c], n_occ, z[k0:k0 + c], d1,
+                                                    out, wq, fock_ao=fock_ao[k0:k0 + c])
+            return d1r, wqr
 
-            def per_chunk(k0, sel, d1, d2, wq, out):
-                c = len(sel)
-                out.copy_(d2)
-                d1r, _, wqr = nucgrad.relaxed_densities(h[k0:k0 + c], g[k0:k0 + c], self.overlap[sel],
-                                                        self.oao_mo_coeff[sel], C[k0:k0 + c], n_occ, z[k0:k0 + c], d1,
-                                                        out, wq, fock_ao=fock_ao[k0:k0 + c])
-                return d1r, wqr
-            return per_chunk
-
-        rows, e, vecs, out, (grad, grad_q) = self._casci_gradient_pass(who, nroots, fix_singlet, index, chunk, tol,
-                                                                       max_iter, interstate=False, relax=relax)
+        values, grad_q = self._casci_derivative_pass(sets, chunk, relaxed_sets)
         sel = torch.as_tensor(rows, device=self.device)
-        k = torch.arange(R, device=self.device)
-        marked = (state["info"] == -4)[:, :, None, None]
-        grad = torch.where(marked, torch.full_like(grad, float("nan")), grad)
+        marked = (z_info == -4)[:, :, None, None]
+        grad = torch.where(marked, torch.full_like(values[:, R:], float("nan")), values[:, R:])
         if grad_q is not None:
             grad_q = torch.where(marked, torch.full_like(grad_q, float("nan")), grad_q)
-        return CASCIRelaxedGradients(e[sel], vecs[sel], grad, out[:, k, k], state["info"], grad_q)
+        return CASCIRelaxedGradients(sets.energies[sel], sets.ci[sel], grad, values[:, :R].contiguous(), z_info, grad_q)
 
     def rhf_nuclear_gradient(self, result=None, index=None):
         """Closed-shell Hartree-Fock gradient -> [G, natm, 3] (device, Hartree / Bohr) from a converged
@@ -692,32 +729,15 @@ class OO_pqc_batch:
         ``D = 2 C_o C_o^T`` and the energy-weighted density ``WQ = -2 C_o eps_o C_o^T``.  Exact for converged orbitals
         only (the orbital gradient is taken as zero)."""
         rows = self._gradient_rows(index, "rhf_nuclear_gradient")
-        if result is None:
-            result = self.rhf(index=index)
-            scf.raise_unless_converged(result.info, rows)
-        if int(result.mo_coeff.shape[0]) != len(rows):
-            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
-                             "for")
+        result, d1 = self._rhf_density(result, index, rows)
         sel = torch.as_tensor(rows, device=self.device)
         grad = nucgrad.rhf_gradient(self.basis, self.coords_bohr[sel], result.mo_coeff, result.mo_energy,
                                     self.nelectron // 2)
         if self.charge_q is not None:
-            d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
-            grad += GTO.point_charge_gradient_into(self.basis, self.coords_bohr[sel], self.charge_q[sel],
-                                                   self.charge_xyz_bohr[sel], d1, True)[0]
+            grad += self._charge_pull(sel, d1, True)[0]
         return grad
 
     # ---- dipole and second moments (auto_oo_amd/properties.py, csrc/gto_moments.hip) -----------------------------------
-    def _moment_rows(self, index, who):
-        if self.basis is None or self.coords_bohr is None:
-            raise RuntimeError(f"{who} needs a batch made by OO_pqc_batch.from_geometries")
-        if index is None:
-            return list(range(self.G))
-        rows = [int(i) for i in np.atleast_1d(index)]
-        if any(not 0 <= r < self.G for r in rows):
-            raise ValueError(f"index must hold rows in 0..{self.G - 1}")
-        return rows
-
     def _moments_of(self, rows, dens, order, origin, nuclear=True):
         """Moments [len(rows), nd, 3 or 9] of the densities ``dens`` [len(rows), nd, N, N] at the geometries ``rows``;
         ``origin`` [3] or [len(rows), 3] in Angstrom."""
@@ -730,16 +750,7 @@ class OO_pqc_batch:
         """``D1`` [len(rows), N, N] of the circuit states at ``thetas`` and the batch's current orbitals, from the RDMs
         the evaluation path makes (dense register: ``ops.circuit_rdms``; sector engine: the RDMs of
         ``_evaluate_sector``)."""
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"the moments of a circuit state cover ncas <= {nucgrad.MAX_NCAS}")
-        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
-        pqc = self.pqc
-        if getattr(pqc, "_use_sector", False):
-            gamma, Gamma = pqc._sector.rdms(pqc._sector.state(thetas))
-        else:
-            gamma, Gamma = ops.circuit_rdms(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, self.ncas,
-                                            pqc._init_index, tangents=False)
-            gamma, Gamma = gamma[:, 0], Gamma[:, 0]
+        gamma, Gamma = self._circuit_rdms(thetas, "the moments of a circuit state", "cover", sector=True)
         sel = torch.as_tensor(rows, device=self.device)
         return nucgrad.cas_ao_densities(self.mo_coeff[sel], self._n_occ, self.ncas, gamma[sel], Gamma[sel],
                                         want_d2=False)[0]
@@ -772,14 +783,25 @@ class OO_pqc_batch:
         """Closed-shell Hartree-Fock dipole moment [G, 3] (device, atomic units) from a ``scf.RHFResult`` of the rows
         ``index`` (default all; ``self.rhf(index=index)`` is run when none is given): ``D = 2 C_o C_o^T``."""
         rows = self._moment_rows(index, "rhf_dipole_moment")
-        if result is None:
-            result = self.rhf(index=index)
-            scf.raise_unless_converged(result.info, rows)
-        if int(result.mo_coeff.shape[0]) != len(rows):
-            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
-                             "for")
-        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+        _, d1 = self._rhf_density(result, index, rows)
         return self._moments_of(rows, d1[:, None], 1, origin)[:, 0]
+
+    def _casci_densities(self, who, nroots, fix_singlet, tol, max_iter):
+        """The CASCI solve of the whole stack and the AO one-particle densities of its roots and pairs of roots ->
+        (energies [G, R], dens [G, R + P, N, N], nuclear [R + P]): the R states' ``D1``, then for the P pairs of
+        ``nucgrad.state_pairs`` the transition density as the half-difference of the densities of ``(c_I +- c_J) /
+        sqrt 2`` (``nucgrad.polarisation_vectors``, ``nucgrad.transition_sets``); ``nuclear``: which sets carry the
+        nuclear term (the states)."""
+        from . import ci
+        self._refuse_large_ncas(who)
+        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
+        G, R, a = self.G, int(nroots), self.ncas
+        stack = nucgrad.polarisation_vectors(vecs)
+        n = int(stack.shape[1])
+        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
+        d1 = nucgrad.cas_ao_densities(self.mo_coeff, self._n_occ, a, gamma.reshape(G, n, a, a),
+                                      Gamma.reshape((G, n) + (a,) * 4), want_d2=False)[0]
+        return e, nucgrad.transition_sets(d1, R), [True] * R + [False] * ((n - R) // 2)
 
     def casci_dipole_matrix(self, nroots=2, fix_singlet=True, origin=None, tol=1e-9, max_iter=200):
         """CASCI states of every geometry at its current orbitals (``casci``) and their dipole matrix -> (energies
@@ -794,30 +816,8 @@ class OO_pqc_batch:
         ``overlaps.track_roots`` on the ``O`` of ``casci_overlaps`` gives the order and signs that are continuous along a
         path, ``overlaps.apply_tracking`` applies them to ``dipoles``."""
         rows = self._moment_rows(None, "casci_dipole_matrix")
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"casci_dipole_matrix covers ncas <= {nucgrad.MAX_NCAS}")
-        from . import ci
-        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
-        G, R, a = self.G, int(nroots), self.ncas
-        pairs = [(i, j) for i in range(R) for j in range(i)]
-        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
-        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
-        r2 = 0.5 ** 0.5
-        stack = torch.cat((vecs, r2 * (vecs[:, ii] + vecs[:, jj]), r2 * (vecs[:, ii] - vecs[:, jj])), dim=1)
-        n, P = R + 2 * len(pairs), len(pairs)
-        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
-        C = self.mo_coeff[:, None].expand(G, n, self.nao, self.nao).reshape(G * n, self.nao, self.nao)
-        d1 = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma, Gamma, want_d2=False)[0]
-        d1 = d1.reshape(G, n, self.nao, self.nao)
-        dens = torch.cat((d1[:, :R], 0.5 * (d1[:, R:R + P] - d1[:, R + P:])), dim=1)
-        val = self._moments_of(rows, dens, 1, origin, nuclear=[True] * R + [False] * P)
-        dip = torch.empty((G, R, R, 3), dtype=F64, device=self.device)
-        k = torch.arange(R, device=self.device)
-        dip[:, k, k] = val[:, :R]
-        if P:
-            dip[:, ii, jj] = val[:, R:]
-            dip[:, jj, ii] = val[:, R:]
-        return e, dip
+        e, dens, nuclear = self._casci_densities("casci_dipole_matrix", nroots, fix_singlet, tol, max_iter)
+        return e, pair_matrix(self._moments_of(rows, dens, 1, origin, nuclear=nuclear), int(nroots))
 
     # ---- electrostatic potential and field at arbitrary points (csrc/gto_potential.hip) ---------------------------------
     def _potential_of(self, rows, dens, points, field, nuclear=True):
@@ -825,17 +825,7 @@ class OO_pqc_batch:
         [M, 3] or [len(rows), M, 3] in Angstrom.  More than ``gto.MAX_GRAD_SETS`` densities go in several calls (a set has
         the same bits whatever the other sets of its call)."""
         sel = torch.as_tensor(rows, device=self.device)
-        r = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points
-        r = np.asarray(r, dtype=np.float64)
-        if r.ndim == 2:
-            r = np.broadcast_to(r, (len(rows),) + r.shape)
-        if r.ndim != 3 or r.shape[0] != len(rows) or r.shape[2] != 3:
-            raise ValueError(f"points of shape {np.shape(points)}, expected [M, 3] or [{len(rows)}, M, 3]")
-        if not 1 <= r.shape[1] <= GTO.MAX_POINTS:
-            raise ValueError(f"{r.shape[1]} points per geometry (1 .. {GTO.MAX_POINTS})")
-        if not np.isfinite(r).all():
-            raise ValueError("the points must be finite")
-        pts = torch.as_tensor(np.array(r / GTO.BOHR)).to(self.device)
+        pts = torch.as_tensor(GTO.points_host(points, len(rows))).to(self.device)
         nd = int(dens.shape[1])
         flags = [bool(nuclear)] * nd if isinstance(nuclear, (bool, np.bool_)) else [bool(f) for f in nuclear]
         xyz = self.coords_bohr[sel]
@@ -876,13 +866,7 @@ class OO_pqc_batch:
         ``electrostatic_potential``: with the orbitals of an embedded batch, ``phi`` at the position of charge k is
         ``dE_RHF / dq_k``."""
         rows = self._moment_rows(index, "rhf_electrostatic_potential")
-        if result is None:
-            result = self.rhf(index=index)
-            scf.raise_unless_converged(result.info, rows)
-        if int(result.mo_coeff.shape[0]) != len(rows):
-            raise ValueError(f"the RHF result holds {int(result.mo_coeff.shape[0])} geometries, {len(rows)} rows asked "
-                             "for")
-        d1 = nucgrad.cas_ao_densities(result.mo_coeff, self.nelectron // 2, 0, want_d2=False)[0]
+        _, d1 = self._rhf_density(result, index, rows)
         out = self._potential_of(rows, d1[:, None], points, field)
         return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]
 
@@ -897,33 +881,9 @@ class OO_pqc_batch:
         (``overlaps.apply_tracking`` works on it).  ``points`` and the embedded case as for
         ``electrostatic_potential``."""
         rows = self._moment_rows(None, "casci_electrostatic_potential")
-        if self.ncas > nucgrad.MAX_NCAS:
-            raise NotImplementedError(f"casci_electrostatic_potential covers ncas <= {nucgrad.MAX_NCAS}")
-        from . import ci
-        e, vecs = self.casci(nroots, fix_singlet, tol, max_iter)
-        G, R, a = self.G, int(nroots), self.ncas
-        pairs = [(i, j) for i in range(R) for j in range(i)]
-        ii = torch.as_tensor([p[0] for p in pairs], dtype=torch.long, device=self.device)
-        jj = torch.as_tensor([p[1] for p in pairs], dtype=torch.long, device=self.device)
-        r2 = 0.5 ** 0.5
-        stack = torch.cat((vecs, r2 * (vecs[:, ii] + vecs[:, jj]), r2 * (vecs[:, ii] - vecs[:, jj])), dim=1)
-        n, P = R + 2 * len(pairs), len(pairs)
-        gamma, Gamma = ci.sector_rdms(stack.reshape(G * n, -1), a, self.nelecas)
-        C = self.mo_coeff[:, None].expand(G, n, self.nao, self.nao).reshape(G * n, self.nao, self.nao)
-        d1 = nucgrad.cas_ao_densities(C, self._n_occ, a, gamma, Gamma, want_d2=False)[0]
-        d1 = d1.reshape(G, n, self.nao, self.nao)
-        dens = torch.cat((d1[:, :R], 0.5 * (d1[:, R:R + P] - d1[:, R + P:])), dim=1)
-        out = self._potential_of(rows, dens, points, field, nuclear=[True] * R + [False] * P)
-        k = torch.arange(R, device=self.device)
-        mats = []
-        for val in (out if field else (out,)):
-            mat = torch.empty((G, R, R) + tuple(val.shape[2:]), dtype=F64, device=self.device)
-            mat[:, k, k] = val[:, :R]
-            if P:
-                mat[:, ii, jj] = val[:, R:]
-                mat[:, jj, ii] = val[:, R:]
-            mats.append(mat)
-        return (e, *mats)
+        e, dens, nuclear = self._casci_densities("casci_electrostatic_potential", nroots, fix_singlet, tol, max_iter)
+        out = self._potential_of(rows, dens, points, field, nuclear=nuclear)
+        return (e, *(pair_matrix(val, int(nroots)) for val in (out if field else (out,))))
 
     # ---- overlaps between the states of different geometries (auto_oo_amd/overlaps.py, csrc/overlap.hip) --------------
     def _pair_rows(self, pairs, closed):

@@ -682,6 +682,23 @@ def _nuc_mask(nuc, K):
     return sum(1 << k for k, b in enumerate(bits) if b)
 
 
+def points_host(points, G):
+    """``points`` of ``potential_batch`` and of the batch's potential methods ([M, 3] shared by all geometries, or
+    [G, M, 3], in Angstrom; array or tensor) -> a checked host array [G, M, 3] in Bohr: the shape, 1 <= M <=
+    ``MAX_POINTS``, finite.  Host work only."""
+    r = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points
+    r = np.asarray(r, dtype=np.float64)
+    if r.ndim == 2:
+        r = np.broadcast_to(r, (G,) + r.shape)
+    if r.ndim != 3 or r.shape[0] != G or r.shape[2] != 3:
+        raise ValueError(f"points of shape {np.shape(points)}, expected [M, 3] or [{G}, M, 3]")
+    if not 1 <= r.shape[1] <= MAX_POINTS:
+        raise ValueError(f"{r.shape[1]} points per geometry (1 .. {MAX_POINTS})")
+    if not np.isfinite(r).all():
+        raise ValueError("the points must be finite")
+    return np.array(r / BOHR)
+
+
 def potential_into(basis, coords_bohr, points_bohr, dm, nuc=True, field=False, work=None):
     """``potential_batch`` for device tensors in atomic units (geometries [G, natm, 3] and points [G, M, 3] in Bohr, ``dm``
     [G, K, N, N]), on the current stream -> ``phi`` [G, K, M], or ``(phi, F [G, K, M, 3])`` with ``field``.  ``work``: a
@@ -745,17 +762,7 @@ def potential_batch(basis, coords, points, dm, nuc=True, field=False):
     xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
     G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
     N = basis.nao
-    r = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points
-    r = np.asarray(r, dtype=np.float64)
-    if r.ndim == 2:
-        r = np.broadcast_to(r, (G,) + r.shape)
-    if r.ndim != 3 or r.shape[0] != G or r.shape[2] != 3:
-        raise ValueError(f"points of shape {np.shape(points)}, expected [M, 3] or [{G}, M, 3]")
-    M = int(r.shape[1])
-    if not 1 <= M <= MAX_POINTS:
-        raise ValueError(f"{M} points per geometry (1 .. {MAX_POINTS})")
-    if not np.isfinite(r).all():
-        raise ValueError("the points must be finite")
+    r = points_host(points, G)
     if not isinstance(dm, torch.Tensor) or dm.dim() not in (3, 4):
         raise ValueError(f"dm has shape {tuple(getattr(dm, 'shape', ()))}, expected [{G}, {N}, {N}] or [{G}, K, {N}, {N}]")
     squeeze = dm.dim() == 3
@@ -768,8 +775,7 @@ def potential_batch(basis, coords, points, dm, nuc=True, field=False):
     if not bool(torch.isfinite(d4).all()):
         raise ValueError("the densities must be finite")
     device = _lib.require_device()
-    out = potential_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(np.array(r / BOHR)).to(device), d4,
-                         nuc, field)
+    out = potential_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(r).to(device), d4, nuc, field)
     if not squeeze:
         return out
     return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]

@@ -289,3 +289,101 @@ def test_get_formal_geo_tokens():
                     ["H", "1", "0.987109", "2", "140", "3", "80"]]
     rows = [ln.split() for ln in aoo.get_formal_geo(120.5, 125).splitlines() if ln.strip()]
     assert rows[-1] == ["H", "1", "0.987109", "2", "120.5", "3", "125"]
+
+
+# ---- the shared host steps of the stack properties (auto_oo_amd/batch.py) ---------------------------
+def test_stack_rows():
+    from auto_oo_amd.batch import stack_rows
+    assert stack_rows(4, None) == [0, 1, 2, 3]
+    assert stack_rows(4, 2) == [2] and stack_rows(4, np.int64(3)) == [3]
+    assert stack_rows(4, [2, 0]) == [2, 0] and stack_rows(4, (1, 1)) == [1, 1]
+    assert stack_rows(4, np.array([3, 0, 1])) == [3, 0, 1] and stack_rows(4, torch.tensor([0, 3])) == [0, 3]
+    assert all(type(r) is int for r in stack_rows(4, np.array([3, 0])))
+    for bad in (4, -1, [0, 4], [-1, 0]):
+        with pytest.raises(ValueError) as err:
+            stack_rows(4, bad)
+        assert str(err.value) == "index must hold rows in 0..3"
+
+
+def test_rows_selector():
+    from auto_oo_amd.batch import rows_selector
+    x = torch.arange(5 * 2, dtype=torch.float64).reshape(5, 2)
+    assert rows_selector([3]) == slice(3, 4)                                  # one row
+    assert rows_selector([0, 1, 2]) == slice(0, 3)                            # a run
+    assert rows_selector([2, 3, 4]) == slice(2, 5)                            # a run not starting at 0
+    for rows in ([3], [0, 1, 2], [2, 3, 4]):
+        view = x[rows_selector(rows)]
+        assert view.data_ptr() == x[rows[0]].data_ptr() and torch.equal(view, x[torch.tensor(rows)])   # a view
+    for rows in ([2, 0, 1], [1, 1], [0, 2], [1, 0]):                          # a permutation, a repeated row, a gap
+        sel = rows_selector(rows)
+        assert isinstance(sel, torch.Tensor) and sel.dtype == torch.long and sel.tolist() == rows
+        assert torch.equal(x[sel], torch.stack([x[r] for r in rows]))
+
+
+@pytest.mark.parametrize("R", [1, 2, 3])
+@pytest.mark.parametrize("trailing", [(3,), (4,), (4, 3), (5, 3)])           # [3], [M], [M, 3], [natm, 3]
+def test_pair_matrix(R, trailing):
+    from auto_oo_amd import nucgrad
+    from auto_oo_amd.batch import pair_matrix
+    pairs = nucgrad.state_pairs(R)
+    P, c = len(pairs), 2
+    values = torch.as_tensor(np.random.default_rng(R).standard_normal((c, R + P) + trailing))
+    mat = pair_matrix(values, R)
+    assert tuple(mat.shape) == (c, R, R) + trailing and mat.dtype == values.dtype
+    assert torch.equal(mat, mat.transpose(1, 2))
+    for s in range(R):
+        assert torch.equal(mat[:, s, s], values[:, s])
+    for p, (i, j) in enumerate(pairs):
+        assert i > j and torch.equal(mat[:, i, j], values[:, R + p]) and torch.equal(mat[:, j, i], values[:, R + p])
+    anti = pair_matrix(values[:, R:], R, -1)
+    assert tuple(anti.shape) == (c, R, R) + trailing
+    assert torch.equal(anti, -anti.transpose(1, 2))
+    for s in range(R):
+        assert torch.equal(anti[:, s, s], torch.zeros((c,) + trailing, dtype=values.dtype))
+    for p, (i, j) in enumerate(pairs):
+        assert torch.equal(anti[:, i, j], values[:, R + p]) and torch.equal(anti[:, j, i], -values[:, R + p])
+    for bad in (values[:, :R + P - 1] if R > 1 else values[:, :0], torch.cat((values, values[:, :1]), dim=1)):
+        with pytest.raises(ValueError, match="values of shape"):
+            pair_matrix(bad, R)
+    with pytest.raises(ValueError, match="values of shape"):
+        pair_matrix(values, R, -1)
+    with pytest.raises(ValueError, match="sign"):
+        pair_matrix(values, R, 0)
+
+
+def test_small_gap_argument():
+    from auto_oo_amd.batch import check_small_gap
+    check_small_gap("raise")
+    check_small_gap("nan")
+    with pytest.raises(ValueError) as err:
+        check_small_gap("zero")
+    assert str(err.value) == "small_gap = 'zero' ('raise' or 'nan')"
+
+
+def test_points_host():
+    from auto_oo_amd import gto
+    from auto_oo_amd.gaussian import BOHR
+    shared = np.random.default_rng(3).standard_normal((4, 3))
+    r = gto.points_host(shared, 3)                                            # one [M, 3] for all geometries
+    assert r.shape == (3, 4, 3) and r.dtype == np.float64 and r.flags.c_contiguous and r.flags.writeable
+    for g in range(3):
+        assert np.array_equal(r[g], shared / BOHR)
+    per = np.random.default_rng(4).standard_normal((2, 5, 3))
+    assert np.array_equal(gto.points_host(per, 2), per / BOHR)
+    assert np.array_equal(gto.points_host(torch.as_tensor(per), 2), per / BOHR)
+    assert np.array_equal(gto.points_host(per.tolist(), 2), per / BOHR)
+    for bad in (np.zeros(3), np.zeros((4, 2)), np.zeros((3, 4, 3)), np.zeros((2, 4, 3, 1))):
+        with pytest.raises(ValueError) as err:
+            gto.points_host(bad, 2)
+        assert str(err.value) == f"points of shape {bad.shape}, expected [M, 3] or [2, M, 3]"
+    for M in (0, gto.MAX_POINTS + 1):
+        with pytest.raises(ValueError) as err:
+            gto.points_host(np.zeros((M, 3)), 2)
+        assert str(err.value) == f"{M} points per geometry (1 .. {gto.MAX_POINTS})"
+    assert gto.points_host(np.zeros((gto.MAX_POINTS, 3)), 1).shape == (1, gto.MAX_POINTS, 3)
+    for bad in (np.inf, -np.inf, np.nan):
+        pts = np.zeros((2, 4, 3))
+        pts[1, 2, 0] = bad
+        with pytest.raises(ValueError) as err:
+            gto.points_host(pts, 2)
+        assert str(err.value) == "the points must be finite"

@@ -371,6 +371,21 @@ def test_casci_dipole_matrix():
     assert dip[:, 1, 0].abs().max().item() > 1e-3 or dip[:, 2, 0].abs().max().item() > 1e-3
 
 
+def test_casci_dipole_matrix_of_one_root():
+    """``nroots=1``: no pair, the matrix is the one root's dipole -- the same library call on the same ``D1``, so the same
+    bits."""
+    b = cas_batch("ucc", 2)
+    e, dip = b.casci_dipole_matrix(nroots=1)
+    e0, vecs = b.casci(nroots=1)
+    assert tuple(e.shape) == (2, 1) and tuple(dip.shape) == (2, 1, 1, 3)
+    assert torch.equal(e, e0)
+    g1, g2 = ci.sector_rdms(vecs.reshape(2, -1), b.ncas, b.nelecas)
+    d1 = nucgrad.cas_ao_densities(b.mo_coeff, b._n_occ, b.ncas, g1, g2, want_d2=False)[0].reshape(2, 1, b.nao, b.nao)
+    want = properties.multipole_moments(b.basis, b.coords_bohr, d1, order=1)
+    print("dipole of the one root", dip[:, 0, 0].tolist(), "multipole_moments of its D1", want[:, 0].tolist())
+    assert torch.equal(dip[:, 0, 0], want[:, 0])
+
+
 # ---- 7. errors ----------------------------------------------------------------------------------------------------------------
 def test_errors():
     pqc, ncas, nelecas = _circuit()

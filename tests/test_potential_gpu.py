@@ -374,6 +374,23 @@ def test_casci_electrostatic_potential():
     assert tuple(tracked.shape) == tuple(phi.shape) and torch.equal(tracked, tracked.transpose(1, 2))
 
 
+def test_casci_electrostatic_potential_of_one_root():
+    """``nroots=1``: no pair, the matrices are the one root's potential and field -- the same library call on the same
+    ``D1``, so the same bits."""
+    b = cas_batch("ucc", 2)
+    pts = batch_points(2, 3)
+    e, phi, F = b.casci_electrostatic_potential(pts, nroots=1, field=True)
+    e0, vecs = b.casci(nroots=1)
+    assert tuple(e.shape) == (2, 1) and tuple(phi.shape) == (2, 1, 1, 3) and tuple(F.shape) == (2, 1, 1, 3, 3)
+    assert torch.equal(e, e0)
+    g1, g2 = ci.sector_rdms(vecs.reshape(2, -1), b.ncas, b.nelecas)
+    d1 = nucgrad.cas_ao_densities(b.mo_coeff, b._n_occ, b.ncas, g1, g2, want_d2=False)[0].reshape(2, 1, b.nao, b.nao)
+    wphi, wF = gto.potential_into(b.basis, b.coords_bohr, to_dev(pts / BOHR), d1, True, True)
+    print("potential of the one root", phi[:, 0, 0].tolist(), "potential_into of its D1", wphi[:, 0].tolist())
+    assert torch.equal(phi[:, 0, 0], wphi[:, 0]) and torch.equal(F[:, 0, 0], wF[:, 0])
+    assert torch.equal(b.casci_electrostatic_potential(pts, nroots=1)[1], phi)
+
+
 def test_errors_of_the_batch_methods():
     pqc, ncas, nelecas = _circuit()
     from auto_oo_amd.gaussian import Moldata_sto3g
