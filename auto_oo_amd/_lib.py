@@ -78,6 +78,9 @@ SIGNATURES = {
     "oovqe_circuit_state": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_uint32, ctypes.c_int, c_double_p,
                                            c_double_p, c_stream]),
+    "oovqe_circuit_state_ws": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_uint32, ctypes.c_int, c_double_p,
+                                              c_double_p, c_double_p, c_stream]),
     "oovqe_rdms": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   c_double_p, c_double_p, c_double_p, c_stream]),
     "oovqe_rdms_tangent": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int,

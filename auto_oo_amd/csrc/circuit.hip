@@ -7,6 +7,7 @@
 // becomes complex.  Tangent states d psi / d theta_k come from the same pass with the k-th gate
 // replaced by its derivative (forward mode).
 #include "internal.h"
+#include <vector>
 #include "circuit_small.h"
 
 namespace {
@@ -66,13 +67,16 @@ __device__ void run_circuit(double* w, uint32_t D, uint32_t init_index, const do
 
 // grid = batch * (1 + n_tan); block b*(1+n_tan) + 0 -> psi, + (1+k) -> d psi / d theta_k.
 // use_lds: the working state lives in LDS (D <= LDS_STATE_MAX) and is copied / accumulated to
-// the output; otherwise the output vector itself is the working state (then a parameter may
-// drive at most one gate - checked on the host).
+// the output; otherwise the output vector itself is the working state of the first gate a
+// parameter drives, and every further gate of that parameter runs in this block's slice of
+// `scratch` ([batch][n_theta][D], laid out as dpsi) and is added to the output.  The host passes
+// scratch whenever a parameter drives several gates (circuit_state_launch); without it only
+// circuits whose parameters drive one gate each are launched.
 __global__ __launch_bounds__(CIRC_THREADS)
 void circuit_kernel(const double* __restrict__ theta, int n_theta,
                     const oovqe_gate_t* __restrict__ gates, int n_gates, int n_qubits,
                     uint32_t init_index, int n_tan, double* __restrict__ psi,
-                    double* __restrict__ dpsi, int use_lds)
+                    double* __restrict__ dpsi, int use_lds, double* __restrict__ scratch)
 {
     extern __shared__ double lds[];
     const uint32_t D = 1u << n_qubits;
@@ -102,6 +106,11 @@ void circuit_kernel(const double* __restrict__ theta, int n_theta,
             __syncthreads();
         } else if (first) {
             run_circuit(dst, D, init_index, th, gates, n_gates, g);
+        } else if (scratch) {
+            double* w = scratch + ((size_t)b * n_theta + k) * D;
+            run_circuit(w, D, init_index, th, gates, n_gates, g);
+            for (uint32_t x = threadIdx.x; x < D; x += CIRC_THREADS) dst[x] += w[x];
+            __syncthreads();
         }
         first = false;
     }
@@ -561,9 +570,34 @@ void hessian_operands_kernel(const double* __restrict__ psi, const double* __res
 
 }  // namespace
 
-extern "C" int oovqe_circuit_state(const double* theta, int n_theta, const oovqe_gate_t* gates,
-                                   int n_gates, int n_qubits, uint32_t init_index, int batch,
-                                   double* psi, double* dpsi, oovqe_stream_t stream)
+// Does any parameter drive more than one gate?  The gate table lives on the device: it is read back on
+// `st` (a few dozen bytes per gate), which a stream under capture cannot do.
+static int circuit_shares_parameters(const oovqe_gate_t* gates, int n_gates, int n_theta, hipStream_t st, bool* shared)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    OOVQE_CHECK_HIP(hipStreamIsCapturing(st, &cap), "circuit_state: capture status");
+    OOVQE_REQUIRE(cap == hipStreamCaptureStatusNone,
+                  "circuit_state: tangents beyond %d amplitudes without scratch need the gate table on the host, "
+                  "which a capturing stream cannot read: pass scratch (oovqe_circuit_state_ws)", LDS_STATE_MAX);
+    std::vector<oovqe_gate_t> host((size_t)n_gates);
+    OOVQE_CHECK_HIP(hipMemcpyAsync(host.data(), gates, (size_t)n_gates * sizeof(oovqe_gate_t), hipMemcpyDeviceToHost, st),
+                    "circuit_state: gate table read-back");
+    OOVQE_CHECK_HIP(hipStreamSynchronize(st), "circuit_state: gate table read-back");
+    std::vector<char> seen((size_t)n_theta, 0);
+    *shared = false;
+    for (const oovqe_gate_t& g : host) {
+        if (g.theta_idx < 0 || g.theta_idx >= n_theta) continue;
+        if (seen[g.theta_idx]) *shared = true;
+        seen[g.theta_idx] = 1;
+    }
+    return 0;
+}
+
+// psi and tangents; scratch [batch][n_theta][D] or null.  Registers beyond LDS_STATE_MAX amplitudes need it for
+// the tangent of a parameter that drives several gates: without it such a call is refused.
+static int circuit_state_launch(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
+                                int n_qubits, uint32_t init_index, int batch, double* psi, double* dpsi,
+                                double* scratch, oovqe_stream_t stream)
 {
     OOVQE_REQUIRE(theta && gates && psi, "circuit_state: null pointer");
     OOVQE_REQUIRE(n_qubits >= 2 && n_qubits <= 26, "circuit_state: n_qubits=%d", n_qubits);
@@ -573,14 +607,38 @@ extern "C" int oovqe_circuit_state(const double* theta, int n_theta, const oovqe
     const int use_lds = D <= (uint32_t)LDS_STATE_MAX;
     const int n_tan = dpsi ? n_theta : 0;
     const size_t lds_bytes = use_lds ? (size_t)D * sizeof(double) : 0;
+    if (!use_lds && n_tan > 0 && !scratch) {
+        bool shared = false;
+        if (int rc_sh = circuit_shares_parameters(gates, n_gates, n_theta, (hipStream_t)stream, &shared)) return rc_sh;
+        OOVQE_REQUIRE(!shared,
+                      "circuit_state: a parameter drives several gates and the register (%d qubits) is beyond the "
+                      "LDS-resident %d amplitudes: its tangent needs scratch (oovqe_circuit_state_ws)",
+                      n_qubits, LDS_STATE_MAX);
+    }
     if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)circuit_kernel, LDS_STATE_MAX * (int)sizeof(double))) return rc_lds;
     const long nblocks = (long)batch * (1 + n_tan);
     OOVQE_REQUIRE(nblocks <= 0x7fffffffL, "circuit_state: grid too large");
     hipLaunchKernelGGL(circuit_kernel, dim3((unsigned)nblocks), dim3(CIRC_THREADS), lds_bytes,
                        (hipStream_t)stream, theta, n_theta, gates, n_gates, n_qubits, init_index,
-                       n_tan, psi, dpsi, use_lds);
+                       n_tan, psi, dpsi, use_lds, use_lds ? nullptr : scratch);
     OOVQE_CHECK_LAUNCH("circuit_state");
     return 0;
+}
+
+extern "C" int oovqe_circuit_state(const double* theta, int n_theta, const oovqe_gate_t* gates,
+                                   int n_gates, int n_qubits, uint32_t init_index, int batch,
+                                   double* psi, double* dpsi, oovqe_stream_t stream)
+{
+    return circuit_state_launch(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi, dpsi, nullptr,
+                                stream);
+}
+
+extern "C" int oovqe_circuit_state_ws(const double* theta, int n_theta, const oovqe_gate_t* gates,
+                                      int n_gates, int n_qubits, uint32_t init_index, int batch,
+                                      double* psi, double* dpsi, double* scratch, oovqe_stream_t stream)
+{
+    return circuit_state_launch(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi, dpsi, scratch,
+                                stream);
 }
 
 extern "C" int oovqe_rdms(const double* bra, const double* ket, int n_qubits, int ncas, int batch,
@@ -680,8 +738,10 @@ int oovqe_circuit_rdms_w(const double* theta, int n_theta, const oovqe_gate_t* g
     // general path: separate launches, vectors in HBM/L2
     OOVQE_REQUIRE(psi && work && (!want_tangents || dpsi),
                   "circuit_rdms: psi/dpsi/work buffers required for this size");
-    int rc = oovqe_circuit_state(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi,
-                                 want_tangents ? dpsi : nullptr, stream);
+    // the RDM work (nvec a^2 D doubles per element >= n_theta D) is idle until the states are done: it is the
+    // scratch of the tangents
+    int rc = circuit_state_launch(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi,
+                                  want_tangents ? dpsi : nullptr, want_tangents ? work : nullptr, stream);
     if (rc) return rc;
     return oovqe_rdms_tangent(psi, want_tangents ? dpsi : nullptr, n_qubits, ncas, n_tan, batch,
                               gamma, Gamma, work, stream);
@@ -762,7 +822,9 @@ int oovqe_circuit_hessian_batched_impl(const double* theta, int n_theta, const o
     double* rwork = g2 + 4 * nb * n_pairs * na2 * na2;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = oovqe_circuit_state(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi, dpsi, stream)))
+    // scratch | bra | ket (9 n_pairs D doubles per element, contiguous) are idle until the tangents are done
+    if ((rc = circuit_state_launch(theta, n_theta, gates, n_gates, n_qubits, init_index, batch, psi, dpsi,
+                                   n_theta <= 9 * n_pairs ? scratch : nullptr, stream)))
         return rc;
     OOVQE_REQUIRE(n_qubits >= 2 && n_qubits <= 26 && n_gates >= 1 && n_theta >= 1, "circuit_hessian: bad sizes");
     hipLaunchKernelGGL(circuit_second_tangent_kernel, dim3(n_pairs, batch), dim3(CIRC_THREADS), 0, st, theta,

@@ -159,17 +159,35 @@ def expm(X, sign=1.0):
     return U
 
 
-def circuit_state(theta, gates_dev, n_gates, n_qubits, init_index, tangents=False):
-    """theta [batch, n_theta] -> psi [batch, D] (and dpsi [batch, n_theta, D])."""
+LDS_STATE_MAX = 8192     # amplitudes of the LDS-resident register of oovqe_circuit_state (13 qubits)
+
+
+def shares_parameters(gates_dev, n_gates):
+    """does a parameter of the packed gate table drive several gates?  (reads the table back from the device)"""
+    idx = gates_dev.cpu().numpy().view(np.int32).reshape(n_gates, -1)[:, 3]
+    idx = idx[idx >= 0]
+    return len(np.unique(idx)) < len(idx)
+
+
+def circuit_state(theta, gates_dev, n_gates, n_qubits, init_index, tangents=False, shared=None):
+    """theta [batch, n_theta] -> psi [batch, D] (and dpsi [batch, n_theta, D]).  ``shared``: whether a parameter
+    drives several gates (None: read from the gate table when it matters) -- beyond the LDS-resident register the
+    tangents of such a circuit are summed through a second [batch, n_theta, D] buffer."""
     lib = _lib.load()
     dev = _dev(theta)
     batch, n_theta = theta.shape
     D = 1 << n_qubits
     psi = torch.empty((batch, D), dtype=F64, device=dev)
     dpsi = torch.empty((batch, n_theta, D), dtype=F64, device=dev) if tangents else None
-    check(lib.oovqe_circuit_state(dptr(theta), n_theta, dptr(gates_dev, torch.uint8), n_gates,
-                                  n_qubits, ctypes.c_uint32(init_index), batch, dptr(psi),
-                                  dptr(dpsi), stream_ptr()), "oovqe_circuit_state")
+    scratch = None
+    if tangents and D > LDS_STATE_MAX and n_gates >= 1:
+        if shared is None:
+            shared = shares_parameters(gates_dev, n_gates)
+        if shared:
+            scratch = torch.empty((batch, n_theta, D), dtype=F64, device=dev)
+    check(lib.oovqe_circuit_state_ws(dptr(theta), n_theta, dptr(gates_dev, torch.uint8), n_gates,
+                                     n_qubits, ctypes.c_uint32(init_index), batch, dptr(psi),
+                                     dptr(dpsi), dptr(scratch), stream_ptr()), "oovqe_circuit_state")
     return (psi, dpsi) if tangents else psi
 
 

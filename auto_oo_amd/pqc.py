@@ -92,6 +92,8 @@ class Parameterized_circuit():
         self.wires = range(self.n_qubits)
         self._init_index = X.basis_index(self.hfstate)
         self._n_gates = len(self._gates)
+        driven = [int(g.theta_idx) for g in self._gates if g.theta_idx >= 0]
+        self._shared = len(set(driven)) < len(driven)     # a parameter drives several gates
         self._gates_dev = torch.as_tensor(X.gates_to_numpy(self._gates)).to(self.device)
         # (N_alpha, N_beta)-sector engine: one-launch circuits + reverse-mode gradients for active
         # spaces beyond the small one-workgroup kernel (e.g. kUpCCD CAS(8e,8o), 16 qubits)
@@ -120,7 +122,7 @@ class Parameterized_circuit():
         if self._use_sector and not tangents:
             return self._sector.state(th, dense=True)[1][0]
         res = ops.circuit_state(th, self._gates_dev, self._n_gates, self.n_qubits,
-                                self._init_index, tangents=tangents)
+                                self._init_index, tangents=tangents, shared=self._shared)
         if tangents:
             return res[0][0], res[1][0]
         return res[0]

@@ -143,6 +143,13 @@ int oovqe_expm(const double* X, double sign, int N, double* U, double* work,
 int oovqe_circuit_state(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
                         int n_qubits, uint32_t init_index, int batch, double* psi, double* dpsi,
                         oovqe_stream_t stream);
+/* The same with scratch [batch, n_theta, D] (or NULL).  Beyond 8192 amplitudes (14 qubits and more) the tangent of a
+ * parameter that drives several gates (OrbitalRotation, GateFabric, a custom table) is summed gate by gate through
+ * scratch; oovqe_circuit_state, which has none, refuses such a call (it reads the gate table back to find out, so it
+ * cannot be captured into a graph there).  Smaller registers and unshared parameters never touch scratch. */
+int oovqe_circuit_state_ws(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates,
+                           int n_qubits, uint32_t init_index, int batch, double* psi, double* dpsi,
+                           double* scratch, oovqe_stream_t stream);
 /* gamma[b,p,q] = bra_b^T E_pq ket_b ; Gamma[b,p,q,r,s] = bra_b^T (E_pq E_rs - d_qr E_ps) ket_b.
  * bra == ket gives the reference's RDMs; bra != ket gives transition RDMs (used for
  * d gamma / d theta = T(dpsi,psi) + T(psi,dpsi)).  work: [batch * 2 * ncas^2 * D] scratch.    */
