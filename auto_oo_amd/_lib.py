@@ -249,6 +249,13 @@ SIGNATURES = {
                                                  ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,
                                                  ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_uint]
                                   + [c_double_p] * 3 + [c_stream]),
+    "oovqe_gto_density_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                               ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int,
+                                               c_double_p, ctypes.c_int] + [c_double_p] * 3 + [c_stream]),
+    "oovqe_gto_orbital_values_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p, c_double_p,
+                                                      ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                      ctypes.c_int, c_double_p, ctypes.c_int] + [c_double_p] * 3
+                                       + [c_stream]),
     "oovqe_gto_overlap_connection_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
     "oovqe_gto_overlap_connection_batch": (ctypes.c_int, [ctypes.c_int, c_int32_p, ctypes.c_int, c_double_p,
                                                           c_double_p, ctypes.c_int, c_double_p, ctypes.c_int,

@@ -885,6 +885,92 @@ class OO_pqc_batch:
         out = self._potential_of(rows, dens, points, field, nuclear=nuclear)
         return (e, *(pair_matrix(val, int(nroots)) for val in (out if field else (out,))))
 
+    # ---- electron density, its gradient and orbital values at arbitrary points (csrc/gto_density.hip) -------------------
+    def _density_of(self, rows, dens, points, gradient):
+        """``gto.density_into`` of the densities ``dens`` [len(rows), nd, N, N] at the geometries ``rows``; ``points``
+        [M, 3] or [len(rows), M, 3] in Angstrom.  More than ``gto.MAX_GRAD_SETS`` densities go in several calls (a set has
+        the same bits whatever the other sets of its call)."""
+        sel = torch.as_tensor(rows, device=self.device)
+        pts = torch.as_tensor(GTO.points_host(points, len(rows))).to(self.device)
+        nd = int(dens.shape[1])
+        xyz = self.coords_bohr[sel]
+        rhos, grads = [], []
+        for a in range(0, nd, GTO.MAX_GRAD_SETS):
+            out = GTO.density_into(self.basis, xyz, pts, dens[:, a:min(nd, a + GTO.MAX_GRAD_SETS)], gradient)
+            rhos.append(out[0] if gradient else out)
+            if gradient:
+                grads.append(out[1])
+        rho = rhos[0] if len(rhos) == 1 else torch.cat(rhos, dim=1)
+        if not gradient:
+            return rho
+        return rho, (grads[0] if len(grads) == 1 else torch.cat(grads, dim=1))
+
+    def electron_density(self, thetas, points, index=None, gradient=False):
+        """The electron density of every geometry's state at ``thetas`` [G, n_theta] and the batch's current orbitals at
+        ``points``, in atomic units: ``rho[g, m] = sum D1[mu, nu] chi_mu(r_m) chi_nu(r_m)`` (``gto.density_batch`` of the
+        density of ``_state_density``).
+
+        Args:
+            points: [M, 3] shared by all rows, or one [M, 3] per row asked for, in Angstrom like the geometries
+            index: rows of the batch (default all); the result then has one entry per row asked for
+            gradient: also return ``d rho / d r`` [G, M, 3] in e / Bohr^4
+
+        Returns ``rho`` [G, M] in e / Bohr^3 on the device, or ``(rho, drho)``.  Needs a batch made by ``from_geometries``
+        (RuntimeError otherwise); ncas <= 8; dense-register circuits only: a circuit of the sector engine (more than 10
+        qubits) raises NotImplementedError before anything is launched.  Same bits whatever ``index``."""
+        rows = self._moment_rows(index, "electron_density")
+        if getattr(self.pqc, "_use_sector", False):
+            raise NotImplementedError("electron_density covers dense-register circuits; circuits in the sector engine "
+                                      "(more than 10 qubits) are not implemented")
+        out = self._density_of(rows, self._state_density(thetas, rows)[:, None], points, gradient)
+        return (out[0][:, 0], out[1][:, 0]) if gradient else out[:, 0]
+
+    def rhf_electron_density(self, points, result=None, index=None, gradient=False):
+        """Closed-shell Hartree-Fock electron density [G, M] (and its gradient [G, M, 3]; device, atomic units) at
+        ``points`` from a ``scf.RHFResult`` of the rows ``index`` (default all; ``self.rhf(index=index)`` is run when none
+        is given): ``D = 2 C_o C_o^T``.  ``points`` and ``gradient`` as for ``electron_density``."""
+        rows = self._moment_rows(index, "rhf_electron_density")
+        _, d1 = self._rhf_density(result, index, rows)
+        out = self._density_of(rows, d1[:, None], points, gradient)
+        return (out[0][:, 0], out[1][:, 0]) if gradient else out[:, 0]
+
+    def casci_electron_density(self, points, nroots=2, fix_singlet=True, gradient=False, tol=1e-9, max_iter=200):
+        """CASCI states of every geometry at its current orbitals (``casci``) and the matrix of their densities at
+        ``points`` -> (energies [G, nroots], rho [G, nroots, nroots, M]) on the device, atomic units; with ``gradient``
+        also drho [G, nroots, nroots, M, 3].
+
+        ``rho[g, I, I]`` is the density of root I.  ``rho[g, I, J]``, I != J, is the transition density ``sum D^IJ chi
+        chi`` with the ``D^IJ`` of ``casci_dipole_matrix`` (the same ``gamma^IJ`` construction): exactly symmetric in
+        (I, J), and with the sign convention described there (``overlaps.apply_tracking`` works on it)."""
+        rows = self._moment_rows(None, "casci_electron_density")
+        e, dens, _ = self._casci_densities("casci_electron_density", nroots, fix_singlet, tol, max_iter)
+        out = self._density_of(rows, dens, points, gradient)
+        return (e, *(pair_matrix(val, int(nroots)) for val in (out if gradient else (out,))))
+
+    def orbital_values(self, points, columns=None, index=None, gradient=False):
+        """The values of the batch's current orbitals ``mo_coeff`` at ``points`` -> psi [G, ncol, M] in Bohr^-3/2 on the
+        device, with ``gradient`` ``(psi, dpsi [G, ncol, M, 3])`` (``gto.orbital_values_batch``).
+
+        Args:
+            points: as for ``electron_density``
+            columns: orbitals (columns of ``mo_coeff``) in the order wanted; default: the doubly occupied and the active
+                ones.  More than ``gto.MAX_GRAD_SETS`` go in several calls (same bits).
+            index: rows of the batch (default all)"""
+        rows = self._moment_rows(index, "orbital_values")
+        n = int(self.mo_coeff.shape[-1])
+        cols = list(range(self._n_occ + self.ncas)) if columns is None else [int(c) for c in columns]
+        if not cols or min(cols) < 0 or max(cols) >= n:
+            raise ValueError(f"columns = {columns!r}: orbitals 0 .. {n - 1}, at least one")
+        sel = torch.as_tensor(rows, device=self.device)
+        pts = torch.as_tensor(GTO.points_host(points, len(rows))).to(self.device)
+        C = self.mo_coeff[sel][:, :, torch.as_tensor(cols, device=self.device)]
+        xyz = self.coords_bohr[sel]
+        outs = [GTO.orbital_values_into(self.basis, xyz, pts, C[:, :, a:a + GTO.MAX_GRAD_SETS].contiguous(), gradient)
+                for a in range(0, len(cols), GTO.MAX_GRAD_SETS)]
+        if not gradient:
+            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        return tuple(o[0] if len(outs) == 1 else torch.cat(o, dim=1) for o in zip(*outs))
+
     # ---- overlaps between the states of different geometries (auto_oo_amd/overlaps.py, csrc/overlap.hip) --------------
     def _pair_rows(self, pairs, closed):
         """``pairs`` -> ([P] rows a, [P] rows b) on the host; the default is the loop (g, g + 1 mod G) when ``closed``,

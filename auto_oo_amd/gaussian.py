@@ -322,6 +322,95 @@ def potential_from_table(table, charges, coords_bohr, points_bohr, dm, d_functio
     return phi
 
 
+# ---- basis functions, density and orbitals at points (the twins of gto.density_batch, gto.orbital_values_batch) ------------
+POINT_CLAMP = 1e75             # Bohr: a coordinate of a point beyond +-POINT_CLAMP is taken as +-POINT_CLAMP (DEN_CLAMP)
+
+
+def _radial_sums(shell, r2):
+    """(sum_p c_p e^(-a_p r2), sum_p |c_p| e^(-a_p r2), sum_p -2 a_p c_p e^(-a_p r2), sum_p 2 a_p |c_p| e^(-a_p r2)) [M]
+    of a ``_Shell``"""
+    e = np.exp(-shell.exps[:, None] * r2[None, :])
+    c = shell.coefs[:, None]
+    a2 = 2.0 * shell.exps[:, None]
+    return np.sum(c * e, axis=0), np.sum(np.abs(c) * e, axis=0), np.sum(-a2 * c * e, axis=0), np.sum(a2 * np.abs(c) * e, axis=0)
+
+
+def _monomial(d, lmn):
+    """x^l y^m z^n [M] at the displacements d [M, 3] (x^0 = 1 at x = 0 as everywhere)"""
+    return d[:, 0] ** lmn[0] * d[:, 1] ** lmn[1] * d[:, 2] ** lmn[2]
+
+
+def _monomial_derivative(d, lmn, axis):
+    """d/dx_axis of ``_monomial``: l x^(l-1) y^m z^n, and 0 for l = 0"""
+    if lmn[axis] == 0:
+        return np.zeros(d.shape[0])
+    low = list(lmn)
+    low[axis] -= 1
+    return lmn[axis] * _monomial(d, low)
+
+
+def functions_at_points(table, coords_bohr, points_bohr, d_functions, gradient=False):
+    """The functions of ``integrals_from_table`` at the points [M, 3] (Bohr), from their definition: chi [N, M] and the
+    sum of the absolute values of the terms each is made of (primitives and Cartesian components), ``a`` [N, M]; with
+    ``gradient`` also d chi / d r [N, M, 3] and its absolute sum.  Returns (chi, a) or (chi, a, dchi, da)."""
+    R = np.asarray(coords_bohr, dtype=float).reshape(-1, 3)
+    P = np.clip(np.asarray(points_bohr, dtype=float).reshape(-1, 3), -POINT_CLAMP, POINT_CLAMP)
+    shells = shells_from_table(table, R)
+    M = P.shape[0]
+    chi, a = np.zeros((len(shells), M)), np.zeros((len(shells), M))
+    dchi, da = np.zeros((len(shells), M, 3)), np.zeros((len(shells), M, 3))
+    for i, sh in enumerate(shells):
+        d = P - sh.center[None, :]
+        r0, r0abs, r1, r1abs = _radial_sums(sh, np.sum(d * d, axis=1))
+        poly = _monomial(d, sh.lmn)
+        chi[i], a[i] = poly * r0, np.abs(poly) * r0abs
+        if gradient:
+            for ax in range(3):
+                low = _monomial_derivative(d, sh.lmn, ax)
+                dchi[i, :, ax] = low * r0 + d[:, ax] * poly * r1
+                da[i, :, ax] = np.abs(low) * r0abs + np.abs(d[:, ax] * poly) * r1abs
+    U = basis_transform(table, d_functions)
+    if not gradient:
+        return U @ chi, np.abs(U) @ a
+    return U @ chi, np.abs(U) @ a, np.einsum("pc,cmx->pmx", U, dchi), np.einsum("pc,cmx->pmx", np.abs(U), da)
+
+
+def density_from_table(table, coords_bohr, points_bohr, dm, d_functions, gradient=False):
+    """``rho[..., m] = sum_{mu nu} dm[..., mu, nu] chi_mu(r_m) chi_nu(r_m)`` at the points ``points_bohr`` [M, 3], on the
+    host and from the definition: the twin of ``gto.density_batch`` for one geometry.  ``dm`` is [N, N] or [K, N, N] over
+    the functions of ``integrals_from_table`` and is not taken as symmetric.  Returns ``(rho, A)``, each [M] or [K, M] in
+    e / Bohr^3, ``A`` the sum of the absolute values of all the terms of the value (the scale of its rounding error); with
+    ``gradient`` ``(rho, drho, A, dA)``, ``drho`` [..., M, 3] = d rho / d r_m in e / Bohr^4."""
+    D = np.asarray(dm, dtype=float)
+    f = functions_at_points(table, coords_bohr, points_bohr, d_functions, gradient)
+    N = f[0].shape[0]
+    if D.ndim not in (2, 3) or D.shape[-2:] != (N, N):
+        raise ValueError(f"dm of shape {D.shape}, expected [{N}, {N}] or [K, {N}, {N}]")
+    rho = np.einsum("...pq,pm,qm->...m", D, f[0], f[0], optimize=True)
+    A = np.einsum("...pq,pm,qm->...m", np.abs(D), f[1], f[1], optimize=True)
+    if not gradient:
+        return rho, A
+    drho = (np.einsum("...pq,pmx,qm->...mx", D, f[2], f[0], optimize=True)
+            + np.einsum("...pq,pm,qmx->...mx", D, f[0], f[2], optimize=True))
+    dA = (np.einsum("...pq,pmx,qm->...mx", np.abs(D), f[3], f[1], optimize=True)
+          + np.einsum("...pq,pm,qmx->...mx", np.abs(D), f[1], f[3], optimize=True))
+    return rho, drho, A, dA
+
+
+def orbital_values_from_table(table, coords_bohr, points_bohr, C, d_functions, gradient=False):
+    """``psi[i, m] = sum_mu C[mu, i] chi_mu(r_m)`` at the points ``points_bohr`` [M, 3] for the columns of ``C``
+    [N, ncol], on the host: the twin of ``gto.orbital_values_batch`` for one geometry.  Returns ``(psi [ncol, M], A)`` in
+    Bohr^-3/2, ``A`` as for ``density_from_table``; with ``gradient`` ``(psi, dpsi [ncol, M, 3], A, dA)``."""
+    C = np.asarray(C, dtype=float)
+    f = functions_at_points(table, coords_bohr, points_bohr, d_functions, gradient)
+    if C.ndim != 2 or C.shape[0] != f[0].shape[0]:
+        raise ValueError(f"C of shape {C.shape}, expected [{f[0].shape[0]}, ncol]")
+    psi, A = C.T @ f[0], np.abs(C).T @ f[1]
+    if not gradient:
+        return psi, A
+    return psi, np.einsum("pi,pmx->imx", C, f[2]), A, np.einsum("pi,pmx->imx", np.abs(C), f[3])
+
+
 # powers of (x - Ox, y - Oy, z - Oz) in the components of the moment integrals: x, y, z | xx, xy, xz, yy, yz, zz
 MOMENT_COMPONENTS = ((1, 0, 0), (0, 1, 0), (0, 0, 1)) + CARTESIAN_D
 

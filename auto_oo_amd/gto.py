@@ -781,6 +781,161 @@ def potential_batch(basis, coords, points, dm, nuc=True, field=False):
     return (out[0][:, 0], out[1][:, 0]) if field else out[:, 0]
 
 
+# ---- electron density, its gradient and orbital values at arbitrary points (csrc/gto_density.hip) ------------------------
+def _points_call(basis, coords_bohr, points_bohr, x, name, inner):
+    """The checks ``density_into`` and ``orbital_values_into`` share -> (G, M, K, xyz, pts, x) with contiguous float64
+    tensors on the device of the geometries; ``x`` is [G, K, *inner]."""
+    _check_stack(basis, coords_bohr)
+    G = int(coords_bohr.shape[0])
+    if G > 65535:
+        raise ValueError(f"{G} geometries in one call (at most 65535)")
+    if not isinstance(points_bohr, torch.Tensor) or points_bohr.dim() != 3 or tuple(points_bohr.shape[::2]) != (G, 3):
+        raise ValueError(f"points of shape {tuple(getattr(points_bohr, 'shape', ()))}, expected [{G}, M, 3]")
+    M = int(points_bohr.shape[1])
+    if not 1 <= M <= MAX_POINTS:
+        raise ValueError(f"{M} points per geometry (1 .. {MAX_POINTS})")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 + len(inner):
+        raise ValueError(f"{name} has shape {tuple(getattr(x, 'shape', ()))}, expected "
+                         f"{'[G, K, N, N]' if name == 'dm' else '[G, N, ncol]'}")
+    K = int(x.shape[1 if name == "dm" else 2])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} {'density sets' if name == 'dm' else 'coefficient columns'} per geometry "
+                         f"(1 .. {MAX_GRAD_SETS})")
+    _check_shape(name, x, (G, K) + inner if name == "dm" else (G,) + inner + (K,))
+    dev = coords_bohr.device
+    xyz = coords_bohr.to(F64).contiguous()
+    pts = points_bohr.to(device=dev, dtype=F64).contiguous()
+    x = x.to(device=dev, dtype=F64).contiguous()
+    if not (bool(torch.isfinite(xyz).all()) and bool(torch.isfinite(pts).all()) and bool(torch.isfinite(x).all())):
+        raise ValueError(f"coordinates, points and {name} must be finite")
+    return G, M, K, xyz, pts, x
+
+
+DENSITY_LDS_COLUMNS = 121      # (DEN_LDS_MAX - sizeof(gto_den_lds_t)) / 512: LDS columns of 64 doubles a workgroup may hold
+
+
+def density_max_sets(basis, gradient=False):
+    """The most density sets one call of ``density_into`` takes for this basis: the density kernel holds K + nshell LDS
+    columns (4 K + 2 nshell with the gradient) of ``DENSITY_LDS_COLUMNS``, and never more than ``MAX_GRAD_SETS`` sets.
+    0: the table has too many shells for the kernel (more than 120, or 58 with the gradient)."""
+    left = DENSITY_LDS_COLUMNS - basis.nshell * (2 if gradient else 1)
+    return max(0, min(MAX_GRAD_SETS, left // (4 if gradient else 1)))
+
+
+def density_into(basis, coords_bohr, points_bohr, dm, gradient=False):
+    """``density_batch`` for device tensors in atomic units (geometries [G, natm, 3] and points [G, M, 3] in Bohr, ``dm``
+    [G, K, N, N]), on the current stream -> ``rho`` [G, K, M], or ``(rho, drho [G, K, M, 3])`` with ``gradient``.  The
+    entry has no work buffer.  Where the table has so many shells that the kernel's LDS holds fewer than K sets
+    (``density_max_sets``), the sets go in several launches: a set has the same bits whatever the other sets of its
+    launch."""
+    N = basis.nao
+    G, M, K, xyz, pts, dm = _points_call(basis, coords_bohr, points_bohr, dm, "dm", (N, N))
+    dev = xyz.device
+    step = density_max_sets(basis, gradient) or K            # (0: one call, which the library refuses with its message)
+    rhos, grads = [], []
+    for a in range(0, K, step):
+        k = min(step, K - a)
+        d = dm if k == K else dm[:, a:a + k].contiguous()
+        rho = torch.empty((G, k, M), dtype=F64, device=dev)
+        drho = torch.empty((G, k, M, 3), dtype=F64, device=dev) if gradient else None
+        if G > 0:
+            check(_lib.load().oovqe_gto_density_batch(
+                *_head(basis, dev)[:-1], G, dptr(xyz), N, k, dptr(d), M, dptr(pts), dptr(rho), dptr(drho), stream_ptr()),
+                "oovqe_gto_density_batch")
+        rhos.append(rho)
+        grads.append(drho)
+    rho = rhos[0] if len(rhos) == 1 else torch.cat(rhos, dim=1)
+    if not gradient:
+        return rho
+    return rho, (grads[0] if len(grads) == 1 else torch.cat(grads, dim=1))
+
+
+def orbital_values_into(basis, coords_bohr, points_bohr, C, gradient=False):
+    """``orbital_values_batch`` for device tensors in atomic units (points [G, M, 3] in Bohr, ``C`` [G, N, ncol]), on the
+    current stream -> ``psi`` [G, ncol, M], or ``(psi, dpsi [G, ncol, M, 3])`` with ``gradient``."""
+    N = basis.nao
+    G, M, K, xyz, pts, C = _points_call(basis, coords_bohr, points_bohr, C, "C", (N,))
+    dev = xyz.device
+    psi = torch.empty((G, K, M), dtype=F64, device=dev)
+    dpsi = torch.empty((G, K, M, 3), dtype=F64, device=dev) if gradient else None
+    if G > 0:
+        check(_lib.load().oovqe_gto_orbital_values_batch(
+            *_head(basis, dev)[:-1], G, dptr(xyz), N, K, dptr(C), M, dptr(pts), dptr(psi), dptr(dpsi), stream_ptr()),
+            "oovqe_gto_orbital_values_batch")
+    return (psi, dpsi) if gradient else psi
+
+
+def density_batch(basis, coords, points, dm, gradient=False):
+    """The electron density (and its gradient) at M points, for G geometries and K densities per geometry on the device
+    (``oovqe_gto_density_batch``, csrc/gto_density.hip):
+
+        rho[g, k, m]     = sum_{mu nu} dm[g, k, mu, nu] chi_mu(r_m) chi_nu(r_m)
+        drho[g, k, m, :] = d rho[g, k, m] / d r_m
+
+    over the functions of ``integrals_batch`` (s, p and d shells, both d forms).
+
+    Args:
+        basis: GTOBasis
+        coords: geometries in the forms ``integrals_batch`` takes (Angstrom)
+        points: [M, 3] shared by all geometries, or [G, M, 3], in Angstrom, 1 <= M <= ``MAX_POINTS``; a point may lie
+            anywhere (ON a nucleus the values are finite and exact; far outside they are exact zeros)
+        dm: [G, N, N] or [G, K, N, N] device tensor, K = 1 .. ``MAX_GRAD_SETS``; NOT taken as symmetric: both (mu, nu)
+            and (nu, mu) are read and only the symmetric part matters, so transition densities go in as they are
+        gradient: also return drho
+
+    Returns ``rho`` [G, K, M] in e / Bohr^3, or ``(rho, drho)`` with drho [G, K, M, 3] in e / Bohr^4, on the device; the K
+    axis is dropped for a 3-d ``dm``.  A (geometry, set, point) has the same bits wherever it stands in the stack,
+    whatever the other points and sets, and with or without the gradient (``gaussian.density_from_table`` is the host
+    twin)."""
+    xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
+    G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
+    N = basis.nao
+    r = points_host(points, G)
+    if not isinstance(dm, torch.Tensor) or dm.dim() not in (3, 4):
+        raise ValueError(f"dm has shape {tuple(getattr(dm, 'shape', ()))}, expected [{G}, {N}, {N}] or [{G}, K, {N}, {N}]")
+    squeeze = dm.dim() == 3
+    d4 = dm[:, None] if squeeze else dm
+    K = int(d4.shape[1])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} density sets per geometry (1 .. {MAX_GRAD_SETS})")
+    _check_shape("dm", d4, (G, K, N, N))
+    if not bool(torch.isfinite(d4).all()):
+        raise ValueError("the densities must be finite")
+    device = _lib.require_device()
+    out = density_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(r).to(device), d4, gradient)
+    if not squeeze:
+        return out
+    return (out[0][:, 0], out[1][:, 0]) if gradient else out[:, 0]
+
+
+def orbital_values_batch(basis, coords, points, C, gradient=False):
+    """The values (and gradients) of orbitals at M points, for G geometries on the device
+    (``oovqe_gto_orbital_values_batch``, csrc/gto_density.hip): ``psi[g, i, m] = sum_mu C[g, mu, i] chi_mu(r_m)``.
+
+    Args:
+        basis, coords, points: as for ``density_batch``
+        C: [G, N, ncol] device tensor of coefficient columns (AO x orbital, as ``mo_coeff``), ncol = 1 ..
+            ``MAX_GRAD_SETS``
+        gradient: also return dpsi = d psi / d r_m
+
+    Returns ``psi`` [G, ncol, M] in Bohr^-3/2, or ``(psi, dpsi [G, ncol, M, 3])``, on the device, with the guarantees of
+    ``density_batch`` (``gaussian.orbital_values_from_table`` is the host twin)."""
+    xyz = basis.coordinates(coords) if not (isinstance(coords, torch.Tensor) and coords.is_cuda) else coords
+    G = int(xyz.shape[0]) if xyz.ndim == 3 else 1
+    N = basis.nao
+    r = points_host(points, G)
+    if not isinstance(C, torch.Tensor) or C.dim() != 3:
+        raise ValueError(f"C has shape {tuple(getattr(C, 'shape', ()))}, expected [{G}, {N}, ncol]")
+    K = int(C.shape[2])
+    if not 1 <= K <= MAX_GRAD_SETS:
+        raise ValueError(f"{K} coefficient columns per geometry (1 .. {MAX_GRAD_SETS})")
+    _check_shape("C", C, (G, N, K))
+    if not bool(torch.isfinite(C).all()):
+        raise ValueError("the coefficients must be finite")
+    device = _lib.require_device()
+    return orbital_values_into(basis, coords_to_device(basis, xyz, device), torch.as_tensor(r).to(device), C, gradient)
+
+
 def sym_invsqrt_batch(S, out=None):
     """``S^-1/2`` (symmetric principal root) of a stack [G, n, n] of symmetric positive definite device matrices ->
     (X [G, n, n], info [G] int32 on the device: 0, or -1 where S has an eigenvalue below ``INVSQRT_MIN_EIG`` -- that

@@ -102,6 +102,60 @@ def traceless_quadrupole(second):
     return 1.5 * second - 0.5 * trace[..., None, None] * eye
 
 
+# ---- uniform grids for densities and orbitals (host only; the values come from gto.density_batch and the batch methods) ----
+def cube_grid(coords, spacing, margin):
+    """A uniform grid around a molecule -> (origin [3] in Angstrom, shape (nx, ny, nz), points [nx ny nz, 3] in Angstrom, x
+    the slowest and z the fastest index, as a cube file lists them).  ``coords`` [natm, 3], ``spacing`` and ``margin``
+    (the least distance from an atom to the faces of the box) are in Angstrom.  At most ``gto.MAX_POINTS`` points go into
+    one call of the device functions: cut ``points`` into slabs."""
+    import numpy as np
+    R = np.asarray(coords, dtype=float).reshape(-1, 3)
+    h, margin = float(spacing), float(margin)
+    if not (h > 0.0 and margin >= 0.0 and np.isfinite(R).all()):
+        raise ValueError(f"spacing = {spacing!r} (> 0), margin = {margin!r} (>= 0), finite coordinates")
+    lo, hi = R.min(axis=0) - margin, R.max(axis=0) + margin
+    shape = tuple(int(n) for n in np.ceil((hi - lo) / h - 1e-9).astype(int) + 1)
+    origin = 0.5 * (lo + hi) - 0.5 * h * (np.asarray(shape) - 1)
+    axes = [origin[d] + h * np.arange(shape[d]) for d in range(3)]
+    points = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    return origin, shape, points
+
+
+def integrate_grid(values, spacing):
+    """``sum_m values[..., m] h^3`` with h = ``spacing`` (Angstrom, as ``cube_grid`` takes it) in Bohr: the integral of
+    values in atomic units (e / Bohr^3 -> e) over a uniform grid, along the last axis (tensor or array; with a trailing
+    component axis, as a gradient has, move the points last first)."""
+    h = float(spacing) / gto.BOHR
+    return values.sum(-1) * h ** 3
+
+
+def write_cube(path, symbols, coords, origin, shape, spacing, values, comment="auto_oo_amd"):
+    """A Gaussian cube file of ``values`` [nx ny nz] (or [nx, ny, nz]; atomic units, tensor or array) on the grid of
+    ``cube_grid``: ``coords`` [natm, 3], ``origin`` and ``spacing`` in Angstrom (the file holds Bohr)."""
+    import numpy as np
+    v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+    v = np.asarray(v, dtype=float)
+    nx, ny, nz = (int(n) for n in shape)
+    if v.size != nx * ny * nz:
+        raise ValueError(f"{v.size} values for a grid of {nx} x {ny} x {nz} points")
+    R = np.asarray(coords, dtype=float).reshape(-1, 3) / gto.BOHR
+    if len(symbols) != R.shape[0]:
+        raise ValueError(f"{len(symbols)} symbols for {R.shape[0]} atoms")
+    o, h = np.asarray(origin, dtype=float).reshape(3) / gto.BOHR, float(spacing) / gto.BOHR
+    with open(path, "w") as fh:
+        fh.write(f"{comment}\nx slowest, z fastest; atomic units\n")
+        fh.write(f"{R.shape[0]:5d}{o[0]:12.6f}{o[1]:12.6f}{o[2]:12.6f}\n")
+        for d, n in enumerate((nx, ny, nz)):
+            step = [h if k == d else 0.0 for k in range(3)]
+            fh.write(f"{n:5d}{step[0]:12.6f}{step[1]:12.6f}{step[2]:12.6f}\n")
+        for sym, xyz in zip(symbols, R):
+            z = gto._Z[str(sym).capitalize()]
+            fh.write(f"{z:5d}{float(z):12.6f}{xyz[0]:12.6f}{xyz[1]:12.6f}{xyz[2]:12.6f}\n")
+        for row in v.reshape(nx * ny, nz):
+            for k in range(0, nz, 6):
+                fh.write("".join(f"{x:13.5E}" for x in row[k:k + 6]) + "\n")
+
+
 def fit_esp_charges(phi, points_bohr, coords_bohr, total_charge=0.0):
     """Atomic charges fitted to an electrostatic potential: the ``q`` [..., natm] that minimise
     ``sum_m (phi[..., m] - sum_A q_A / |r_m - R_A|)^2`` under ``sum_A q_A = total_charge`` (a Lagrange constraint), batched

@@ -818,6 +818,32 @@ int oovqe_gto_potential_batch(int nshell, const int32_t* shells, int nprim_total
                               const double* coefs, int natm, const double* charges, int batch, const double* coords,
                               int nao, int nset, const double* dm, int npoint, const double* points, unsigned nuc_mask,
                               double* phi, double* field, double* work, oovqe_stream_t stream);
+/* Electron density, its gradient and orbital values at arbitrary points (csrc/gto_density.hip): every geometry has its
+ * own npoint points [batch][npoint][3] (Bohr), 1 <= npoint <= 65535, batch <= 65535; the basis tables, AO order and
+ * normalisation are those of oovqe_gto_integrals_batch (s, p, d shells, both d forms; no charges are needed).
+ *   rho[g][k][m]     = sum dm[g][k][mu][nu] chi_mu(r_m) chi_nu(r_m)      dm [batch][nset][nao][nao], NOT taken as symmetric:
+ *                      both (mu, nu) and (nu, mu) are read;  1 <= nset <= OOVQE_GTO_GRAD_MAX_SETS
+ *   drho[g][k][m][:] = d rho[g][k][m] / d r_m                             (null: not computed)
+ *   psi[g][i][m]     = sum_mu cmat[g][mu][i] chi_mu(r_m)                  cmat [batch][nao][ncol], 1 <= ncol <=
+ *                      OOVQE_GTO_GRAD_MAX_SETS
+ *   dpsi[g][i][m][:] = d psi[g][i][m] / d r_m                             (null: not computed)
+ * in e / Bohr^3, e / Bohr^4, Bohr^-3/2, Bohr^-5/2.  A point may lie anywhere: ON a nucleus the values are finite and
+ * exact, and where every exponential has underflowed they are exact zeros (a coordinate beyond +-1e75 Bohr is taken as
+ * +-1e75).  points and coords are taken as finite.  No floating-point atomics, fixed orders of summation: a (geometry,
+ * set or column, point) has the same bits wherever it stands in the stack, whatever the other points and sets, their
+ * number and order, on any stream, with or without the gradient.  Neither entry has a work buffer (a Gaussian at a point
+ * needs no pair data), so there is no *_work_size; both read the shell table back (one stream synchronisation).  The
+ * density kernel keeps the radial sums of every shell in LDS: (nset + nshell) * 512 bytes, four and two times that with
+ * the gradient, plus 3392 must fit 65536 bytes (40 shells with 10 sets and the gradient, 111 shells with 10 sets
+ * without; one set: 58 and 120 shells.  A set has the same bits in any call, so a caller cuts the sets into several calls:
+ * gto.density_into does).  Anything out of scope returns a negative code before any launch (oovqe_last_error gives the text). */
+int oovqe_gto_density_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps, const double* coefs,
+                            int natm, int batch, const double* coords, int nao, int nset, const double* dm, int npoint,
+                            const double* points, double* rho, double* drho, oovqe_stream_t stream);
+int oovqe_gto_orbital_values_batch(int nshell, const int32_t* shells, int nprim_total, const double* exps,
+                                   const double* coefs, int natm, int batch, const double* coords, int nao, int ncol,
+                                   const double* cmat, int npoint, const double* points, double* psi, double* dpsi,
+                                   oovqe_stream_t stream);
 /* AO densities of a CAS wave function for the calls above, from mo_coeff [batch][n][n] (AO x MO), the first n_core
  * orbitals doubly occupied, the next ncas active with the spin-free RDMs gamma [batch][a][a], Gamma [batch][a]^4 in the
  * convention of oovqe_cas_eval (E = c0 + c1 . gamma + c2 . Gamma, c2 = g / 2):
