@@ -26,6 +26,7 @@ from auto_oo_amd import _lib, gaussian, gto, scf            # noqa: E402
 from auto_oo_amd.gaussian import Moldata_sto3g              # noqa: E402
 from auto_oo_amd.moldata import get_formal_geo              # noqa: E402
 from auto_oo_amd.synthetic import synthetic_problem         # noqa: E402
+from tests._scf_scope import host_rhf_counted               # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, "golden", "notebook_runs.json")) as fh:
@@ -58,55 +59,6 @@ def formal_basis():
 
 def cuda(x):
     return torch.as_tensor(np.array(x, dtype=np.float64)).cuda()
-
-
-def host_rhf_counted(int1e, int2e, overlap, n_occ, conv_tol=1e-12, max_cycle=200):
-    """``gaussian.rhf`` statement for statement, returning the number of Fock builds and the last commutator as well
-    (the host routine does not report them); ``host_solution`` asserts that it gives the bits of ``gaussian.rhf``."""
-    s_val, s_vec = np.linalg.eigh(overlap)
-    X = s_vec @ np.diag(s_val ** -0.5) @ s_vec.T
-
-    def diag(F):
-        e, c = np.linalg.eigh(X.T @ F @ X)
-        return e, X @ c
-    e, C = diag(int1e)
-    D = 2.0 * C[:, :n_occ] @ C[:, :n_occ].T
-    fs, errs = [], []
-    energy, count, last = 0.0, 0, np.inf
-    converged = False
-    for _ in range(max_cycle):
-        count += 1
-        J = np.einsum("pqrs,rs->pq", int2e, D)
-        K = np.einsum("prqs,rs->pq", int2e, D)
-        F = int1e + J - 0.5 * K
-        new_energy = 0.5 * np.sum(D * (int1e + F))
-        err = F @ D @ overlap - overlap @ D @ F
-        last = np.abs(err).max()
-        fs.append(F)
-        errs.append(err)
-        fs, errs = fs[-8:], errs[-8:]
-        if len(fs) > 1:
-            m = len(fs)
-            B = -np.ones((m + 1, m + 1))
-            B[m, m] = 0.0
-            for a_ in range(m):
-                for b_ in range(m):
-                    B[a_, b_] = np.sum(errs[a_] * errs[b_])
-            rhs = np.zeros(m + 1)
-            rhs[m] = -1.0
-            try:
-                w = np.linalg.solve(B, rhs)[:m]
-                F = sum(wi * fi for wi, fi in zip(w, fs))
-            except np.linalg.LinAlgError:
-                pass
-        e, C = diag(F)
-        D = 2.0 * C[:, :n_occ] @ C[:, :n_occ].T
-        if abs(new_energy - energy) < conv_tol and np.abs(err).max() < 1e-9:
-            energy = new_energy
-            converged = True
-            break
-        energy = new_energy
-    return C, e, energy, count, last, converged
 
 
 @functools.lru_cache(maxsize=None)
