@@ -3563,7 +3563,7 @@ static int sym_gm_batched(const double* J, const double* C, double* Gm, int N, i
     memset(&job, 0, sizeof(job));
     if (cj) job = *cj;
     const unsigned nx = nty + (cj ? 1 : 0);
-    const bool xcd_grid = batch > 1 && oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) == 0;
+    const bool xcd_grid = oovqe_xcd_grid(batch, oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) != 0);
     const dim3 grid = xcd_grid ? dim3(nx * (unsigned)((batch + 7) / 8 * 8)) : dim3(nx, batch);
 #define OOVQE_LAUNCH_GM2(KS_, WPE_)                                                               \
     do {                                                                                          \
@@ -4117,73 +4117,100 @@ int oovqe_eval_plan(const EvalShape& s, EvalPlan* plan)
     return 0;
 }
 
-// panel kernel: stage 3 on panels of npan general indices per workgroup, about one resident round of workgroups;
-// Wpre: W = C^T h_ao [G][N][N] from the circuit launch, or null (the kernel then stages h_ao and forms its rows itself)
-static int cas_panel_batched(const CasEvalArgs& a, const EvalPlan& p, const double* Wpre, hipStream_t st)
+// launch geometry of cas_panel_kernel (plan.h)
+bool oovqe_panel_geom(int N, int n_occ, int ncas, int nrdm, int batch, bool w, int panel_rows, PanelGeom* g)
 {
-    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
-    const size_t m3 = (size_t)M * M * M, na2 = (size_t)a.ncas * a.ncas;
+    const int M = n_occ + ncas;
+    const size_t m3 = (size_t)M * M * M, na2 = (size_t)ncas * ncas;
     const size_t set_bytes = (na2 + na2 * na2) * sizeof(double);
     const size_t lds_cap = 160 * 1024;
-    const size_t fixed_bytes = ((size_t)N * M + (Wpre ? 0 : (size_t)N * N)) * sizeof(double);
-    const size_t per_n = (m3 + (Wpre ? 1 : 2) * (size_t)N + 2 * (size_t)M) * sizeof(double);
-    OOVQE_REQUIRE(fixed_bytes + per_n + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS",
-                  N, M, fixed_bytes + per_n + set_bytes);
+    const size_t fixed_bytes = ((size_t)N * M + (w ? 0 : (size_t)N * N)) * sizeof(double);
+    const size_t per_n = (m3 + (w ? 1 : 2) * (size_t)N + 2 * (size_t)M) * sizeof(double);
+    g->lds_bytes = fixed_bytes + per_n + set_bytes;       // (the least; what the caller reports when it does not fit)
+    if (g->lds_bytes > lds_cap) return false;
     long npan = ((long)N * batch + 383) / 384;
     const long npan_max = (long)((lds_cap - fixed_bytes - set_bytes) / per_n);
     if (npan > npan_max) npan = npan_max;
     if (npan > 8) npan = 8;   // (two workgroups per CU: 40 us against 47 us with panels of 16 at 256 geometries)
-    if (Wpre) {
+    if (w) {
         // without h_ao in LDS a panel of this many general indices leaves room for THREE workgroups per CU
         // (N = 43, M = 9: 7 indices, 51 KB; 39 -> 31 us at 256 geometries)
         const long n3 = (long)((lds_cap / 3 - fixed_bytes - set_bytes) / per_n);
         if (n3 >= 4 && n3 < npan) npan = n3;
     }
-    if (oovqe_opt(OOVQE_OPT_PANEL_ROWS) > 0) npan = oovqe_opt(OOVQE_OPT_PANEL_ROWS);   // measurement hook
+    if (panel_rows > 0) npan = panel_rows;   // measurement hook
     if (npan < 1) npan = 1;
     int rdm_chunk = (int)((lds_cap - fixed_bytes - (size_t)npan * per_n) / set_bytes);
-    if (rdm_chunk > a.nrdm) rdm_chunk = a.nrdm;
-    const size_t lds_bytes = fixed_bytes + (size_t)npan * per_n + (size_t)rdm_chunk * set_bytes;
-    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_panel_kernel, lds_cap)) return rc_lds;
+    if (rdm_chunk > nrdm) rdm_chunk = nrdm;
+    g->npan = (int)npan;
+    g->npan_max = (int)npan_max;
+    g->rdm_chunk = rdm_chunk;
+    g->lds_bytes = fixed_bytes + (size_t)npan * per_n + (size_t)rdm_chunk * set_bytes;
+    return true;
+}
+
+// panel kernel: stage 3 on panels of npan general indices per workgroup, about one resident round of workgroups;
+// Wpre: W = C^T h_ao [G][N][N] from the circuit launch, or null (the kernel then stages h_ao and forms its rows itself)
+static int cas_panel_batched(const CasEvalArgs& a, const EvalPlan& p, const double* Wpre, hipStream_t st)
+{
+    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
+    PanelGeom pg;
+    const bool fits = oovqe_panel_geom(N, a.n_occ, a.ncas, a.nrdm, batch, Wpre != nullptr, oovqe_opt(OOVQE_OPT_PANEL_ROWS), &pg);
+    OOVQE_REQUIRE(fits, "cas_eval: N=%d M=%d needs %zu B of LDS", N, M, pg.lds_bytes);
+    const int npan = pg.npan;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_panel_kernel, 160 * 1024)) return rc_lds;
     oovqe_profile_mark_start_l(st, LABEL_COLUMN);
     const unsigned npanels = (unsigned)((N + npan - 1) / npan);
-    const bool xcd_grid = batch > 1 && oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) == 0;
+    const bool xcd_grid = oovqe_xcd_grid(batch, oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) != 0);
     hipLaunchKernelGGL(cas_panel_kernel,
                        xcd_grid ? dim3(npanels * (unsigned)((batch + 7) / 8 * 8)) : dim3(npanels, batch),
-                       dim3(PAN_THREADS), lds_bytes, st, a.work + p.off[WB_GMW], a.h_ao, a.C, a.gamma, a.Gamma, a.nrdm,
-                       N, a.n_occ, a.ncas, (int)npan, a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART],
-                       a.work + p.off[WB_CPART], a.out.c1, a.out.c2, a.Gm, a.hmo, a.out_stride, rdm_chunk,
+                       dim3(PAN_THREADS), pg.lds_bytes, st, a.work + p.off[WB_GMW], a.h_ao, a.C, a.gamma, a.Gamma, a.nrdm,
+                       N, a.n_occ, a.ncas, npan, a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART],
+                       a.work + p.off[WB_CPART], a.out.c1, a.out.c2, a.Gm, a.hmo, a.out_stride, pg.rdm_chunk,
                        xcd_grid ? batch : 0, Wpre);
     oovqe_profile_mark_stop(st);
     OOVQE_CHECK_LAUNCH("cas_eval/panel");
     return 0;
 }
 
-// column kernel: q -> x and stage 3 per general index on U = C^T T2
-static int cas_column_batched(const CasEvalArgs& a, const EvalPlan& p, hipStream_t st)
+// launch geometry of cas_column_kernel (plan.h)
+bool oovqe_column_geom(int N, int n_occ, int ncas, int nrdm, int batch, int n_cu, ColumnGeom* g)
 {
-    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
-    const size_t na2 = (size_t)a.ncas * a.ncas;
+    const size_t na2 = (size_t)ncas * ncas;
     const size_t set_bytes = (na2 + na2 * na2) * sizeof(double);
     const size_t lds_cap = 160 * 1024;
-    const size_t base_bytes = column_base_bytes(N, M);
-    OOVQE_REQUIRE(base_bytes + set_bytes <= lds_cap, "cas_eval: N=%d M=%d needs %zu B of LDS", N, M,
-                  base_bytes + set_bytes);
+    const size_t base_bytes = column_base_bytes(N, n_occ + ncas);
+    g->lds_bytes = base_bytes + set_bytes;
+    if (g->lds_bytes > lds_cap) return false;
     int rdm_chunk = (int)((lds_cap - base_bytes) / set_bytes);
-    if (rdm_chunk > a.nrdm) rdm_chunk = a.nrdm;
-    const size_t lds_bytes = base_bytes + (size_t)rdm_chunk * set_bytes;
-    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_column_kernel, lds_cap)) return rc_lds;
-    oovqe_profile_mark_start_l(st, LABEL_COLUMN);
+    if (rdm_chunk > nrdm) rdm_chunk = nrdm;
     // many large RDM sets (a derivative evaluation of a big active space): their chunks are dealt to
     // zsplit workgroups per n, about one resident round of workgroups in all
     int zsplit = 1;
-    if (a.ncas * a.ncas * a.ncas >= 128 && rdm_chunk > 0) {
-        const int nchunks = (a.nrdm + rdm_chunk - 1) / rdm_chunk;
-        zsplit = (int)((long)oovqe_cu_count() * 2 / ((long)N * batch));
+    if (ncas * ncas * ncas >= 128 && rdm_chunk > 0) {
+        const int nchunks = (nrdm + rdm_chunk - 1) / rdm_chunk;
+        zsplit = (int)((long)n_cu * 2 / ((long)N * batch));
         if (zsplit > nchunks) zsplit = nchunks;
         if (zsplit > 64) zsplit = 64;
         if (zsplit < 1) zsplit = 1;
     }
+    g->rdm_chunk = rdm_chunk;
+    g->zsplit = zsplit;
+    g->lds_bytes = base_bytes + (size_t)rdm_chunk * set_bytes;
+    return true;
+}
+
+// column kernel: q -> x and stage 3 per general index on U = C^T T2
+static int cas_column_batched(const CasEvalArgs& a, const EvalPlan& p, hipStream_t st)
+{
+    const int N = a.N, M = a.n_occ + a.ncas, batch = a.batch;
+    ColumnGeom cg;
+    const bool fits = oovqe_column_geom(N, a.n_occ, a.ncas, a.nrdm, batch, oovqe_cu_count(), &cg);
+    OOVQE_REQUIRE(fits, "cas_eval: N=%d M=%d needs %zu B of LDS", N, M, cg.lds_bytes);
+    const int rdm_chunk = cg.rdm_chunk, zsplit = cg.zsplit;
+    const size_t lds_bytes = cg.lds_bytes;
+    if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)cas_column_kernel, 160 * 1024)) return rc_lds;
+    oovqe_profile_mark_start_l(st, LABEL_COLUMN);
     hipLaunchKernelGGL(cas_column_kernel, dim3(N, batch, zsplit), dim3(COL_THREADS), lds_bytes, st,
                        a.work + p.off[WB_U], a.h_ao, a.C, a.gamma, a.Gamma, a.nrdm, N, a.n_occ, a.ncas,
                        a.work + p.off[WB_FCOL], a.work + p.off[WB_EPART], a.work + p.off[WB_CPART], a.out.c1, a.out.c2,
@@ -4247,8 +4274,9 @@ static int cas_eval_staged(const CasEvalArgs& a, const EvalPlan& p)
 // Launches the evaluation the plan describes (same shape, flags and buffers the plan was made for).
 static int cas_eval_batched(const CasEvalArgs& a, const EvalPlan& p)
 {
+    // (no orbital rotation, n_kappa == 0 -- one orbital, all of it active: the gradient vector has no element)
     OOVQE_REQUIRE(a.g_ao && a.h_ao && a.C && a.gamma && a.Gamma && a.work && a.out.c0 && a.out.c1 && a.out.c2 &&
-                  a.out.E && a.out.gvec, "cas_eval: null pointer");
+                  a.out.E && (a.out.gvec || a.n_kappa == 0), "cas_eval: null pointer");
     OOVQE_REQUIRE(a.n_kappa == 0 || (a.kap_row && a.kap_col), "cas_eval: null index table");
     OOVQE_REQUIRE(a.nrdm == 1 || a.out.dE, "cas_eval: dE required when nrdm > 1");
     OOVQE_REQUIRE((p.circuit == CIRCUIT_RIDES) == (a.cj != nullptr), "cas_eval: circuit job and plan disagree");
@@ -4532,7 +4560,7 @@ extern "C" const char* oovqe_oo_eval_plan_describe(int n_theta, int n_gates, int
                                                    int ncas, int n_kappa, int derivatives, int batch,
                                                    unsigned eri_flags, int have_packed)
 {
-    static thread_local char line[512];
+    static thread_local char line[1024];
     static const char* const path_names[] = {"packed_tail", "packed_split", "packed_two_step", "fused", "column", "staged"};
     static const char* const circuit_names[] = {"none", "rides", "own"};
     static const char* const block_names[WB_COUNT] = {"Jp", "T3", "Gmw", "Cdup", "T2", "U", "Fcol", "Epart", "Cpart"};
@@ -4568,6 +4596,23 @@ extern "C" const char* oovqe_oo_eval_plan_describe(int n_theta, int n_gates, int
         if (stage1_variant(N, &v)) return nullptr;
         add("; tail=cas_tail_kernel<%d>; tail_lds=%zu", tail_depth(N, v), p.tail_lds);
     }
+    // what the launch code of the path decides below the plan (plan.h: PanelGeom, ColumnGeom, FusedPlan)
+    if (p.path == PATH_FUSED)
+        add("; nchunk=%d; qc=%d; nbuf=%d; wpg=%d", p.fused.nchunk, p.fused.qc, p.fused.nbuf, p.fused.wpg);
+    if (p.path == PATH_PACKED_SPLIT || p.path == PATH_PACKED_TWO_STEP || p.path == PATH_FUSED) {
+        PanelGeom pg;
+        const bool panel_w = p.w && p.path == PATH_PACKED_SPLIT;
+        // (npan = 0: the panel does not fit LDS at this shape, the launch will say so)
+        if (!oovqe_panel_geom(N, n_occ, ncas, s.nrdm, batch, panel_w, oovqe_opt(OOVQE_OPT_PANEL_ROWS), &pg)) pg = PanelGeom{};
+        add("; npan=%d; npan_max=%d; rdm_chunk=%d; panel_w=%d; xcd_grid=%d", pg.npan, pg.npan_max, pg.rdm_chunk,
+            panel_w ? 1 : 0, oovqe_xcd_grid(batch, oovqe_opt(OOVQE_OPT_GM_PLAIN_GRID) != 0) ? 1 : 0);
+    }
+    if (p.path == PATH_COLUMN) {
+        ColumnGeom cg;
+        if (!oovqe_column_geom(N, n_occ, ncas, s.nrdm, batch, s.n_cu, &cg)) cg = ColumnGeom{};
+        add("; rdm_chunk=%d; zsplit=%d", cg.rdm_chunk, cg.zsplit);
+    }
+    if (p.path == PATH_STAGED) add("; staged_rows=%d", p.staged_rows ? 1 : 0);
     return line;
 }
 

@@ -89,3 +89,22 @@ struct EvalPlan {
 
 // 0, or OOVQE_ERR_ARG with the error set (a shape no kernel serves)
 int oovqe_eval_plan(const EvalShape& s, EvalPlan* plan);
+
+// What the launch code of a path decides below the plan, as plain arithmetic on the shape, the option values and the
+// CU count (cas.hip: the launch functions call these, oovqe_oo_eval_plan_describe reports them).
+// cas_panel_kernel: general indices per workgroup, the LDS limit of that number, RDM sets per LDS chunk
+struct PanelGeom {
+    int npan, npan_max, rdm_chunk;
+    size_t lds_bytes;
+};
+// cas_column_kernel: RDM sets per LDS chunk, workgroups per general index that share the chunks
+struct ColumnGeom {
+    int rdm_chunk, zsplit;
+    size_t lds_bytes;
+};
+// w: the kernel reads the ready-made W = C^T h_ao; panel_rows: option panel_rows (0: chosen here).  false: no room in LDS
+bool oovqe_panel_geom(int N, int n_occ, int ncas, int nrdm, int batch, bool w, int panel_rows, PanelGeom* g);
+bool oovqe_column_geom(int N, int n_occ, int ncas, int nrdm, int batch, int n_cu, ColumnGeom* g);
+// the 1-D grid that keeps the workgroups of a geometry on one XCD (sym_gm_kernel, cas_panel_kernel): the batch rounded
+// up to a multiple of 8; plain_grid: option gm_plain_grid
+inline bool oovqe_xcd_grid(int batch, bool plain_grid) { return batch > 1 && !plain_grid; }

@@ -43,7 +43,10 @@ def eval_plan(N, n_occ, ncas, n_kappa, batch, eri_flags, have_packed, n_theta=0,
     dict: path, stage1, circuit, w (bool), launches (int), k1_hosts (bool: the K1 launch of the path, if it makes one, can
     host circuit workgroups), labels {PROFILE_LABELS name: bracketed launches},
     blocks {name: (offset, doubles)}; on the packed_tail path also tail (the build of cas_tail_kernel) and tail_lds
-    (its LDS bytes), both as strings.  ``circuit=False``: the evaluation from given RDM sets."""
+    (its LDS bytes), both as strings; and, as strings too, what the launch code of the path picks from the shape
+    (include/oovqe.h): nchunk, qc, nbuf, wpg (fused); npan, npan_max, rdm_chunk, panel_w, xcd_grid (the paths with the
+    panel kernel); rdm_chunk, zsplit (column); staged_rows (staged).  ``circuit=False``: the evaluation from given RDM
+    sets."""
     lib = _lib.load()
     line = lib.oovqe_oo_eval_plan_describe(n_theta, n_gates, 2 * ncas if circuit else 0, N, n_occ, ncas, n_kappa,
                                            int(bool(derivatives)), batch, eri_flags, int(bool(have_packed)))

@@ -50,7 +50,12 @@ const char* oovqe_last_stage1_kernel(void);
  *    oovqe_last_stage1_kernel reports it>; circuit=<none|rides|own>; w=<0|1>; launches=<kernel launches>;
  *    k1_hosts=<0|1: the batched contraction launch of the path, if it makes one, can host circuit workgroups>;
  *    labels=<bracketed launches by profile label, comma separated>; blocks=<name>@<offset>+<doubles>,..."
- *   and, on the packed_tail path only, "; tail=cas_tail_kernel<k-depth>; tail_lds=<LDS bytes of its workgroup>"
+ *   and, on the packed_tail path only, "; tail=cas_tail_kernel<k-depth>; tail_lds=<LDS bytes of its workgroup>";
+ *   then what the launch code of the path picks from the shape: fused "; nchunk=; qc=; nbuf=; wpg=" (q chunks, slots
+ *   per chunk, LDS ring blocks, workgroups per geometry); packed_split, packed_two_step and fused "; npan=;
+ *   npan_max=; rdm_chunk=; panel_w=<0|1>; xcd_grid=<0|1>" (general indices per panel workgroup and their LDS limit,
+ *   RDM sets per LDS chunk, the panel kernel reads W, the 1-D grid over the batch rounded up to 8; npan = 0: the panel
+ *   does not fit LDS); column "; rdm_chunk=; zsplit=" (workgroups per general index); staged "; staged_rows=<0|1>"
  * for an oovqe_oo_eval_batch call of this shape (n_qubits == 0: an oovqe_cas_eval_batch call with
  * nrdm = derivatives ? 1 + n_theta : 1) under the debug options set now and the CU count of the current device
  * (256 without one).  w: the circuit's own launch leaves W = C^T h_ao for the Fock stage; blocks: the parts of the
