@@ -71,6 +71,12 @@ SIGNATURES = {
     "oovqe_mode_contract": (ctypes.c_int, [c_double_p, c_double_p, c_double_p, ctypes.c_int64,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                            ctypes.c_int, c_stream]),
+    "oovqe_mode_contract_batch": (ctypes.c_int, [c_double_p, c_double_p, c_double_p, ctypes.c_int64,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_int64, c_stream]),
+    "oovqe_mode_contract_plan_describe": (ctypes.c_char_p, [ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.c_int64] * 2),
     "oovqe_expm_skew": (ctypes.c_int, [c_double_p, c_int32_p, c_int32_p, ctypes.c_int, ctypes.c_int,
                                        c_double_p, c_double_p, c_double_p, c_stream]),
     "oovqe_expm": (ctypes.c_int, [c_double_p, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,

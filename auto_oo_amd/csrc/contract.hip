@@ -521,6 +521,15 @@ bool step_offsets_fit(int ks, long B)
     return (double)rows * (double)B * 8.0 + 128.0 < 4294967296.0;
 }
 
+// persistent grid: at most ~2 workgroups per CU in total, each walks many item groups
+long contract_grid_x(long n_items, int ngroups, int batch)
+{
+    const long ngroups_items = (n_items + NWAVES - 1) / NWAVES;
+    long per_slice = 512 / ((long)ngroups * batch);
+    if (per_slice < 1) per_slice = 1;
+    return ngroups_items < per_slice ? ngroups_items : per_slice;
+}
+
 template <int NT, bool LAST, int KS, bool WIDE = false>
 int launch_nt(const double* T, const double* Cm, double* out, long A, int K, int J, long B,
               int ldc, int ngroups, long n_items, int nbt, int batch, long t_bs, long c_bs, long o_bs,
@@ -528,14 +537,10 @@ int launch_nt(const double* T, const double* Cm, double* out, long A, int K, int
 {
     constexpr int LDJ = 16 * (NT | 1);
     constexpr int KC = 4 * KS;
-    constexpr int NW = NWAVES, NTH = NTHREADS;
+    constexpr int NTH = NTHREADS;
     constexpr int CREG = (KC * LDJ + NTH - 1) / NTH;
     size_t lds_bytes = (size_t)2 * CREG * NTH * sizeof(double);
-    // persistent grid: at most ~2 workgroups per CU in total, each walks many item groups
-    const long ngroups_items = (n_items + NW - 1) / NW;
-    long per_slice = 512 / ((long)ngroups * batch);
-    if (per_slice < 1) per_slice = 1;
-    const long nblocks = ngroups_items < per_slice ? ngroups_items : per_slice;
+    const long nblocks = contract_grid_x(n_items, ngroups, batch);
     OOVQE_REQUIRE(WIDE || LAST || step_offsets_fit(KS, B), "mode_contract: stride too long for this kernel");
     if constexpr (KS == 12) {
         if (cj) {
@@ -691,6 +696,18 @@ static ContractPlan contract_plan(long A, int K, int J, long B, int last, int ba
     return p;
 }
 
+// what a contraction's shape has to satisfy, whatever its pointers
+static int contract_check_shape(long A, int K, int J, long B, int ldc, int last, int batch)
+{
+    OOVQE_REQUIRE(batch >= 1 && batch <= 65535, "mode_contract: batch=%d", batch);
+    OOVQE_REQUIRE((double)A * (double)((B + 15) / 16) < 2.0e9, "mode_contract: too many strips");
+    OOVQE_REQUIRE(A >= 1 && K >= 1 && J >= 1 && B >= 1 && ldc >= J,
+                  "mode_contract: bad dims A=%ld K=%d J=%d B=%ld ldc=%d", A, K, J, B, ldc);
+    OOVQE_REQUIRE(!last || B == 1, "mode_contract: last-mode needs B == 1");
+    OOVQE_REQUIRE(last || (B + 15) / 16 <= 0x7fffffffL, "mode_contract: B too large");
+    return 0;
+}
+
 int oovqe_contract_hosts_circuit(long A, int K, int J, long B, int last, int batch, const ContractOpts& o)
 {
     return contract_plan(A, K, J, B, last, batch, o).family == CONTRACT_SHORT;
@@ -700,13 +717,8 @@ int oovqe_mode_contract_batched(const double* T, const double* Cm, double* out, 
                                 long B, int ldc, int last, int batch, long t_bs, long c_bs, long o_bs,
                                 hipStream_t st, const oovqe_circuit_job_t* cj)
 {
-    OOVQE_REQUIRE(batch >= 1 && batch <= 65535, "mode_contract: batch=%d", batch);
-    OOVQE_REQUIRE((double)A * (double)((B + 15) / 16) < 2.0e9, "mode_contract: too many strips");
     OOVQE_REQUIRE(T && Cm && out, "mode_contract: null pointer");
-    OOVQE_REQUIRE(A >= 1 && K >= 1 && J >= 1 && B >= 1 && ldc >= J,
-                  "mode_contract: bad dims A=%ld K=%d J=%d B=%ld ldc=%d", A, K, J, B, ldc);
-    OOVQE_REQUIRE(!last || B == 1, "mode_contract: last-mode needs B == 1");
-    OOVQE_REQUIRE(last || (B + 15) / 16 <= 0x7fffffffL, "mode_contract: B too large");
+    if (int rc = contract_check_shape(A, K, J, B, ldc, last, batch)) return rc;
     const ContractPlan p = contract_plan(A, K, J, B, last, batch, oovqe_contract_opts(), T, out, t_bs, o_bs);
     OOVQE_REQUIRE(p.ngroups <= 65535, "mode_contract: J too large");
     OOVQE_REQUIRE(!cj || p.family == CONTRACT_SHORT, "mode_contract: this shape cannot host circuit workgroups");
@@ -740,6 +752,49 @@ extern "C" int oovqe_mode_contract(const double* T, const double* Cm, double* ou
 {
     return oovqe_mode_contract_impl(T, Cm, out, (long)A, K, J, (long)B, ldc, last,
                                     (hipStream_t)stream);
+}
+
+extern "C" int oovqe_mode_contract_batch(const double* T, const double* Cm, double* out, int64_t A, int K, int J,
+                                         int64_t B, int ldc, int last, int batch, int64_t t_bs, int64_t c_bs,
+                                         int64_t o_bs, oovqe_stream_t stream)
+{
+    OOVQE_REQUIRE(T && Cm && out, "mode_contract_batch: null pointer");
+    if (int rc = contract_check_shape((long)A, K, J, (long)B, ldc, last, batch)) return rc;
+    // a stride is 0 (every element reads the same T / Cm) or clears its tensor; results never share memory
+    const long t_len = (long)A * K * (long)B, c_len = (long)(K - 1) * ldc + J, o_len = (long)A * J * (long)B;
+    OOVQE_REQUIRE(t_bs == 0 || t_bs >= t_len, "mode_contract_batch: t_bs=%ld, T has %ld doubles", (long)t_bs, t_len);
+    OOVQE_REQUIRE(c_bs == 0 || c_bs >= c_len, "mode_contract_batch: c_bs=%ld, Cm spans %ld doubles", (long)c_bs, c_len);
+    OOVQE_REQUIRE(batch == 1 ? o_bs >= 0 : o_bs >= o_len, "mode_contract_batch: o_bs=%ld, out has %ld doubles",
+                  (long)o_bs, o_len);
+    return oovqe_mode_contract_batched(T, Cm, out, (long)A, K, J, (long)B, ldc, last, batch, (long)t_bs, (long)c_bs,
+                                       (long)o_bs, (hipStream_t)stream);
+}
+
+// The launch that would serve a contraction as one line, without launching anything (include/oovqe.h has the format).
+extern "C" const char* oovqe_mode_contract_plan_describe(int64_t A, int K, int J, int64_t B, int last, int batch,
+                                                         int t_align16, int out_align16, int64_t t_bs, int64_t o_bs)
+{
+    static thread_local char line[256];
+    static const char* const family_names[] = {"short", "pair", "wide", "deep", "shallow"};
+    if (contract_check_shape((long)A, K, J, (long)B, J, last, batch)) return nullptr;
+    // contract_plan looks at the two pointers for their alignment alone
+    const double* T = (const double*)(uintptr_t)(t_align16 ? 16 : 8);
+    const double* out = (const double*)(uintptr_t)(out_align16 ? 16 : 8);
+    const ContractPlan p = contract_plan((long)A, K, J, (long)B, last, batch, oovqe_contract_opts(), T, out,
+                                         (long)t_bs, (long)o_bs);
+    long strips = p.n_items, grid_x;
+    int waves = NWAVES;
+    if (p.family == CONTRACT_PAIR) {
+        waves = oovqe_contract_pair_grid((long)A, (long)B, p.ngroups, batch, &strips, &grid_x);
+    } else {
+        grid_x = contract_grid_x(p.n_items, p.ngroups, batch);
+    }
+    const long groups = (strips + waves - 1) / waves;
+    snprintf(line, sizeof(line),
+             "family=%s; deep=%d; nt=%d; ngroups=%d; nbt=%d; n_items=%ld; strips=%ld; waves=%d; grid_x=%ld; rounds=%ld",
+             family_names[p.family], p.deep ? 1 : 0, p.nt, p.ngroups, p.nbt, p.n_items, strips, waves, grid_x,
+             (groups + grid_x - 1) / grid_x);
+    return line;
 }
 
 extern "C" int oovqe_matmul_nn(const double* A, const double* B, int M, int K, int N, double* out,

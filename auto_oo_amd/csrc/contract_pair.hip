@@ -322,11 +322,8 @@ int launch_pair_nt(const double* T, const double* Cm, double* out, long A, int K
     constexpr int CREG = (KC * LDJ + PTHREADS - 1) / PTHREADS;
     const size_t lds_bytes = (size_t)2 * CREG * PTHREADS * sizeof(double);
     const long nbt = (B + 31) / 32;
-    const long n_items = A * nbt;
-    const long ngroups_items = (n_items + PWAVES - 1) / PWAVES;
-    long per_slice = 256 / ((long)ngroups * batch);   // persistent: one workgroup per CU
-    if (per_slice < 1) per_slice = 1;
-    const long nblocks = ngroups_items < per_slice ? ngroups_items : per_slice;
+    long n_items, nblocks;
+    oovqe_contract_pair_grid(A, B, ngroups, batch, &n_items, &nblocks);
     if (int rc_lds = oovqe_ensure_dynamic_lds((const void*)contract_pair_kernel<NT, KS>, lds_bytes)) return rc_lds;
     hipLaunchKernelGGL((contract_pair_kernel<NT, KS>),
                        dim3((unsigned)nblocks, (unsigned)ngroups, (unsigned)batch), dim3(PTHREADS), lds_bytes, st,
@@ -366,6 +363,17 @@ int oovqe_contract_pair_ok(const double* T, const double* out, long A, long B, i
     if (((B + 31) / 32) * 32 * 100 > ((B + 15) / 16) * 16 * 102) return 0;
     const long n_items = A * ((B + 31) / 32);
     return n_items * ngroups * batch >= 2 * 256 * PWAVES;
+}
+
+// The launch of the two-strip kernel: its 32-wide strips, workgroups in x; returns the waves of a workgroup
+int oovqe_contract_pair_grid(long A, long B, int ngroups, int batch, long* n_items, long* grid_x)
+{
+    *n_items = A * ((B + 31) / 32);
+    const long ngroups_items = (*n_items + PWAVES - 1) / PWAVES;
+    long per_slice = 256 / ((long)ngroups * batch);   // persistent: one workgroup per CU
+    if (per_slice < 1) per_slice = 1;
+    *grid_x = ngroups_items < per_slice ? ngroups_items : per_slice;
+    return PWAVES;
 }
 
 int oovqe_contract_pair_launch(const double* T, const double* Cm, double* out, long A, int K, int J, long B,

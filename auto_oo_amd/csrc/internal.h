@@ -23,6 +23,7 @@ int oovqe_contract_hosts_circuit(long A, int K, int J, long B, int last, int bat
 // ---- contract_pair.hip: two 16-wide strips per wave ------------------------------------------------------
 int oovqe_contract_pair_ok(const double* T, const double* out, long A, long B, int nt, int ngroups, int batch,
                            long t_bs, long o_bs);
+int oovqe_contract_pair_grid(long A, long B, int ngroups, int batch, long* n_items, long* grid_x);
 int oovqe_contract_pair_launch(const double* T, const double* Cm, double* out, long A, int K, int J, long B,
                                int ldc, int nt, int ngroups, int deep, int batch, long t_bs, long c_bs,
                                long o_bs, hipStream_t st);

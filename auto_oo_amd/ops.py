@@ -89,6 +89,34 @@ def mode_contract(T, Cm, A, K, J, B, last, out=None):
     return out
 
 
+def mode_contract_batch(T, Cm, out, A, K, J, B, ldc, last, batch, t_bs, c_bs, o_bs):
+    """``batch`` contractions of one shape in one launch (oovqe_mode_contract_batch): element b reads T + b * t_bs and
+    Cm + b * c_bs and writes out + b * o_bs (strides in doubles).  T, Cm and out are tensors whose first element is
+    element 0's; nothing is allocated or copied here, so views into larger buffers keep their alignment."""
+    lib = _lib.load()
+    _dev(T)
+    check(lib.oovqe_mode_contract_batch(T.data_ptr(), Cm.data_ptr(), out.data_ptr(), A, K, J, B, ldc,
+                                        int(bool(last)), batch, t_bs, c_bs, o_bs, stream_ptr()),
+          "oovqe_mode_contract_batch")
+    return out
+
+
+def contract_plan(A, K, J, B, last, batch=1, t_align16=True, out_align16=True, t_bs=0, o_bs=0):
+    """Which launch serves a contraction of this shape under the debug options set now
+    (oovqe_mode_contract_plan_describe; no device needed), as a dict: family (short / pair / wide / deep / shallow),
+    deep (bool: 20-row K-chunks), and the ints nt, ngroups, nbt, n_items, strips, waves, grid_x, rounds."""
+    lib = _lib.load()
+    line = lib.oovqe_mode_contract_plan_describe(A, K, J, B, int(bool(last)), batch, int(bool(t_align16)),
+                                                 int(bool(out_align16)), t_bs, o_bs)
+    if line is None:
+        raise _lib.OovqeError(lib.oovqe_last_error().decode())
+    plan = dict(field.split("=", 1) for field in line.decode().split("; "))
+    family = plan.pop("family")
+    plan = {k: int(v) for k, v in plan.items()}
+    plan["family"], plan["deep"] = family, plan["deep"] == 1
+    return plan
+
+
 def matmul_nn(A, B):
     """A @ B"""
     lib = _lib.load()

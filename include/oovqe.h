@@ -123,6 +123,24 @@ int oovqe_matmul_nn_batch(const double* A, const double* B, int M, int K, int N,
  *   last != 0: out[a,j]   = sum_k T[a,k] * Cm[k*ldc + j]       T: [A,K],   out: [A,J]        */
 int oovqe_mode_contract(const double* T, const double* Cm, double* out, int64_t A, int K, int J,
                         int64_t B, int ldc, int last, oovqe_stream_t stream);
+/* the same for `batch` (1 .. 65535) independent problems of one shape in one launch: element b reads T + b * t_bs and
+ * Cm + b * c_bs and writes out + b * o_bs (strides in doubles).  t_bs and c_bs are 0 (every element reads the same
+ * tensor) or at least the tensor's length (A*K*B; (K-1)*ldc + J); o_bs is at least A*J*B when batch > 1.  Any other
+ * stride is refused before anything is launched. */
+int oovqe_mode_contract_batch(const double* T, const double* Cm, double* out, int64_t A, int K, int J,
+                              int64_t B, int ldc, int last, int batch, int64_t t_bs, int64_t c_bs, int64_t o_bs,
+                              oovqe_stream_t stream);
+/* Which launch serves a contraction of this shape, as one line, without launching anything (needs no device; a test /
+ * debug aid), under the debug options set now:
+ *   "family=<short|pair|wide|deep|shallow>; deep=<0|1: 20-row K-chunks; the chunk depth of the pair family>;
+ *    nt=<tiles of 16 columns of J per wave>; ngroups=<j-groups: grid y>; nbt=<16-wide strips per row of T>;
+ *    n_items=<16-wide strips>; strips=<strips as launched: 32 wide in the pair family>; waves=<per workgroup>;
+ *    grid_x=<workgroups in x>; rounds=<strip groups the busiest workgroup walks>"
+ * t_align16 / out_align16: T / out is 16-byte aligned (the pair family needs both); t_bs, o_bs: the batch strides of
+ * T and out.  NULL (see oovqe_last_error) for a shape oovqe_mode_contract refuses.  The string belongs to the calling
+ * thread and is overwritten by its next call. */
+const char* oovqe_mode_contract_plan_describe(int64_t A, int K, int J, int64_t B, int last, int batch,
+                                              int t_align16, int out_align16, int64_t t_bs, int64_t o_bs);
 
 /* ---- a3/a5: kappa -> U = expm(-K) ----------------------------------------------------------
  * replaces OO_energy.kappa_vector_to_matrix + vector_to_skew_symmetric + math.expm(-K)

@@ -644,7 +644,9 @@ def test_mode_contract_strides_beyond_32_bit_row_offsets():
 @pytest.mark.parametrize("A,K,J,B", [(1, 49, 16, 4000), (2, 100, 250, 40), (3, 60, 33, 1000), (1, 13, 13, 2197)])
 def test_mode_contract_long_stride_kernels_on_small_shapes(A, K, J, B, lib_options):
     """The long-stride build of K1 (one descriptor per k-step, 64-bit store addresses), forced by
-    option k1_force_wide on shapes whose einsum is cheap: every tile count class, ragged edges."""
+    option k1_force_wide on shapes whose einsum is cheap: ragged edges, several slabs, one and several K-chunks.
+    These four shapes are all small enough for the planning rule to halve them down to one tile per wave (NT = 1);
+    the long-stride builds with NT = 2 .. 13 run in tests/test_contract_scope_gpu.py."""
     lib_options(k1_force_wide=1)
     rng = np.random.default_rng(A * 31 + K)
     T = _rand(rng, A, K, B)
