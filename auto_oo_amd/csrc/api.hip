@@ -92,7 +92,7 @@ static const char* const g_opt_names[OOVQE_OPT_COUNT] = {
     "sym_no_rs", "sym_mirror", "sym_simple", "sym_two_step", "no_ride", "k1_no_pair", "k1_force_wide", "gm_plain_grid",
     "newton_one_wg", "sector_unfused", "hess_vk_pass", "hess_own_stage1", "panel_rows",
     "k1_force_nt", "newton_no_chol", "sector_lambda_w", "sector_rdm_r3", "panel_no_w",
-    "stage1_free_run", "one_stream", "tail_split"};
+    "stage1_free_run", "one_stream", "tail_split", "tail_generic"};
 static_assert(sizeof(g_opt_names) / sizeof(g_opt_names[0]) == OOVQE_OPT_COUNT, "option name table out of step with oovqe_option_t");
 
 int oovqe_opt(int id) { return (id >= 0 && id < OOVQE_OPT_COUNT) ? g_opts[id] : 0; }

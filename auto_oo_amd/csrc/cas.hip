@@ -2890,7 +2890,8 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
                      int na, int NC, double nuc, const double* __restrict__ nuc_arr,
                      const int32_t* __restrict__ kap_row, const int32_t* __restrict__ kap_col, int n_kappa,
                      double* __restrict__ c0, double* __restrict__ E, double* __restrict__ gvec,
-                     double* __restrict__ dE, double* __restrict__ c1, double* __restrict__ c2, size_t out_stride)
+                     double* __restrict__ dE, double* __restrict__ c1, double* __restrict__ c2, size_t out_stride,
+                     int generic)
 {
     extern __shared__ double lds[];
     constexpr int NW = TAIL_THREADS / 64;
@@ -2898,7 +2899,7 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     constexpr int GR = 2, NG = (PW + GR - 1) / GR;   // ... in NG groups of GR rows
     constexpr int NTN = (4 * KS + 15) / 16;          // 16-blocks of n in p -> n
     const int M = no + na, M2 = M * M, M3 = M2 * M;
-    const int na2 = na * na, na3 = na2 * na, na4 = na2 * na2;
+    const int na2 = na * na, na4 = na2 * na2;
     const int ncol = M * (M + 1) / 2, nty = (ncol + 15) / 16;
     const long tri = (long)N * (N + 1) / 2;
     const int by = blockIdx.x;
@@ -3014,27 +3015,73 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
     };
     double bs[2][GR][KS];
     TAIL_MARK(0);
-#pragma unroll
-    for (int s0 = 0; s0 < 2; ++s0) load_group(bs[s0], s0 / NG, s0 % NG);
 
-    // ---- inputs; the position table by a ballot prefix over (x, y <= z) in order ------------------
-    for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
+    // ---- inputs: every global load of the prologue is issued here, into registers, and the first two groups of J
+    // right behind them; the registers go to LDS after the position table, which needs nothing from memory.  One
+    // round trip instead of one per array (a loop "load, then LDS store" waits for its own loads before the next
+    // loop issues, the LDS stores may alias).  The inputs stand in front of J because loads come back in order: the
+    // wait for them then leaves every J load in flight.  Range-checked buffer loads, so that the number of loads in
+    // flight is the same on every path.  SW x 512 >= N^2 for every N the tail serves (N <= 48); what an array has beyond
+    // its registers (large active spaces) is copied by the plain loops below, before the J loads.
+    constexpr int SW = 5, SC = 2, SG1 = 1, SG2 = 2, SK = 3;
+    double wst[SW], cst[SC], g1st[SG1], g2st[SG2];
+    int krst[SK], kcst[SK];
+    {
+        constexpr int DB = (int)sizeof(double), IB = (int)sizeof(int32_t);
+        const __amdgpu_buffer_rsrc_t wsrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(Wpre), 0, N * N * DB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t csrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(C), 0, N * N * DB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t g1srd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(gamma), 0, nrdm * na2 * DB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t g2srd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<double*>(Gamma), 0, nrdm * na4 * DB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t krsrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<int32_t*>(kap_row), 0, n_kappa * IB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t kcsrd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<int32_t*>(kap_col), 0, n_kappa * IB, 0x00020000);
+#pragma unroll
+        for (int u = 0; u < SW; ++u)
+            wst[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(wsrd, (unsigned)((tid + u * TAIL_THREADS) * DB), 0, 0));
+#pragma unroll
+        for (int u = 0; u < SC; ++u) {
+            const int idx = tid + u * TAIL_THREADS;
+            const int q = idx / M, x = idx - q * M;
+            cst[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
+                csrd, idx < N * M ? (unsigned)((q * N + x) * DB) : 0x7fffffffu, 0, 0));
+        }
+#pragma unroll
+        for (int u = 0; u < SG1; ++u)
+            g1st[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(g1srd, (unsigned)((tid + u * TAIL_THREADS) * DB), 0, 0));
+#pragma unroll
+        for (int u = 0; u < SG2; ++u)
+            g2st[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(g2srd, (unsigned)((tid + u * TAIL_THREADS) * DB), 0, 0));
+#pragma unroll
+        for (int u = 0; u < SK; ++u) {
+            krst[u] = __builtin_amdgcn_raw_buffer_load_b32(krsrd, (unsigned)((tid + u * TAIL_THREADS) * IB), 0, 0);
+            kcst[u] = __builtin_amdgcn_raw_buffer_load_b32(kcsrd, (unsigned)((tid + u * TAIL_THREADS) * IB), 0, 0);
+        }
+    }
+    for (int idx = tid + SC * TAIL_THREADS; idx < N * M; idx += TAIL_THREADS) {
         const int q = idx / M, x = idx - q * M;
         Cl[idx] = C[(size_t)q * N + x];
     }
-    for (int idx = tid; idx < N * N; idx += TAIL_THREADS) scr[idx] = Wpre[idx];
-    for (int idx = tid; idx < nrdm * na2; idx += TAIL_THREADS) gml[idx] = gamma[idx];
-    for (int idx = tid; idx < nrdm * na4; idx += TAIL_THREADS) Gml[idx] = Gamma[idx];
-    for (int idx = tid; idx < n_kappa; idx += TAIL_THREADS) {
+    for (int idx = tid + SW * TAIL_THREADS; idx < N * N; idx += TAIL_THREADS) scr[idx] = Wpre[idx];
+    for (int idx = tid + SG1 * TAIL_THREADS; idx < nrdm * na2; idx += TAIL_THREADS) gml[idx] = gamma[idx];
+    for (int idx = tid + SG2 * TAIL_THREADS; idx < nrdm * na4; idx += TAIL_THREADS) Gml[idx] = Gamma[idx];
+    for (int idx = tid + SK * TAIL_THREADS; idx < n_kappa; idx += TAIL_THREADS) {
         krow[idx] = kap_row[idx];
         kcol[idx] = kap_col[idx];
     }
+#pragma unroll
+    for (int s0 = 0; s0 < 2; ++s0) load_group(bs[s0], s0 / NG, s0 % NG);
+
     // the columns of Gc behind the kept ones: p -> n reads those of the last column tile
     for (int idx = tid; idx < 4 * KS * (LDG - NC); idx += TAIL_THREADS) {
         const int p = idx / (LDG - NC);
         Gc[p * LDG + NC + (idx - p * (LDG - NC))] = 0.0;
     }
-    TAIL_MARK(1);
+    // ---- the position table by a ballot prefix over (x, y <= z) in order, while the loads fly -------
     {
         const int total = M * ncol;
         int base = 0;
@@ -3067,6 +3114,27 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
             base += all;
         }
     }
+    TAIL_MARK(1);
+    // the inputs from their registers to LDS
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+        if (tid + u * TAIL_THREADS < N * N) scr[tid + u * TAIL_THREADS] = wst[u];
+#pragma unroll
+    for (int u = 0; u < SC; ++u)
+        if (tid + u * TAIL_THREADS < N * M) Cl[tid + u * TAIL_THREADS] = cst[u];
+#pragma unroll
+    for (int u = 0; u < SG1; ++u)
+        if (tid + u * TAIL_THREADS < nrdm * na2) gml[tid + u * TAIL_THREADS] = g1st[u];
+#pragma unroll
+    for (int u = 0; u < SG2; ++u)
+        if (tid + u * TAIL_THREADS < nrdm * na4) Gml[tid + u * TAIL_THREADS] = g2st[u];
+#pragma unroll
+    for (int u = 0; u < SK; ++u)
+        if (tid + u * TAIL_THREADS < n_kappa) {
+            krow[tid + u * TAIL_THREADS] = krst[u];
+            kcol[tid + u * TAIL_THREADS] = kcst[u];
+        }
+    __syncthreads();
     TAIL_MARK(2);
     // h_mo[n, x] = sum_q W[n, q] C[q, x]
     for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
@@ -3157,6 +3225,16 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
 
     // ---- stage 3 (cas_panel_kernel with one panel of all N general indices) -----------------------
 #define TAIL_G(n, a, b, c) Gc[(n) * LDG + tab[((a) * M + (b)) * M + (c)]]
+    // One body, instantiated for the active-space sizes the callers reach (nac = na: 2, 3) and once with the size at run
+    // time (nac = 0: any other na, or option tail_generic).  With na a constant the sums below are straight-line code: the
+    // LDS reads of a sum are issued together and its additions follow in the order of the loops, the same
+    // instructions on the same operands as the run-time loops execute; the index arithmetic divides by constants.
+    double* Fl = scr;                                // [nrdm][M][N]  Fock columns
+    double* El = Fl + (size_t)nrdm * M * N;          // [nrdm][N]     Epart
+    const int na_given = na;
+    auto stage3 = [&](auto nac) {
+    constexpr int NA = decltype(nac)::value;
+    const int na = NA > 0 ? NA : na_given, na2 = na * na, na3 = na2 * na, na4 = na2 * na2;
     for (int idx = tid; idx < N * M; idx += TAIL_THREADS) {
         const int n = idx / M, x = idx - n * M;
         double fi = hn[idx];
@@ -3164,21 +3242,52 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         FIn[idx] = fi;
     }
     TAIL_MARK(6);
-    double* Fl = scr;                                // [nrdm][M][N]  Fock columns
-    double* El = Fl + (size_t)nrdm * M * N;          // [nrdm][N]     Epart
     double* Ga = El + (size_t)nrdm * N;              // [N][na3]      g_mo[n, no + w, no + x, no + y]
     double* Dc = Ga + (size_t)N * na3;               // [N][no][na2]  g_mo[n, m, V, W] - 0.5 g_mo[n, W, V, m]
     // the operands of the Fock columns and energy parts gathered once (dense, no table lookup in their sums)
-    for (int idx = tid; idx < N * na3; idx += TAIL_THREADS) {
-        const int n = idx / na3, r = idx - n * na3;
-        const int w = r / na2, x = (r / na) % na, y = r % na;
-        Ga[idx] = TAIL_G(n, no + w, no + x, no + y);
-    }
-    for (int idx = tid; idx < N * no * na2; idx += TAIL_THREADS) {
-        const int n = idx / (no * na2), r = idx - n * (no * na2);
-        const int m = r / na2, v = (r / na) % na, w = r % na;
-        const int V = no + v, W = no + w;
-        Dc[idx] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
+    if constexpr (NA > 0) {
+        // four entries per thread at a time: the table reads, then the reads of Gc they address, then the stores (a
+        // plain loop pays the two dependent LDS latencies per entry: its stores may alias the next entry's reads)
+        constexpr int U = 4;
+        for (int b0 = 0; b0 < N * na3; b0 += U * TAIL_THREADS) {
+            double val[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = b0 + u * TAIL_THREADS + tid < N * na3 ? b0 + u * TAIL_THREADS + tid : 0;
+                const int n = idx / na3, r = idx - n * na3;
+                const int w = r / na2, x = (r / na) % na, y = r % na;
+                val[u] = TAIL_G(n, no + w, no + x, no + y);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (b0 + u * TAIL_THREADS + tid < N * na3) Ga[b0 + u * TAIL_THREADS + tid] = val[u];
+        }
+        for (int b0 = 0; b0 < N * no * na2; b0 += U * TAIL_THREADS) {
+            double val[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int idx = b0 + u * TAIL_THREADS + tid < N * no * na2 ? b0 + u * TAIL_THREADS + tid : 0;
+                const int n = idx / (no * na2), r = idx - n * (no * na2);
+                const int m = r / na2, v = (r / na) % na, w = r % na;
+                const int V = no + v, W = no + w;
+                val[u] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (b0 + u * TAIL_THREADS + tid < N * no * na2) Dc[b0 + u * TAIL_THREADS + tid] = val[u];
+        }
+    } else {
+        for (int idx = tid; idx < N * na3; idx += TAIL_THREADS) {
+            const int n = idx / na3, r = idx - n * na3;
+            const int w = r / na2, x = (r / na) % na, y = r % na;
+            Ga[idx] = TAIL_G(n, no + w, no + x, no + y);
+        }
+        for (int idx = tid; idx < N * no * na2; idx += TAIL_THREADS) {
+            const int n = idx / (no * na2), r = idx - n * (no * na2);
+            const int m = r / na2, v = (r / na) % na, w = r % na;
+            const int V = no + v, W = no + w;
+            Dc[idx] = TAIL_G(n, m, V, W) - 0.5 * TAIL_G(n, W, V, m);
+        }
     }
     __syncthreads();
     TAIL_MARK(7);
@@ -3254,6 +3363,11 @@ void cas_tail_kernel(const double* __restrict__ J, const double* __restrict__ C,
         }
         El[(size_t)k * N + n] = acc;
     }
+    };
+    const int nac = generic ? 0 : na;
+    if (nac == 3) stage3(std::integral_constant<int, 3>{});
+    else if (nac == 2) stage3(std::integral_constant<int, 2>{});
+    else stage3(std::integral_constant<int, 0>{});
 #undef TAIL_G
     __syncthreads();
     TAIL_MARK(10);
@@ -3634,8 +3748,10 @@ static int cas_tail_batched(const CasEvalArgs& a, const EvalPlan& p, const doubl
         hipLaunchKernelGGL((cas_tail_kernel<KS_>), dim3(a.batch), dim3(TAIL_THREADS), p.tail_lds, st, J, a.C, Wpre, \
                            a.gamma, a.Gamma, a.nrdm, a.N, a.n_occ, a.ncas, p.tail_nc, a.nuc, a.nuc_arr, a.kap_row, \
                            a.kap_col, a.n_kappa, a.out.c0, a.out.E, a.out.gvec, a.out.dE, a.out.c1, a.out.c2,       \
-                           a.out_stride);                                                         \
+                           a.out_stride, generic);                                                \
     } while (0)
+    // option tail_generic: stage 3 with the active-space size at run time whatever it is
+    const int generic = oovqe_opt(OOVQE_OPT_TAIL_GENERIC) != 0;
     oovqe_profile_mark_start_l(st, LABEL_P_TO_N);
     OOVQE_TAIL_DISPATCH(tail_depth(a.N, v), OOVQE_LAUNCH_TAIL)
     oovqe_profile_mark_stop(st);

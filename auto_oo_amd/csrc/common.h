@@ -51,6 +51,7 @@ enum oovqe_option_t {
     OOVQE_OPT_STAGE1_FREE_RUN,       // 1: N^4 sweeps enqueued on different streams are not ordered one after the other
     OOVQE_OPT_ONE_STREAM,            // 1: every launch of a call on the caller's stream (no chain of a call on the library's internal streams)
     OOVQE_OPT_TAIL_SPLIT,            // 1: packed-triangle path: the three-launch tail (sym_gm, panel, final) instead of cas_tail_kernel
+    OOVQE_OPT_TAIL_GENERIC,          // 1: cas_tail_kernel runs stage 3 with the active-space size at run time (the loops every size without an instance of its own takes)
     OOVQE_OPT_COUNT
 };
 int oovqe_opt(int id);

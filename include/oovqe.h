@@ -90,7 +90,9 @@ typedef struct {
  * "k1_no_pair", "k1_force_wide", "gm_plain_grid", "newton_one_wg", "sector_unfused",
  * "hess_vk_pass", "hess_own_stage1", "panel_rows" (int), "k1_force_nt" (int),
  * "newton_no_chol", "sector_lambda_w" (int), "sector_rdm_r3" (int),
- * "tail_split" (the three-launch tail of the packed-triangle path instead of the one-workgroup-per-geometry tail);
+ * "tail_split" (the three-launch tail of the packed-triangle path instead of the one-workgroup-per-geometry tail),
+ * "tail_generic" (that tail runs its Fock stage with the active-space size at run time, not the code compiled for 2 or 3
+ * active orbitals);
  * "no_ride": 1 = the circuit + RDM step as a launch of its own, 2 = riding on the launch in front of the Fock stage
  * whatever the batch (0: the library decides by the grid of that launch).
  * All 0 by default; the library never reads environment variables.  tests/ and tools/ only. */

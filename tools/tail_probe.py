@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 NCAS, NELECAS, NELEC = 3, 4, 16
 WGS, MARKS = 512, 32
-PHASES = [(0, 1, "inputs staged (first J loads issued)"), (1, 2, "position table"), (2, 3, "h_mo"),
+PHASES = [(0, 1, "input + first J loads issued, table"), (1, 2, "inputs: registers to LDS"), (2, 3, "h_mo"),
           (3, 4, "q->x, all tiles of (y <= z)"), (4, 5, "p->n over the packed columns"),
           (5, 6, "FI"), (6, 7, "gathers (Ga, Dc)"), (7, 8, "Cpart, c1, c2"), (8, 9, "Fock columns"),
           (9, 10, "energy parts"), (10, 11, "assembly"), (0, 11, "whole workgroup")]
