@@ -213,6 +213,12 @@ void norm1_partial_kernel(const double* __restrict__ X, int N, double* __restric
     part[(size_t)slice * N + c] = (s0 + s1) + (s2 + s3);
 }
 
+// fmax drops a NaN; the host's test for a non-finite input needs it kept
+__device__ __forceinline__ double max_keep_nan(double a, double b)
+{
+    return (a != a || b != b) ? a + b : fmax(a, b);
+}
+
 __global__ __launch_bounds__(256)
 void norm1_kernel(const double* __restrict__ part, int N, double* out)
 {
@@ -222,12 +228,12 @@ void norm1_kernel(const double* __restrict__ part, int N, double* out)
         double cs = 0.0;
 #pragma unroll
         for (int sl = 0; sl < NORM_SLICES; ++sl) cs += part[(size_t)sl * N + c];
-        best = fmax(best, cs);
+        best = max_keep_nan(best, cs);
     }
     red[threadIdx.x] = best;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        if (threadIdx.x < s) red[threadIdx.x] = max_keep_nan(red[threadIdx.x], red[threadIdx.x + s]);
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = red[0];

@@ -107,7 +107,8 @@ extern "C" int oovqe_linesearch_points(const double* flat, const double* dp, con
                                        double* slope, oovqe_stream_t stream)
 {
     OOVQE_REQUIRE(flat && dp && t && points_a, "linesearch_points: null pointer");
-    OOVQE_REQUIRE(n >= 1 && n_a >= 0 && n_a <= n && (n_a == n || points_b) && batch >= 1 && batch <= 65535,
+    // (n_a = 0 means n_a = n, include/oovqe.h: neither writes points_b)
+    OOVQE_REQUIRE(n >= 1 && n_a >= 0 && n_a <= n && (n_a == 0 || n_a == n || points_b) && batch >= 1 && batch <= 65535,
                   "linesearch_points: bad sizes");
     OOVQE_REQUIRE(!slope || grad, "linesearch_points: the slope needs the gradient");
     if (n_a == 0) { n_a = n; }      // no split: everything into points_a

@@ -107,6 +107,50 @@ def _apply_rows(fn, v, shape):
     return fn(unwrap(v).reshape(-1)).reshape(shape)
 
 
+# Below this 1-norm of the diagonal block a block matrix of ``_balanced_blocks`` already takes the cheapest route of
+# ``ops.expm`` (its columns sum to at most twice it: degree 8 up to 0.06, no squaring), so nothing is gained by
+# scaling the other blocks further down; it also keeps X = 0 from being divided by.
+_BALANCE_FLOOR = 2.0 ** -6
+
+
+def _balance_exponent(norm_diag, norm_off):
+    """The smallest e >= 0 with norm_off 2^-e <= max(norm_diag, _BALANCE_FLOOR); 0 when a norm is not finite (the
+    exponential then sees the input as it came)."""
+    ref = max(norm_diag, _BALANCE_FLOOR)
+    if not (np.isfinite(norm_diag) and np.isfinite(norm_off)) or norm_off <= ref:
+        return 0
+    m, e = np.frexp(norm_off / ref)                # norm_off / ref = m 2^e, 0.5 <= m < 1
+    e = int(e) - 1 if m == 0.5 else int(e)
+    while np.ldexp(norm_off, -e) > ref:            # (the quotient was rounded)
+        e += 1
+    return e
+
+
+def _balanced_blocks(X, offs):
+    """The block bidiagonal matrix [[X, A], [0, X]] (one block in ``offs``) or [[X, A, 0], [0, X, B], [0, 0, X]] (two)
+    whose exponential carries the first / second Frechet derivative of exp at X in its upper right block, with every
+    off-diagonal block divided by a power of two so that its 1-norm does not exceed that of X: -> (matrix, c), and the
+    wanted block of the exponential is c times that of exp(matrix).  Exact, because that block is linear in each
+    off-diagonal block and a power of two only moves exponents.
+
+    ``ops.expm`` takes its number of squarings from the 1-norm of the whole matrix.  Unbalanced, a block of tens of
+    Hartree (U (2 F^T) in ``kappa_gradient``) beside a K of norm below 1 costs 11 to 13 squarings of the 2N or 3N
+    matrix where K alone needs 0 to 4, and their rounding: with blocks of magnitude 30 to 100 the wanted block of the
+    float64 algorithm came out with an error of 5e-14 .. 5e-13 of its largest element unbalanced and at most 4e-15
+    balanced (measured on the host, tests/test_rotation_scope_cpu.py)."""
+    N, nb = X.shape[0], len(offs) + 1
+    norms = torch.stack([M.abs().sum(dim=0).max() for M in (X,) + tuple(offs)]).tolist()    # (one readback)
+    blk = torch.zeros((nb * N, nb * N), dtype=F64, device=X.device)
+    c = 1.0
+    for i in range(nb):
+        blk[i * N:(i + 1) * N, i * N:(i + 1) * N] = X
+    for i, M in enumerate(offs):
+        f = float(np.ldexp(1.0, _balance_exponent(norms[0], norms[i + 1])))
+        blk[i * N:(i + 1) * N, (i + 1) * N:(i + 2) * N] = M * (1.0 / f)
+        c *= f
+    return blk, c
+
+
 class _OrbitalRotationRule:
     """Shared chain rule through C(kappa) = C0 expm(-K(kappa)) (oo_energy.py:226-236).
 
@@ -151,23 +195,16 @@ class _OrbitalRotationRule:
         return tabs
 
     def _frechet(self, X, A):
+        blk, c = _balanced_blocks(X, (A,))
         N = X.shape[0]
-        blk = torch.zeros((2 * N, 2 * N), dtype=F64, device=X.device)
-        blk[:N, :N] = X
-        blk[N:, N:] = X
-        blk[:N, N:] = A
-        return ops.expm(blk, 1.0)[:N, N:]
+        return ops.expm(blk, 1.0)[:N, N:] * c
 
     def _frechet2(self, X, A, B):
         N = X.shape[0]
 
         def ordered(P, Q):
-            blk = torch.zeros((3 * N, 3 * N), dtype=F64, device=X.device)
-            for i in range(3):
-                blk[i * N:(i + 1) * N, i * N:(i + 1) * N] = X
-            blk[:N, N:2 * N] = P
-            blk[N:2 * N, 2 * N:] = Q
-            return ops.expm(blk, 1.0)[:N, 2 * N:]
+            blk, c = _balanced_blocks(X, (P, Q))
+            return ops.expm(blk, 1.0)[:N, 2 * N:] * c
         return ordered(A, B) + ordered(B, A)
 
     def _kmat(self, v):
@@ -212,13 +249,7 @@ class _OrbitalRotationRule:
         if U is None:
             return gvec0
         oo = self.oo
-        N = oo.nao
-        X = ops.matmul_nn(U, (2.0 * fock.T).contiguous())
-        blk = torch.zeros((2 * N, 2 * N), dtype=F64, device=oo.device)
-        blk[:N, :N] = K
-        blk[N:, N:] = K
-        blk[:N, N:] = X
-        gK = -ops.expm(blk, 1.0)[:N, N:]
+        gK = -self._frechet(K, ops.matmul_nn(U, (2.0 * fock.T).contiguous()))
         r, c = oo._kap_row.long(), oo._kap_col.long()
         return gK[r, c] - gK[c, r]
 

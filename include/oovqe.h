@@ -154,7 +154,8 @@ int oovqe_expm_skew(const double* kappa, const int32_t* kap_row, const int32_t* 
                     int n_kappa, int N, double* K, double* U, double* work,
                     oovqe_stream_t stream);
 /* U = expm(sign * X) for a general [N,N] matrix X (sign = -1 reproduces math.expm(-X));
- * work: [6*N*N] scratch (only touched when N > 48). */
+ * work: [6*N*N] scratch (only touched when N > 48).  Both calls refuse a NaN or an Inf in the input when N > 48
+ * (the norm is read on the host); up to 48 they return, and U is not finite. */
 int oovqe_expm(const double* X, double sign, int N, double* U, double* work,
                oovqe_stream_t stream);
 
