@@ -40,6 +40,8 @@ from .gto import cross_overlap_batch, overlap_connection_batch   # noqa: E402
 from .gto import point_charge_integrals_batch, point_charge_gradient_batch   # noqa: E402
 from .gto import potential_batch, potential_into   # noqa: E402
 from .gto import density_batch, density_into, orbital_values_batch   # noqa: E402
+from . import adapt                                         # noqa: E402
+from .adapt import AdaptResult, OperatorPool, adapt_vqe     # noqa: E402
 
 __all__ = [
     "Parameterized_circuit", "Moldata", "Moldata_sto3g", "GTOBasis", "integrals_batch", "gto", "scf", "nucgrad", "RHFResult", "rhf_batch", "ao_to_oao", "get_formal_geo", "OO_pqc", "OO_pqc_batch", "OO_energy", "mo_ao_to_mo_oao",
@@ -50,4 +52,5 @@ __all__ = [
     "overlaps", "sector_overlaps", "state_overlaps_oao", "track_roots", "apply_tracking", "cross_overlap_batch",
     "transition_rdm1", "overlap_connection_batch", "point_charge_integrals_batch", "point_charge_gradient_batch",
     "potential_batch", "potential_into", "density_batch", "density_into", "orbital_values_batch",
+    "adapt", "AdaptResult", "OperatorPool", "adapt_vqe",
 ]

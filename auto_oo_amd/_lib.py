@@ -346,6 +346,16 @@ SIGNATURES = {
     "oovqe_rotate_orbitals_batch": (ctypes.c_int, [c_double_p, c_int32_p, c_int32_p, ctypes.c_int,
                                                    ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                                    c_double_p, c_double_p, c_stream]),
+    "oovqe_pool_gradients_batch": (ctypes.c_int, [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  c_int32_p, ctypes.c_int, c_int32_p, c_int32_p, ctypes.c_int,
+                                                  c_double_p, c_stream]),
+    "oovqe_pool_gradients_from_coefficients_work_size": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "oovqe_pool_gradients_from_coefficients_batch": (ctypes.c_int, [c_double_p, ctypes.c_int, c_int32_p, c_int32_p,
+                                                                    c_int32_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                                                    ctypes.c_int, c_double_p, c_double_p,
+                                                                    ctypes.c_int64, ctypes.c_void_p, c_int32_p,
+                                                                    ctypes.c_int, c_int32_p, c_int32_p, ctypes.c_int,
+                                                                    c_double_p, c_double_p, c_stream]),
     "oovqe_oo_newton_step_batch": (ctypes.c_int, [ctypes.POINTER(NewtonStepT), c_stream, c_stream]),
     "oovqe_newton_step_size": (ctypes.c_int, []),
 }

@@ -1357,6 +1357,46 @@ class OO_pqc_batch:
             return self.evaluate(thetas, derivatives=False)[:, 1]
         return self.evaluate(thetas, derivatives=False, mo_coeff=self.rotated_mo_coeff(kappas))[:, 1]
 
+    # ---- ADAPT-VQE on a stack (auto_oo_amd/adapt.py, DESIGN.md section 13) ----------------------------------------
+    def pool_gradients(self, thetas, pool, index=None):
+        """[G, P] (the rows of ``index``): the energy derivative of every geometry with respect to every operator of
+        ``pool`` (``adapt.OperatorPool``) appended behind the circuit with its parameter at 0, at the states
+        psi(thetas[g]) and the current orbitals.  The CAS coefficients come from the evaluation of the stack, read
+        where it leaves them; the operator on every state and the P sparse scalar products per state are ONE library
+        call (``oovqe_pool_gradients_from_coefficients_batch``).  A row has the same bits wherever its geometry stands
+        in the stack and whatever stream the call runs on."""
+        from . import adapt
+        adapt.check_pool(pool, self.pqc, "OO_pqc_batch.pool_gradients")
+        adapt.check_thetas(thetas, self.G, self.n_theta, "OO_pqc_batch.pool_gradients")
+        rows = stack_rows(self.G, index)
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
+        thetas = thetas if thetas.is_contiguous() else thetas.contiguous()
+        out = self.evaluate(thetas, derivatives=False)
+        a = self.ncas
+        c12 = out[:, 3 + self.n_kappa:]                      # c1 | c2 of every geometry (include/oovqe.h)
+        if index is not None:
+            sel = rows_selector(rows, self.device)
+            thetas, c12 = thetas[sel].contiguous(), c12[sel].contiguous()
+        return adapt.gradients_from_coefficients(self.pqc, pool, thetas, c12, c12[:, a * a:], c12.stride(0))
+
+    def set_circuit(self, pqc):
+        """Hand the stack another circuit of the same active space (ADAPT-VQE appends a gate per step).  The resident
+        integrals, their packed copy and symmetry flags, the orbitals and the geometry data stay as they are -- no
+        integral is read again; ``n_theta``, the evaluation plans and the cached step arguments, which are sized by
+        the circuit, are made afresh on next use."""
+        if int(pqc.ncas) != int(self.ncas) or int(pqc.nelecas) != int(self.nelecas):
+            raise ValueError(f"set_circuit: a circuit for CAS({pqc.nelecas}e, {pqc.ncas}o) on a stack of "
+                             f"CAS({self.nelecas}e, {self.ncas}o)")
+        # the workspaces about to be dropped may still be read by work enqueued on the side streams
+        torch.cuda.synchronize(self.device)
+        self.pqc = pqc
+        self.n_theta = int(np.prod(pqc.theta_shape))
+        self._plans = {}
+        self._step_args = None
+        self._flat0 = None
+        self._all_pd_last_step = False
+        self.__dict__.pop("_slabs_in_flight", None)
+
     # ---- exact reference of the stack ------------------------------------------------------------------
     def casci(self, nroots=1, fix_singlet=True, tol=1e-9, max_iter=200):
         """CASCI of every geometry at its current orbitals: the CAS coefficients of the whole stack from ONE

@@ -7,6 +7,8 @@ mkdir -p "$OUT" "$HERE/obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wall -Wno-unused-function"
 pids=()
+# every translation unit of the library: api, cas, ci, circuit, contract*, expm, gto*, hessian, linesearch, newton*,
+# overlap, pool (ADAPT pool gradients), scf, sector*, spin_rdms, step, zvector
 for src in "$HERE"/*.hip; do
     obj="$HERE/obj/$(basename "${src%.hip}").o"
     if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/common.h" -nt "$obj" ] || [ "$HERE/internal.h" -nt "$obj" ] || [ "$HERE/plan.h" -nt "$obj" ] || [ "$HERE/circuit_small.h" -nt "$obj" ] || [ "$HERE/jacobi.h" -nt "$obj" ] || [ "$HERE/gto.h" -nt "$obj" ] || [ "$HERE/gto_grad.h" -nt "$obj" ] || [ "$HERE/sector_tables.h" -nt "$obj" ] || [ "$HERE/../../include/oovqe.h" -nt "$obj" ]; then

@@ -302,6 +302,19 @@ class OO_pqc(OO_energy):
         """oo_pqc.py:132-134"""
         return self.energy_and_gradient(theta)[1]
 
+    def pool_gradients(self, theta, pool):
+        """Extension (ADAPT-VQE, ``auto_oo_amd.adapt``): [P] = the energy derivative with respect to every operator of
+        ``pool`` (an ``adapt.OperatorPool``) appended behind the circuit with its parameter at 0, at the state
+        psi(theta) and the current orbitals -- one application of the active-space operator and P sparse scalar
+        products (``oovqe_pool_gradients_from_coefficients_batch``) instead of P + 1 evaluations of circuits with the
+        candidate appended.  c1, c2 are those of the evaluation this object runs anyway."""
+        from . import adapt
+        adapt.check_pool(pool, self.pqc, "OO_pqc.pool_gradients")
+        adapt.check_thetas(theta, 1, self._n_theta(), "OO_pqc.pool_gradients")
+        res = self._evaluate(theta, derivatives=False)
+        c1, c2 = res["c1"].contiguous(), res["c2"].contiguous()       # (referenced until the call is enqueued)
+        return adapt.gradients_from_coefficients(self.pqc, pool, self.pqc._theta2d(theta), c1, c2, 0)[0]
+
     def full_circuit_hessian_to_matrix(self, full_circuit_hessian):
         """oo_pqc.py:150-153"""
         size = self._n_theta()

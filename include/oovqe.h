@@ -974,6 +974,33 @@ int oovqe_sector_overlap_batch(const double* s, int m, int n_core, int ncas, int
                                const double* bra, int rb, const double* ket, int rk, const int32_t* index, int64_t ld,
                                int mode, int with_signs, double* out, double* core_det, oovqe_stream_t stream);
 
+/* ---- ADAPT-VQE: the energy derivative with respect to every operator of a pool (csrc/pool.hip) -----------------
+ * An operator of the pool is one parameter driving the gates op_first[k] .. op_first[k + 1] - 1 (op_first [n_ops + 1],
+ * int32, device) of a gate table whose pair lists `pairs` are what oovqe_sector_pairs writes for that table
+ * (n_gates <= 65 535, at most 32 767 determinants); gate_sign [n_gates] (int32, device) = the `sign` of every gate.
+ * Appended behind the circuit with its parameter at 0, operator k has the derivative
+ *     out[b][k] = sum over its gates, over the gate's pairs (x, y):  (sign / 2) pi(x) (psi[y] lam[x] - psi[x] lam[y])
+ * for the sector vectors psi_c [batch][na nb] and lam [batch][na nb] = (Hop + Hop^T) psi (oovqe_sector_lambda).
+ * One launch for all states and operators; no floating-point atomics: a result has the same bits wherever its state
+ * stands in the stack and whatever stream it runs on; an operator without pairs in this sector gives exactly 0.0.
+ * The gates must conserve (N_alpha, N_beta) (the lists of others are not valid).  Sizes beyond scope return a negative
+ * code before any launch (oovqe_last_error gives the text).
+ * oovqe_pool_gradients_from_coefficients_batch: the whole step in one call -- lam from the CAS coefficients of every
+ * state (c1 + b c_stride, c2 + b c_stride as for oovqe_sector_lambda_pg, which serves it where
+ * oovqe_sector_geometry_coefficients_ok; a loop over the states inside the library elsewhere), then the launch
+ * above.  tabs: as for oovqe_sector_lambda (may be NULL); work: ..._work_size() doubles. */
+int oovqe_pool_gradients_batch(const double* psi_c, const double* lam, int na, int nb, int batch,
+                               const uint32_t* pairs, int n_gates, const int32_t* op_first, const int32_t* gate_sign,
+                               int n_ops, double* out, oovqe_stream_t stream);
+int64_t oovqe_pool_gradients_from_coefficients_work_size(int ncas, int na, int nb, int batch);
+int oovqe_pool_gradients_from_coefficients_batch(const double* psi_c, int ncas, const uint32_t* unrank_a,
+                                                 const uint32_t* unrank_b, const int32_t* rank_a,
+                                                 const int32_t* rank_b, int na, int nb, int batch, const double* c1,
+                                                 const double* c2, int64_t c_stride, const uint16_t* tabs,
+                                                 const uint32_t* pairs, int n_gates, const int32_t* op_first,
+                                                 const int32_t* gate_sign, int n_ops, double* work, double* out,
+                                                 oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
