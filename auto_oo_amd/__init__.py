@@ -42,6 +42,8 @@ from .gto import potential_batch, potential_into   # noqa: E402
 from .gto import density_batch, density_into, orbital_values_batch   # noqa: E402
 from . import adapt                                         # noqa: E402
 from .adapt import AdaptResult, OperatorPool, adapt_vqe     # noqa: E402
+from . import ensemble                                      # noqa: E402
+from .ensemble import SA_OO_pqc_batch, StateEnsemble, check_ensemble, singlet_states   # noqa: E402
 
 __all__ = [
     "Parameterized_circuit", "Moldata", "Moldata_sto3g", "GTOBasis", "integrals_batch", "gto", "scf", "nucgrad", "RHFResult", "rhf_batch", "ao_to_oao", "get_formal_geo", "OO_pqc", "OO_pqc_batch", "OO_energy", "mo_ao_to_mo_oao",
@@ -53,4 +55,5 @@ __all__ = [
     "transition_rdm1", "overlap_connection_batch", "point_charge_integrals_batch", "point_charge_gradient_batch",
     "potential_batch", "potential_into", "density_batch", "density_into", "orbital_values_batch",
     "adapt", "AdaptResult", "OperatorPool", "adapt_vqe",
+    "ensemble", "SA_OO_pqc_batch", "StateEnsemble", "check_ensemble", "singlet_states",
 ]

@@ -356,6 +356,15 @@ SIGNATURES = {
                                                                     ctypes.c_int64, ctypes.c_void_p, c_int32_p,
                                                                     ctypes.c_int, c_int32_p, c_int32_p, ctypes.c_int,
                                                                     c_double_p, c_double_p, c_stream]),
+    "oovqe_ensemble_work_size": (ctypes.c_int64, [ctypes.c_int] * 5),
+    "oovqe_ensemble_states": (ctypes.c_int, [c_double_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             c_double_p, ctypes.c_int, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                             c_double_p, c_stream]),
+    "oovqe_ensemble_rdms": (ctypes.c_int, [c_double_p, ctypes.c_int, c_double_p] + [ctypes.c_int] * 5
+                            + [c_double_p] * 4 + [c_stream]),
+    "oovqe_ensemble_circuit_hessian_batch": (ctypes.c_int, [c_double_p, c_double_p] + [ctypes.c_int] * 4
+                                             + [c_int32_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                                ctypes.c_int64, c_double_p, c_stream]),
     "oovqe_oo_newton_step_batch": (ctypes.c_int, [ctypes.POINTER(NewtonStepT), c_stream, c_stream]),
     "oovqe_newton_step_size": (ctypes.c_int, []),
 }

@@ -404,6 +404,11 @@ class OO_pqc_batch:
         (more than 10 qubits) raises NotImplementedError -- its RDMs would serve, that path has not been tested."""
         rows = self._gradient_rows(index, "nuclear_gradient")
         gamma, Gamma = self._circuit_rdms(thetas, "nuclear_gradient")
+        return self._nuclear_gradient_from_rdms(gamma, Gamma, rows, chunk)
+
+    def _nuclear_gradient_from_rdms(self, gamma, Gamma, rows, chunk):
+        """``nuclear_gradient`` behind its RDMs: gamma [G, a, a], Gamma [G, a, a, a, a] of the whole stack (the
+        circuit's, or those of an ensemble: ``ensemble.SA_OO_pqc_batch.nuclear_gradient``) -> [len(rows), natm, 3]."""
         _, _, fock = self._cas_batch(gamma[:, None], Gamma[:, None], self.G, want_fock=True)
         step = len(rows) if chunk is None else max(1, int(chunk))
         out = torch.empty((len(rows), self.basis.natm, 3), dtype=F64, device=self.device)

@@ -7,7 +7,7 @@ mkdir -p "$OUT" "$HERE/obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wall -Wno-unused-function"
 pids=()
-# every translation unit of the library: api, cas, ci, circuit, contract*, expm, gto*, hessian, linesearch, newton*,
+# every translation unit of the library: api, cas, ci, circuit, contract*, ensemble, expm, gto*, hessian, linesearch, newton*,
 # overlap, pool (ADAPT pool gradients), scf, sector*, spin_rdms, step, zvector
 for src in "$HERE"/*.hip; do
     obj="$HERE/obj/$(basename "${src%.hip}").o"

@@ -1001,6 +1001,51 @@ int oovqe_pool_gradients_from_coefficients_batch(const double* psi_c, int ncas, 
                                                  const int32_t* gate_sign, int n_ops, double* work, double* out,
                                                  oovqe_stream_t stream);
 
+/* ---- state-averaged OO-VQE: an ensemble of states through one circuit (csrc/ensemble.hip) ----
+ * nstate orthonormal real initial vectors psi0 [nstate][D] (device; superpositions allowed, e.g. the open-shell singlet
+ * (|..a b-bar..> + |..b a-bar..>) / sqrt 2) go through the SAME circuit U(theta) of the gate table; the ensemble is
+ * described by the weights w [nstate] (device).  Fed to oovqe_cas_eval_batch / oovqe_orbital_hessian_batch, the
+ * ensemble RDM sets below give the state-averaged energy E_SA = sum_I w_I <psi0_I| U^T H U |psi0_I>, its gradient and
+ * the kappa blocks of its Hessian (the CAS path is linear in the RDMs); oovqe_ensemble_circuit_hessian_batch gives the
+ * theta-theta block.
+ * Scope: the dense register, 2 <= n_qubits <= OOVQE_ENSEMBLE_MAX_QUBITS (every vector is LDS-resident, D = 2^n_qubits
+ * <= 1024), 1 <= nstate <= OOVQE_ENSEMBLE_MAX_STATES; anything else returns a negative code before any launch, and
+ * oovqe_last_error names the limit.  fp64; every launch on `stream`, no host synchronisation; no atomics and no sum
+ * whose order depends on the grid: a row has the same bits wherever it stands in the stack and whatever the batch
+ * size, and a state of weight exactly 0 is skipped (it contributes exactly nothing).
+ *
+ * oovqe_ensemble_states: theta [batch][n_theta], pairs [n_pairs][2] (int32, device, j <= k; NULL with n_pairs = 0)
+ *   -> vecs [batch][nstate][1 + n_theta + n_pairs][D]: entry 0 the state U(theta) psi0_I, entries 1 .. n_theta its
+ *   tangents d/dtheta_k, then the second tangents d^2/dtheta_j dtheta_k of `pairs`.  A parameter that drives several
+ *   gates contributes the sum over its gates (a second tangent: the double sum over the gates of j and of k; the same
+ *   gate twice gives -1/4 of its block; a differentiated gate annihilates the amplitudes it leaves alone); gates with
+ *   theta_idx < 0 are skipped; a parameter that drives no gate gives an exactly zero tangent.
+ * oovqe_ensemble_rdms: vecs as above with nvec vectors per state, of which the state and the first n_tan tangents are
+ *   read (0 <= n_tan < nvec) -> gamma_sa [batch][1 + n_tan][a^2], Gamma_sa [batch][1 + n_tan][a^4]: set 0 =
+ *   sum_I w_I RDM(psi_I), set k = sum_I w_I (T(tau_I,k, psi_I) + T(psi_I, tau_I,k)), T the transition RDMs of
+ *   oovqe_rdms (the conventions of oovqe_rdms_tangent), summed in the order I = 0, 1, ...; and, unless both pointers
+ *   are NULL, the state and transition RDMs gamma_st [batch][nstate][nstate][a^2], Gamma_st [...][a^4], [I][J] =
+ *   T(psi_I, psi_J).
+ * oovqe_ensemble_circuit_hessian_batch: vecs of oovqe_ensemble_states for the same n_theta and pairs -> H [batch]
+ *   [n_theta][n_theta], H_jk = H_kj = sum_I w_I sum over the four sets T(psi_I,jk, psi_I), T(psi_I,j, psi_I,k),
+ *   T(psi_I,k, psi_I,j), T(psi_I, psi_I,jk) of c1 . gamma + c2 . Gamma (the definition of
+ *   oovqe_circuit_hessian_assemble) for the listed pairs (elements of no listed pair are left untouched).  Row b reads
+ *   c1 + b * c_stride [a^2] and c2 + b * c_stride [a^4] (doubles), e.g. where oovqe_cas_eval_batch leaves them.
+ * oovqe_ensemble_work_size: the doubles of `vecs`, the one buffer the three calls share; needs no device; a negative
+ *   code (oovqe_last_error gives the text) for arguments out of scope. */
+#define OOVQE_ENSEMBLE_MAX_QUBITS 10
+#define OOVQE_ENSEMBLE_MAX_STATES 4
+int64_t oovqe_ensemble_work_size(int n_theta, int n_qubits, int nstate, int n_pairs, int batch);
+int oovqe_ensemble_states(const double* theta, int n_theta, const oovqe_gate_t* gates, int n_gates, int n_qubits,
+                          const double* psi0, int nstate, const int32_t* pairs, int n_pairs, int batch, double* vecs,
+                          oovqe_stream_t stream);
+int oovqe_ensemble_rdms(const double* vecs, int nvec, const double* weights, int n_qubits, int ncas, int nstate,
+                        int n_tan, int batch, double* gamma_sa, double* Gamma_sa, double* gamma_st, double* Gamma_st,
+                        oovqe_stream_t stream);
+int oovqe_ensemble_circuit_hessian_batch(const double* vecs, const double* weights, int n_qubits, int ncas, int nstate,
+                                         int n_theta, const int32_t* pairs, int n_pairs, int batch, const double* c1,
+                                         const double* c2, int64_t c_stride, double* H, oovqe_stream_t stream);
+
 /* 1 when oovqe_circuit_rdms takes its one-workgroup LDS path for these sizes */
 int oovqe_circuit_rdms_is_small(int n_qubits, int ncas, int nvec, int n_gates);
 
