@@ -355,7 +355,7 @@ class OO_pqc_batch:
         as the evaluation path makes them (dense register: ``ops.circuit_rdms``; sector engine: the RDMs of
         ``_evaluate_sector``, served only with ``sector``: NotImplementedError otherwise)."""
         pqc = self.pqc
-        in_sector = getattr(pqc, "_use_sector", False)
+        in_sector = self._sector
         if in_sector and not sector:
             raise NotImplementedError(f"{who} covers dense-register circuits; circuits in the sector engine "
                                       "(more than 10 qubits) are not implemented")
@@ -924,7 +924,7 @@ class OO_pqc_batch:
         (RuntimeError otherwise); ncas <= 8; dense-register circuits only: a circuit of the sector engine (more than 10
         qubits) raises NotImplementedError before anything is launched.  Same bits whatever ``index``."""
         rows = self._moment_rows(index, "electron_density")
-        if getattr(self.pqc, "_use_sector", False):
+        if self._sector:
             raise NotImplementedError("electron_density covers dense-register circuits; circuits in the sector engine "
                                       "(more than 10 qubits) are not implemented")
         out = self._density_of(rows, self._state_density(thetas, rows)[:, None], points, gradient)
@@ -1038,7 +1038,7 @@ class OO_pqc_batch:
         if not ra:
             return torch.empty(0, dtype=F64, device=self.device)
         pqc = self.pqc
-        if getattr(pqc, "_use_sector", False):
+        if self._sector:
             psi, index = pqc._sector.state(thetas), None
         else:
             psi = ops.circuit_state(thetas, pqc._gates_dev, pqc._n_gates, pqc.n_qubits, pqc._init_index)
@@ -1166,20 +1166,34 @@ class OO_pqc_batch:
         """mo_coeff[g] = S^-1/2[g] C_oao[g] for the whole stack (oo_energy.py:173-176), one launch."""
         ops.matmul_nn_batch(self.oao_coeff, self.oao_mo_coeff, out=self.mo_coeff)
 
-    def _plan(self, derivatives, slot=0):
-        key = (bool(derivatives), slot)
+    _sector = property(lambda self: getattr(self.pqc, "_use_sector", False))      # the circuit is in the sector engine
+
+    def _layout(self, derivatives):
+        """The packed output row of ``evaluate`` (``ops.PackedLayout``)."""
+        return ops.PackedLayout(self.n_theta, self.n_kappa, self.ncas, bool(derivatives))
+
+    def _workspace(self, key, work_size, *args, row=None):
+        """``_plans[key]`` = (workspace of ``work_size(*args)`` doubles per geometry, the library's size of a packed
+        output row with the ``ops.PackedLayout`` fields ``row``, or 0), made on first use."""
         if key not in self._plans:
-            pqc = self.pqc
-            wsz = self.lib.oovqe_oo_eval_work_size(self.n_theta, pqc._n_gates, pqc.n_qubits, self.nao,
-                                                   self._n_occ, self.ncas, int(key[0]))
-            osz = self.lib.oovqe_oo_eval_out_size(self.n_theta, self.n_kappa, self.ncas, int(key[0]))
-            work = torch.empty(self.G * wsz, dtype=F64, device=self.device)
-            self._plans[key] = (work, int(osz))
+            osz = self.lib.oovqe_oo_eval_out_size(*row) if row else 0
+            self._plans[key] = (torch.empty(self.G * work_size(*args), dtype=F64, device=self.device), int(osz))
         return self._plans[key]
+
+    def _plan(self, derivatives, slot=0):
+        key, der, pqc = (bool(derivatives), slot), int(bool(derivatives)), self.pqc     # (looked up on every evaluation)
+        return self._plans.get(key) or self._workspace(
+            key, self.lib.oovqe_oo_eval_work_size, self.n_theta, pqc._n_gates, pqc.n_qubits, self.nao, self._n_occ,
+            self.ncas, der, row=(self.n_theta, self.n_kappa, self.ncas, der))
+
+    def _hessian_workspace(self, n_pairs):          # (``energy_gradient_hessian`` and the one-call step share it)
+        return self._workspace(("hessian", 0), self.lib.oovqe_oo_hessian_work_size, self.n_theta, self.pqc._n_gates,
+                               self.pqc.n_qubits, self.nao, self._n_occ, self.ncas, n_pairs,
+                               row=(self.n_theta, self.n_kappa, self.ncas, 1))
 
     def evaluate(self, thetas, derivatives=True, count=None, slot=0, mo_coeff=None):
         """thetas [G, n_theta] (device, fp64) -> packed outputs [G, out_size]
-        ([c0 | E | dE/dtheta | gvec rows | c1 | c2] per geometry, include/oovqe.h).
+        ([c0 | E | dE/dtheta | gvec rows | c1 | c2] per geometry, include/oovqe.h: ``ops.PackedLayout``).
         ``count``: evaluate only the first ``count`` geometries of the batch.
         ``slot``: workspace slot -- calls issued on different HIP streams must use different slots
         (their kernels then overlap: the HBM-bound N^4 sweep of one call runs beside the
@@ -1190,7 +1204,7 @@ class OO_pqc_batch:
         if not 1 <= G <= self.G:
             raise ValueError(f"count must be in 1..{self.G}")
         thetas = ops.as_device(thetas, self.device).reshape(-1, self.n_theta)[:G]
-        if getattr(self.pqc, "_use_sector", False):
+        if self._sector:
             return self._evaluate_sector(thetas, derivatives, G, slot, mo_coeff)
         work, osz = self._plan(derivatives, slot)
         out = torch.empty((G, osz), dtype=F64, device=self.device)
@@ -1209,14 +1223,10 @@ class OO_pqc_batch:
     # ---- circuits in the sector engine ---------------------------------------------------------------
     def _cas_batch(self, gamma, Gamma, G, slot=0, mo_coeff=None, want_fock=False):
         """The CAS path of the first G geometries from RDM sets gamma [G, nrdm, a, a], Gamma [G, nrdm, a,a,a,a]
-        (``oovqe_cas_eval_batch``) -> (packed outputs [G, osz] in the layout of ``evaluate``, n_t, fock or None)."""
+        (``oovqe_cas_eval_batch``) -> (packed rows [G, osz] of ``ops.PackedLayout.for_rdm_sets``, n_t, fock or None)."""
         nrdm = int(gamma.shape[1])
-        key = ("cas", nrdm, slot)
-        if key not in self._plans:
-            wsz = self.lib.oovqe_cas_eval_work_size(self.nao, self._n_occ, self.ncas, nrdm)
-            osz = self.lib.oovqe_oo_eval_out_size(nrdm - 1, self.n_kappa, self.ncas, int(nrdm > 1))
-            self._plans[key] = (torch.empty(self.G * wsz, dtype=F64, device=self.device), int(osz))
-        work, osz = self._plans[key]
+        work, osz = self._workspace(("cas", nrdm, slot), self.lib.oovqe_cas_eval_work_size, self.nao, self._n_occ,
+                                    self.ncas, nrdm, row=(nrdm - 1, self.n_kappa, self.ncas, int(nrdm > 1)))
         out = torch.empty((G, osz), dtype=F64, device=self.device)
         fock = torch.empty((G, self.nao, self.nao), dtype=F64, device=self.device) if want_fock else None
         gamma = gamma if gamma.is_contiguous() else gamma.contiguous()
@@ -1235,33 +1245,57 @@ class OO_pqc_batch:
         the reverse sweep with each geometry's (c1, c2) as cotangents (oo_pqc.py:86-95).  The packed layout is that
         of the dense path; the rows d gvec / d theta_k (the kappa-theta block, which the reverse sweep does not
         produce) are NaN here -- ``energy_gradient_hessian`` delivers them."""
-        pqc, eng = self.pqc, self.pqc._sector
-        nt, nk, a = self.n_theta, self.n_kappa, self.ncas
+        eng, a = self.pqc._sector, self.ncas
         psi = eng.state(thetas)
         g1, g2 = eng.rdms(psi)
         cas, _, _ = self._cas_batch(g1[:, None], g2[:, None], G, slot, mo_coeff)
         if not derivatives:
             return cas
-        osz = int(self.lib.oovqe_oo_eval_out_size(nt, nk, a, 1))
-        out = torch.full((G, osz), float("nan"), dtype=F64, device=self.device)
-        out[:, 0:2] = cas[:, 0:2]                                    # c0, E
-        out[:, 2 + nt:2 + nt + nk] = cas[:, 3:3 + nk]                # gvec row 0 = dE/dkappa
-        c12 = cas[:, 3 + nk:]
-        out[:, 2 + nt + (1 + nt) * nk:] = c12                        # c1 | c2
+        Lc, L = self._layout(False), self._layout(True)
+        out = cas.new_full((G, int(self.lib.oovqe_oo_eval_out_size(*L))), float("nan"))
+        out[:, :2] = cas[:, :2]                                                 # c0, E
+        L.gvec_rows(out)[:, 0] = Lc.gvec_rows(cas)[:, 0]                        # gvec row 0 = dE/dkappa
+        out[:, L.c12] = cas[:, Lc.c12]                                          # c1 | c2
         if eng.geometry_coefficients_ok():
             # every geometry's reverse sweep in one launch sequence, its (c1 | c2) read where the CAS path left them
-            out[:, 2:2 + nt] = eng.adjoint_geometries(thetas, psi, c12, cas.stride(0))
+            out[:, L.dE] = eng.adjoint_geometries(thetas, psi, cas[:, Lc.c12], cas.stride(0))
         else:
-            c1 = c12[:, :a * a].reshape(G, a, a)
-            c2 = c12[:, a * a:].reshape(G, a, a, a, a)
+            c1, c2 = cas[:, Lc.c1].reshape(G, a, a), cas[:, Lc.c2].reshape(G, a, a, a, a)
             for g in range(G):      # (the operator of the reverse sweep takes ONE set of coefficients per call)
-                out[g, 2:2 + nt] = eng.adjoint(thetas[g:g + 1], psi[g:g + 1], c1[g], c2[g])[0]
+                out[g, L.dE] = eng.adjoint(thetas[g:g + 1], psi[g:g + 1], c1[g], c2[g])[0]
         return out
+
+    def _hessian_from_rdm_sets(self, gamma, Gamma, theta_theta):
+        """``energy_gradient_hessian`` of the whole stack from RDM sets gamma [G, 1 + n_theta, a, a], Gamma [G, 1 +
+        n_theta, a, a, a, a] (set 0 the RDMs, set k their derivatives by theta_k: the sector engine's, an ensemble's).
+        Launches, in this order: the CAS path with Fock matrices (E, gradient, kappa-theta blocks), the kappa-kappa
+        blocks in one ``oovqe_orbital_hessian_batch`` call, then the caller's ``theta_theta(out, c12, c_stride) ->
+        [G, n_theta, n_theta]``, given the packed rows ``out`` of the CAS path (``ops.PackedLayout.for_rdm_sets``),
+        their columns ``c12`` (c1 | c2 of every geometry, to be read where they lie) and the stride between rows."""
+        G, nk, nt = self.G, self.n_kappa, int(gamma.shape[1]) - 1
+        L = ops.PackedLayout.for_rdm_sets(1 + nt, nk, self.ncas)
+        out, _, fock = self._cas_batch(gamma, Gamma, G, want_fock=True)
+        gv = L.gvec_rows(out)
+        work, _ = self._workspace(("orbital_hessian", 0), self.lib.oovqe_orbital_hessian_work_size, self.nao, self._n_occ,
+                                  self.ncas)
+        Hkk = torch.empty((G, nk, nk), dtype=F64, device=self.device)
+        # the copies stay referenced until the call is enqueued: a temporary freed inside the argument list goes back
+        # to the caching allocator at once, and the next copy can land in it before the kernel has read it
+        gamma0, Gamma0 = gamma[:, 0].contiguous(), Gamma[:, 0].contiguous()
+        check(self.lib.oovqe_orbital_hessian_batch(
+            dptr(self.int2e_ao), dptr(self.int1e_ao), dptr(self.mo_coeff), dptr(gamma0), dptr(Gamma0), dptr(fock),
+            self.nao, self._n_occ, self.ncas, dptr(self._kap_row, torch.int32), dptr(self._kap_col, torch.int32), nk, G,
+            dptr(work), dptr(Hkk), int(self.eri_flags), stream_ptr()), "oovqe_orbital_hessian_batch")
+        H = torch.empty((G, nt + nk, nt + nk), dtype=F64, device=self.device)
+        H[:, :nt, :nt] = theta_theta(out, out[:, L.c12], out.stride(0))
+        H[:, nt:, nt:] = Hkk
+        H[:, nt:, :nt] = gv[:, 1:].transpose(1, 2)
+        H[:, :nt, nt:] = gv[:, 1:]
+        return out[:, L.E], torch.cat((out[:, L.dE], gv[:, 0]), dim=1), H
 
     def _energy_gradient_hessian_sector(self, thetas):
         pqc, eng = self.pqc, self.pqc._sector
-        G, nt, nk, a = self.G, self.n_theta, self.n_kappa, self.ncas
-        n = nt + nk
+        G, nt, a = self.G, self.n_theta, self.ncas
         st = eng.tangent_states(thetas, pqc._gates, second=True)                 # [G, 1 + nt + n_pairs, Dc]
         psi, tau = st[:, 0:1], st[:, 1:1 + nt]
         # derivative RDMs by polarisation of the plain RDM kernel (exact: the RDMs are quadratic forms of the real
@@ -1272,34 +1306,19 @@ class OO_pqc_batch:
         r2 = r2.reshape(G, 2 * nt + 1, a, a, a, a)
         gamma = torch.cat((r1[:, 0:1], 0.5 * (r1[:, 1:1 + nt] - r1[:, 1 + nt:])), dim=1)
         Gamma = torch.cat((r2[:, 0:1], 0.5 * (r2[:, 1:1 + nt] - r2[:, 1 + nt:])), dim=1)
-        out, _, fock = self._cas_batch(gamma, Gamma, G, want_fock=True)
-        E, dE = out[:, 1], out[:, 2:2 + nt]
-        gv = out[:, 2 + nt:2 + nt + (1 + nt) * nk].reshape(G, 1 + nt, nk)
-        c12 = out[:, 2 + nt + (1 + nt) * nk:]
-        H = torch.empty((G, n, n), dtype=F64, device=self.device)
-        # kappa-kappa blocks of all geometries in one call
-        key = ("orbital_hessian", 0)
-        if key not in self._plans:
-            wsz = self.lib.oovqe_orbital_hessian_work_size(self.nao, self._n_occ, self.ncas)
-            self._plans[key] = (torch.empty(G * wsz, dtype=F64, device=self.device), 0)
-        Hkk = torch.empty((G, nk, nk), dtype=F64, device=self.device)
-        # the copies stay referenced until the call is enqueued: a temporary freed inside the argument list goes back
-        # to the caching allocator at once, and the next copy can land in it before the kernel has read it
-        gamma0, Gamma0 = gamma[:, 0].contiguous(), Gamma[:, 0].contiguous()
-        check(self.lib.oovqe_orbital_hessian_batch(
-            dptr(self.int2e_ao), dptr(self.int1e_ao), dptr(self.mo_coeff), dptr(gamma0),
-            dptr(Gamma0), dptr(fock), self.nao, self._n_occ, self.ncas,
-            dptr(self._kap_row, torch.int32), dptr(self._kap_col, torch.int32), nk, G, dptr(self._plans[key][0]),
-            dptr(Hkk), int(self.eri_flags), stream_ptr()), "oovqe_orbital_hessian_batch")
-        H[:, nt:, nt:] = Hkk
-        H[:, nt:, :nt] = gv[:, 1:].transpose(1, 2)
-        H[:, :nt, nt:] = gv[:, 1:]
-        if eng.geometry_coefficients_ok():
-            # theta-theta blocks: H_jk = tau_jk . lam(psi) + tau_j . lam(tau_k), lam = the operator of EACH geometry
-            # applied to its psi and first tangents -- one launch sequence for all geometries
+
+        def theta_theta(out, c12, c_stride):
+            if not eng.geometry_coefficients_ok():
+                L = self._layout(True)
+                c1, c2 = out[:, L.c1].reshape(G, a, a), out[:, L.c2].reshape(G, a, a, a, a)
+                # (one set of CAS coefficients per application of the operator)
+                return torch.stack([eng.circuit_hessian_from_states(st[g], pqc._gates, c1[g].contiguous(),
+                                                                    c2[g].contiguous()) for g in range(G)])
+            # H_jk = tau_jk . lam(psi) + tau_j . lam(tau_k), lam = the operator of EACH geometry applied to its psi and
+            # first tangents -- one launch sequence for all geometries
             ja, ka, _ = eng.hessian_pair_tables(pqc._gates)
             lam = eng.lam_geometries(st[:, :1 + nt].reshape(G * (1 + nt), eng.Dc), 1 + nt, c12,
-                                     out.stride(0)).reshape(G, 1 + nt, eng.Dc)
+                                     c_stride).reshape(G, 1 + nt, eng.Dc)
             first = (st[:, 1 + nt:] * lam[:, 0:1]).sum(dim=2)                           # [G, n_pairs]
             # tau_j . lam(tau_k): scalar products over the sector dimension, geometry by geometry (elementwise multiply
             # + sum, as SectorEngine.circuit_hessian_from_states: no vendor GEMM on this path)
@@ -1308,15 +1327,9 @@ class OO_pqc_batch:
             Htt = torch.zeros((G, nt, nt), dtype=F64, device=self.device)
             Htt[:, ja, ka] = val
             Htt[:, ka, ja] = val
-            H[:, :nt, :nt] = Htt
-        else:
-            c1 = c12[:, :a * a].reshape(G, a, a)
-            c2 = c12[:, a * a:].reshape(G, a, a, a, a)
-            for g in range(G):      # (one set of CAS coefficients per application of the operator)
-                H[g, :nt, :nt] = eng.circuit_hessian_from_states(st[g], pqc._gates, c1[g].contiguous(),
-                                                                 c2[g].contiguous())
-        grad = torch.cat((dE, gv[:, 0]), dim=1)
-        return E, grad, H
+            return Htt
+
+        return self._hessian_from_rdm_sets(gamma, Gamma, theta_theta)
 
     def evaluate_deferred(self, thetas, derivatives=True, count=None, mo_coeff=None, view=None):
         """``evaluate`` enqueued on one of the library's two side streams (taken in turn, each with a workspace of its
@@ -1326,7 +1339,7 @@ class OO_pqc_batch:
         during which HBM idles) runs under the N^4 sweep of the next call instead of in front of it.  The inputs
         must be complete on the current stream when this is called (the side stream is forked from it here);
         per call the launches and the arithmetic are those of ``evaluate``: the same bits."""
-        if getattr(self.pqc, "_use_sector", False):
+        if self._sector:
             # the sector engine keeps ONE workspace per batch size (not per stream): its calls stay in order on the
             # current stream; the result is complete in stream order, the handle has nothing to wait for
             out = self.evaluate(thetas, derivatives=derivatives, count=count, mo_coeff=mo_coeff)
@@ -1348,19 +1361,20 @@ class OO_pqc_batch:
     def energy_and_gradient(self, thetas, count=None, slot=0, defer=False):
         """-> [G, 1 + n_theta + n_kappa]: column 0 = E, then dE/dtheta, then dE/dkappa.
         ``defer``: -> ``ops.PendingTensor`` of the same (``evaluate_deferred``)."""
-        n_out = 2 + self.n_theta + self.n_kappa
+        piece = self._layout(True).energy_and_gradient
         if defer:
-            return self.evaluate_deferred(thetas, derivatives=True, count=count, view=lambda o: o[:, 1:n_out])
-        out = self.evaluate(thetas, derivatives=True, count=count, slot=slot)
-        return out[:, 1:n_out]
+            return self.evaluate_deferred(thetas, derivatives=True, count=count, view=lambda o: o[:, piece])
+        return self.evaluate(thetas, derivatives=True, count=count, slot=slot)[:, piece]
+
+    def _energy_at(self, thetas, mo_coeff):
+        """[G]: the energies at ``thetas`` and the orbitals ``mo_coeff`` [G, N, N] (None: the current ones)."""
+        return self.evaluate(thetas, derivatives=False, mo_coeff=mo_coeff)[:, ops.PackedLayout.E]
 
     def energy(self, thetas, kappas=None):
         """-> [G] energies (OO_pqc.energy_from_parameters(theta, kappa) per geometry, oo_pqc.py:64-84).
         ``kappas`` [G, n_kappa]: evaluate at the rotated orbitals mo_coeff[g] expm(-K(kappa[g])) --
         one extra launch for all geometries (oovqe_rotate_orbitals_batch)."""
-        if kappas is None:
-            return self.evaluate(thetas, derivatives=False)[:, 1]
-        return self.evaluate(thetas, derivatives=False, mo_coeff=self.rotated_mo_coeff(kappas))[:, 1]
+        return self._energy_at(thetas, None if kappas is None else self.rotated_mo_coeff(kappas))
 
     # ---- ADAPT-VQE on a stack (auto_oo_amd/adapt.py, DESIGN.md section 13) ----------------------------------------
     def pool_gradients(self, thetas, pool, index=None):
@@ -1374,15 +1388,13 @@ class OO_pqc_batch:
         adapt.check_pool(pool, self.pqc, "OO_pqc_batch.pool_gradients")
         adapt.check_thetas(thetas, self.G, self.n_theta, "OO_pqc_batch.pool_gradients")
         rows = stack_rows(self.G, index)
-        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)
-        thetas = thetas if thetas.is_contiguous() else thetas.contiguous()
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)        # (contiguous)
         out = self.evaluate(thetas, derivatives=False)
-        a = self.ncas
-        c12 = out[:, 3 + self.n_kappa:]                      # c1 | c2 of every geometry (include/oovqe.h)
         if index is not None:
             sel = rows_selector(rows, self.device)
-            thetas, c12 = thetas[sel].contiguous(), c12[sel].contiguous()
-        return adapt.gradients_from_coefficients(self.pqc, pool, thetas, c12, c12[:, a * a:], c12.stride(0))
+            thetas, out = thetas[sel].contiguous(), out[sel].contiguous()
+        L = self._layout(False)                              # c1 | c2 of every geometry, read where they lie
+        return adapt.gradients_from_coefficients(self.pqc, pool, thetas, out[:, L.c1], out[:, L.c2], out.stride(0))
 
     def set_circuit(self, pqc):
         """Hand the stack another circuit of the same active space (ADAPT-VQE appends a gate per step).  The resident
@@ -1414,8 +1426,8 @@ class OO_pqc_batch:
         zero1 = torch.zeros((self.G, 1, a, a), dtype=F64, device=self.device)
         zero2 = torch.zeros((self.G, 1) + (a,) * 4, dtype=F64, device=self.device)
         cas, _, _ = self._cas_batch(zero1, zero2, self.G)
-        e, vecs, _, rn, info = ci.casci_packed(cas, 3 + self.n_kappa, a, self.nelecas, nroots, fix_singlet, tol,
-                                               max_iter)
+        e, vecs, _, rn, info = ci.casci_packed(cas, ops.PackedLayout.for_rdm_sets(1, self.n_kappa, a).c12.start, a,
+                                               self.nelecas, nroots, fix_singlet, tol, max_iter)
         bad = torch.nonzero(info != 0).flatten().tolist()
         if bad:
             raise RuntimeError(f"OO_pqc_batch.casci: geometries {bad} did not converge "
@@ -1456,22 +1468,15 @@ class OO_pqc_batch:
         OO_pqc.full_hessian (oo_pqc.py:132-148) with the geometry index as a grid dimension of every
         launch.  Block layout of the Hessian as the reference's: [[tt, (kt)^T], [kt, kk]]."""
         G, nt, nk = self.G, self.n_theta, self.n_kappa
-        n = nt + nk
         thetas = ops.as_device(thetas, self.device).reshape(G, nt)
         pqc = self.pqc
-        if getattr(pqc, "_use_sector", False):
+        if self._sector:
             return self._energy_gradient_hessian_sector(thetas)
         pairs_dev, _, _ = ops._hessian_pair_tables(nt, self.device)
         n_pairs = pairs_dev.shape[0]
-        key = ("hessian", 0)
-        if key not in self._plans:
-            wsz = self.lib.oovqe_oo_hessian_work_size(nt, pqc._n_gates, pqc.n_qubits, self.nao, self._n_occ,
-                                                      self.ncas, n_pairs)
-            osz = self.lib.oovqe_oo_eval_out_size(nt, nk, self.ncas, 1)
-            self._plans[key] = (torch.empty(G * wsz, dtype=F64, device=self.device), int(osz))
-        work, osz = self._plans[key]
+        work, osz = self._hessian_workspace(n_pairs)
         out = torch.empty((G, osz), dtype=F64, device=self.device)
-        H = torch.empty((G, n, n), dtype=F64, device=self.device)
+        H = torch.empty((G, nt + nk, nt + nk), dtype=F64, device=self.device)
         check(self.lib.oovqe_oo_hessian_batch(
             dptr(thetas), nt, dptr(pqc._gates_dev, torch.uint8), pqc._n_gates, pqc.n_qubits,
             ctypes.c_uint32(pqc._init_index), dptr(self.int2e_ao), dptr(self.int1e_ao), dptr(self.mo_coeff),
@@ -1479,7 +1484,7 @@ class OO_pqc_batch:
             dptr(self._kap_col, torch.int32), nk, dptr(pairs_dev, torch.int32), n_pairs, G, dptr(work),
             dptr(out), dptr(H), int(self.eri_flags),
             dptr(self._eri_packed) if self.eri_flags == 3 else None, stream_ptr()), "oovqe_oo_hessian_batch")
-        return out[:, 1], out[:, 2:2 + n], H
+        return out[:, ops.PackedLayout.E], out[:, self._layout(True).gradient], H
 
     def full_gradient(self, thetas):
         """-> [G, n_theta + n_kappa] (OO_pqc.full_gradient per geometry, oo_pqc.py:132-134)."""
@@ -1503,12 +1508,20 @@ class OO_pqc_batch:
         (``oovqe_oo_newton_step_batch``: ~45 launches back to back) and one 32-byte readback; only further trials
         (rare) are driven from here.  ``step_by_calls=True`` (attribute; for tests and measurements) drives every
         stage through its own entry point instead -- the same launches, the same bits."""
+        thetas = ops.as_device(thetas, self.device).reshape(self.G, self.n_theta)        # (contiguous)
+        by_calls = (self.step_by_calls or self.n_theta + self.n_kappa > self.lib.oovqe_newton_direction_max_n()
+                    or self.G > 32767 or self._sector)
+        new_thetas, energies, low = self._lockstep_step(thetas, opt, self._energy_at,
+                                                        self.energy_gradient_hessian if by_calls else None)
+        return new_thetas, energies, (low if defer_lowest else low.checked())
+
+    def _lockstep_step(self, thetas, opt, energy_at, egh):
+        """The body of ``damped_newton_step`` for every driver on the stack (dense, sector engine, ``ensemble``):
+        ``energy_at(thetas, mo_coeff) -> [G]`` is the driver's energy at given orbitals, ``egh(thetas) -> (E, grad, H)``
+        at the current ones (None: the dense stack's ``_newton_step_one_call``, which makes them inside its library
+        call).  -> (new thetas, energies there, lowest eigenvalues as ``ops.PendingLowest``); the orbitals are adopted."""
         from .newton_raphson import BatchedNewtonStep
-        if opt is None:
-            opt = BatchedNewtonStep(verbose=0)
-        nt = self.n_theta
-        thetas = ops.as_device(thetas, self.device).reshape(self.G, nt)
-        thetas = thetas if thetas.is_contiguous() else thetas.contiguous()
+        nt, opt = self.n_theta, (BatchedNewtonStep(verbose=0) if opt is None else opt)
         if self._trial_orbitals is None:
             self._trial_orbitals = (torch.empty_like(self.oao_mo_coeff), torch.empty_like(self.mo_coeff))
 
@@ -1519,22 +1532,19 @@ class OO_pqc_batch:
             t_oao, t_mo = self._trial_orbitals
             self._rotate(self.oao_mo_coeff, pb, t_oao)
             ops.matmul_nn_batch(self.oao_coeff, t_oao, out=t_mo)
-            return self.evaluate(pa, derivatives=False, mo_coeff=t_mo)[:, 1]
+            return energy_at(pa, t_mo)
 
-        n = nt + self.n_kappa
-        if (self.step_by_calls or n > self.lib.oovqe_newton_direction_max_n() or self.G > 32767
-                or getattr(self.pqc, "_use_sector", False)):
-            E, grad, H = self.energy_gradient_hessian(thetas)
-            flat = self._flat0
-            if flat is None:
-                flat = self._flat0 = torch.zeros((self.G, n), dtype=F64, device=self.device)
-            flat[:, :nt] = thetas                    # (the kappa part stays zero: steps start at the current orbitals)
+        if egh is None:
+            new_thetas, new_kappas, low, energies = self._newton_step_one_call(thetas, opt, trial)
+        else:
+            E, grad, H = egh(thetas)
+            if self._flat0 is None:
+                self._flat0 = torch.zeros((self.G, nt + self.n_kappa), dtype=F64, device=self.device)
+            self._flat0[:, :nt] = thetas             # (the kappa part stays zero: steps start at the current orbitals)
             # the energy at the accepted trial point IS the energy at the new parameters, so the loop body's closing
             # evaluation (oo_pqc.py:195) is not repeated
             (new_thetas, new_kappas), low, energies = opt.damped_newton_steps_flat(
-                trial, flat, grad, H, energy0=E, defer_lowest=True, split=nt, return_energy=True)
-        else:
-            new_thetas, new_kappas, low, energies = self._newton_step_one_call(thetas, opt, trial)
+                trial, self._flat0, grad, H, energy0=E, defer_lowest=True, split=nt, return_energy=True)
         if opt.last_search_gave_up:
             self.rotate_(new_kappas)                 # (some problems went back to their old parameters)
         else:
@@ -1544,7 +1554,7 @@ class OO_pqc_batch:
             t_oao, t_mo = self._trial_orbitals
             self._trial_orbitals = (self.oao_mo_coeff, self.mo_coeff)
             self.oao_mo_coeff, self.mo_coeff = t_oao, t_mo
-        return new_thetas, energies, (low if defer_lowest else low.checked())
+        return new_thetas, energies, low
 
     def _step_block(self):
         """The argument block of oovqe_oo_newton_step_batch with everything that does not change from step to
@@ -1556,12 +1566,8 @@ class OO_pqc_batch:
         n = nt + nk
         pairs_dev, _, _ = ops._hessian_pair_tables(nt, self.device)
         n_pairs = int(pairs_dev.shape[0])
-        osz1 = int(lib.oovqe_oo_eval_out_size(nt, nk, self.ncas, 1))
         osz0 = int(lib.oovqe_oo_eval_out_size(nt, nk, self.ncas, 0))
-        key = ("hessian", 0)
-        if key not in self._plans:
-            wsz = lib.oovqe_oo_hessian_work_size(nt, pqc._n_gates, pqc.n_qubits, N, self._n_occ, self.ncas, n_pairs)
-            self._plans[key] = (torch.empty(G * wsz, dtype=F64, device=self.device), osz1)
+        work_hessian, osz1 = self._hessian_workspace(n_pairs)
         work_eval, _ = self._plan(False, 0)
         b = _lib.NewtonStepT()
         keep = {"pairs": pairs_dev, "trial_out": torch.empty((G, osz0), dtype=F64, device=self.device),
@@ -1585,7 +1591,7 @@ class OO_pqc_batch:
         b.gates = pqc._gates_dev.data_ptr()
         b.kap_row, b.kap_col = self._kap_row.data_ptr(), self._kap_col.data_ptr()
         b.pairs = pairs_dev.data_ptr()
-        b.work_hessian = self._plans[key][0].data_ptr()
+        b.work_hessian = work_hessian.data_ptr()
         b.work_eval = work_eval.data_ptr()
         b.work_pd = keep["work_pd"].data_ptr() if has_pd else None
         b.work_rest = keep["work_rest"].data_ptr()

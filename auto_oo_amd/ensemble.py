@@ -153,6 +153,10 @@ class SA_OO_pqc_batch:
     def n_kappa(self):
         return self.batch.n_kappa
 
+    def _layout(self, nrdm):
+        """The packed rows of the batch's CAS path fed with ``nrdm`` ensemble RDM sets."""
+        return ops.PackedLayout.for_rdm_sets(nrdm, self.n_kappa, self.batch.ncas)
+
     def _thetas(self, thetas, who):
         nt = self.n_theta
         shape = tuple(thetas.shape) if hasattr(thetas, "shape") else tuple(np.shape(thetas))
@@ -204,16 +208,15 @@ class SA_OO_pqc_batch:
         core energy drop out: the states are orthonormal)."""
         thetas = self._thetas(thetas, "hamiltonian")
         g1, g2, t1, t2 = self.rdms(thetas, transition=True)
-        b, a = self.batch, self.batch.ncas
-        out, _, _ = b._cas_batch(g1, g2, self.G)
-        c0 = out[:, 0]
-        c1 = out[:, 3 + b.n_kappa:3 + b.n_kappa + a * a].reshape(self.G, 1, 1, a * a)
-        c2 = out[:, 3 + b.n_kappa + a * a:].reshape(self.G, 1, 1, a ** 4)
+        out, _, _ = self.batch._cas_batch(g1, g2, self.G)
+        L = self._layout(1)
+        c1 = out[:, L.c1].reshape(self.G, 1, 1, -1)
+        c2 = out[:, L.c2].reshape(self.G, 1, 1, -1)
         H = (t1.reshape(self.G, self.S, self.S, -1) * c1).sum(dim=3) \
             + (t2.reshape(self.G, self.S, self.S, -1) * c2).sum(dim=3)
         H = 0.5 * (H + H.transpose(1, 2))
         eye = torch.eye(self.S, dtype=F64, device=self.device)
-        return H + c0[:, None, None] * eye
+        return H + out[:, L.c0, None, None] * eye
 
     def state_energies(self, thetas):
         """[G, S]: <psi_I| H |psi_I>, the diagonal of ``hamiltonian``."""
@@ -234,7 +237,7 @@ class SA_OO_pqc_batch:
     # ---- energy, gradient, Hessian ------------------------------------------------------------------------------------
     def _energy_at(self, thetas, mo_coeff):
         g1, g2 = self.rdms(thetas)
-        return self.batch._cas_batch(g1, g2, self.G, mo_coeff=mo_coeff)[0][:, 1]
+        return self.batch._cas_batch(g1, g2, self.G, mo_coeff=mo_coeff)[0][:, ops.PackedLayout.E]
 
     def energy(self, thetas, kappas=None):
         """[G]: E_SA at the batch's orbitals, or (``kappas`` [G, n_kappa]) at mo_coeff[g] expm(-K(kappa[g]))."""
@@ -246,77 +249,37 @@ class SA_OO_pqc_batch:
         thetas = self._thetas(thetas, "energy_and_gradient")
         g1, g2 = self.rdms(thetas, derivatives=True)
         out, _, _ = self.batch._cas_batch(g1, g2, self.G)
-        return out[:, 1:2 + self.n_theta + self.n_kappa]
+        return out[:, self._layout(1 + self.n_theta).energy_and_gradient]
 
     def energy_gradient_hessian(self, thetas):
         """(E_SA [G], gradient [G, n], Hessian [G, n, n]), n = n_theta + n_kappa, in the block layout of
         ``OO_pqc_batch.energy_gradient_hessian``: [[tt, (kt)^T], [kt, kk]]."""
         thetas = self._thetas(thetas, "energy_gradient_hessian")
-        b, G, nt, nk, a = self.batch, self.G, self.n_theta, self.n_kappa, self.batch.ncas
-        n = nt + nk
+        a, nt = self.batch.ncas, self.n_theta
         pairs_dev, _, _ = ops._hessian_pair_tables(nt, self.device)
         vecs = self._states(thetas, pairs_dev)
         gamma, Gamma, _, _ = self._rdms(vecs, nt, False)
-        out, _, fock = b._cas_batch(gamma, Gamma, G, want_fock=True)
-        E, dE = out[:, 1], out[:, 2:2 + nt]
-        gv = out[:, 2 + nt:2 + nt + (1 + nt) * nk].reshape(G, 1 + nt, nk)
-        c12 = out[:, 2 + nt + (1 + nt) * nk:]
-        H = torch.empty((G, n, n), dtype=F64, device=self.device)
-        key = ("orbital_hessian", 0)
-        if key not in b._plans:
-            wsz = self.lib.oovqe_orbital_hessian_work_size(b.nao, b._n_occ, a)
-            b._plans[key] = (torch.empty(G * wsz, dtype=F64, device=self.device), 0)
-        Hkk = torch.empty((G, nk, nk), dtype=F64, device=self.device)
-        # (the copies stay referenced until the call is enqueued, as in OO_pqc_batch._energy_gradient_hessian_sector)
-        gamma0, Gamma0 = gamma[:, 0].contiguous(), Gamma[:, 0].contiguous()
-        check(self.lib.oovqe_orbital_hessian_batch(
-            dptr(b.int2e_ao), dptr(b.int1e_ao), dptr(b.mo_coeff), dptr(gamma0), dptr(Gamma0), dptr(fock), b.nao,
-            b._n_occ, a, dptr(b._kap_row, torch.int32), dptr(b._kap_col, torch.int32), nk, G, dptr(b._plans[key][0]),
-            dptr(Hkk), int(b.eri_flags), stream_ptr()), "oovqe_orbital_hessian_batch")
-        Htt = torch.empty((G, nt, nt), dtype=F64, device=self.device)
-        check(self.lib.oovqe_ensemble_circuit_hessian_batch(
-            dptr(vecs), dptr(self.ensemble.weights), 2 * a, a, self.S, nt, dptr(pairs_dev, torch.int32),
-            int(pairs_dev.shape[0]), G, ctypes.c_void_p(c12.data_ptr()), ctypes.c_void_p(c12.data_ptr() + 8 * a * a),
-            int(out.stride(0)), dptr(Htt), stream_ptr()), "oovqe_ensemble_circuit_hessian_batch")
-        H[:, :nt, :nt] = Htt
-        H[:, nt:, nt:] = Hkk
-        H[:, nt:, :nt] = gv[:, 1:].transpose(1, 2)
-        H[:, :nt, nt:] = gv[:, 1:]
-        return E, torch.cat((dE, gv[:, 0]), dim=1), H
+
+        def theta_theta(out, c12, c_stride):
+            L = self._layout(1 + nt)
+            Htt = torch.empty((self.G, nt, nt), dtype=F64, device=self.device)
+            check(self.lib.oovqe_ensemble_circuit_hessian_batch(
+                dptr(vecs), dptr(self.ensemble.weights), 2 * a, a, self.S, nt, dptr(pairs_dev, torch.int32),
+                int(pairs_dev.shape[0]), self.G, ctypes.c_void_p(out[:, L.c1].data_ptr()),
+                ctypes.c_void_p(out[:, L.c2].data_ptr()), int(c_stride), dptr(Htt), stream_ptr()),
+                "oovqe_ensemble_circuit_hessian_batch")
+            return Htt
+
+        return self.batch._hessian_from_rdm_sets(gamma, Gamma, theta_theta)
 
     # ---- optimisation ---------------------------------------------------------------------------------------------------
     def damped_newton_step(self, thetas, opt=None):
-        """One damped Newton step on (theta, kappa) of every geometry in lockstep, as ``OO_pqc_batch.damped_newton_step``
-        drives it stage by stage: gradient + Hessian of E_SA, the G directions, a line search whose trials evaluate the
+        """One damped Newton step on (theta, kappa) of every geometry in lockstep (``OO_pqc_batch._lockstep_step``
+        driven stage by stage): gradient + Hessian of E_SA, the G directions, a line search whose trials evaluate the
         ensemble energy of all geometries at once.  The accepted orbitals are adopted by the wrapped batch.
         -> (new thetas [G, n_theta], E_SA at the new parameters [G], lowest Hessian eigenvalues [G])."""
-        from .newton_raphson import BatchedNewtonStep
-        if opt is None:
-            opt = BatchedNewtonStep(verbose=0)
-        b, nt = self.batch, self.n_theta
-        thetas = self._thetas(thetas, "damped_newton_step")
-        if b._trial_orbitals is None:
-            b._trial_orbitals = (torch.empty_like(b.oao_mo_coeff), torch.empty_like(b.mo_coeff))
-
-        def trial(pa, pb):
-            # the orbitals of a trial are formed as an accepted step forms them (OO_pqc_batch.damped_newton_step)
-            t_oao, t_mo = b._trial_orbitals
-            b._rotate(b.oao_mo_coeff, pb, t_oao)
-            ops.matmul_nn_batch(b.oao_coeff, t_oao, out=t_mo)
-            return self._energy_at(pa.reshape(self.G, nt), t_mo)
-
-        E, grad, H = self.energy_gradient_hessian(thetas)
-        flat = torch.zeros((self.G, nt + self.n_kappa), dtype=F64, device=self.device)
-        flat[:, :nt] = thetas
-        (new_thetas, new_kappas), low, energies = opt.damped_newton_steps_flat(
-            trial, flat, grad.contiguous(), H, energy0=E.contiguous(), defer_lowest=True, split=nt,
-            return_energy=True)
-        if opt.last_search_gave_up:
-            b.rotate_(new_kappas)
-        else:
-            t_oao, t_mo = b._trial_orbitals
-            b._trial_orbitals = (b.oao_mo_coeff, b.mo_coeff)
-            b.oao_mo_coeff, b.mo_coeff = t_oao, t_mo
+        new_thetas, energies, low = self.batch._lockstep_step(self._thetas(thetas, "damped_newton_step"), opt,
+                                                              self._energy_at, self.energy_gradient_hessian)
         return new_thetas, energies, low.checked()
 
     def full_optimization(self, thetas, max_iterations=50, conv_tol=1e-10):

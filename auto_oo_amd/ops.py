@@ -5,6 +5,7 @@ device pointers to liboovqe_hip.so and returns torch tensors.  No arithmetic hap
 there is no CPU path: every call needs a HIP device.
 """
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -461,6 +462,39 @@ def cas_eval(g_ao, h_ao, C, gamma, Gamma, nuc, n_occ, ncas, kap_row, kap_col, wa
                 Gm=Gm, hmo=hmo, packed=packed)
 
 
+def _behind(piece, n):
+    return slice(piece.stop, piece.stop + n)
+
+
+class PackedLayout(namedtuple("PackedLayout", "n_theta n_kappa ncas derivatives")):
+    """The pieces of a packed output row [c0 | E | dE/dtheta | gvec rows | c1 (a^2) | c2 (a^4)] (include/oovqe.h) in its
+    two forms: with ``derivatives`` dE has n_theta slots (one when n_theta = 0) and gvec ``nvec = 1 + n_theta`` rows of
+    n_kappa (row 0 = dE/dkappa, row k = d^2E / dkappa dtheta_k); without, dE has one unused slot and gvec one row.
+    ``c0``, ``E``: columns; the others: slices (``c12.start``: the offset of c1 | c2 that some entry points take;
+    ``gradient`` = [dE/dtheta | dE/dkappa], side by side in the form with derivatives for n_theta >= 1, E in front of
+    them).  Arithmetic only: allocations are still sized by ``oovqe_oo_eval_out_size``."""
+    __slots__ = ()
+    c0, E = 0, 1
+    nvec = property(lambda s: 1 + s.n_theta if s.derivatives else 1)
+    dE = property(lambda s: slice(2, 2 + max(s.nvec - 1, 1)))
+    gvec = property(lambda s: _behind(s.dE, s.nvec * s.n_kappa))
+    c1 = property(lambda s: _behind(s.gvec, s.ncas ** 2))
+    c2 = property(lambda s: _behind(s.c1, s.ncas ** 4))
+    c12 = property(lambda s: _behind(s.gvec, s.ncas ** 2 + s.ncas ** 4))
+    size = property(lambda s: s.c12.stop)
+    gradient = property(lambda s: slice(2, 2 + s.n_theta + s.n_kappa))
+    energy_and_gradient = property(lambda s: slice(1, s.gradient.stop))
+
+    @classmethod
+    def for_rdm_sets(cls, nrdm, n_kappa, ncas):
+        """The row ``oovqe_cas_eval_batch`` writes for ``nrdm`` RDM sets (set 0 the RDMs, sets k >= 1 derivatives)."""
+        return cls(nrdm - 1, n_kappa, ncas, nrdm > 1)
+
+    def gvec_rows(self, out):
+        """gvec of the rows ``out`` [G, size] -> [G, nvec, n_kappa]."""
+        return out[:, self.gvec].view(out.shape[0], self.nvec, self.n_kappa)
+
+
 class OoEvalPlan:
     """Pre-resolved arguments + persistent workspace for oovqe_oo_eval (one geometry, one circuit).
     Calling it costs one small allocation (the packed result) and one ctypes call."""
@@ -476,12 +510,12 @@ class OoEvalPlan:
         self.N = h_ao.shape[0]
         self.n_theta, self.ncas, self.derivatives = n_theta, ncas, bool(derivatives)
         self.n_kappa = kap_row.numel()
-        self.nvec = 1 + n_theta if derivatives else 1
-        self.n_t = max(self.nvec - 1, 1)
         wsz = self.lib.oovqe_oo_eval_work_size(n_theta, n_gates, n_qubits, self.N, n_occ, ncas,
                                                int(self.derivatives))
         self.work = torch.empty(wsz, dtype=F64, device=self.dev)
-        self.out_size = 2 + self.n_t + self.nvec * self.n_kappa + ncas ** 2 + ncas ** 4
+        L = PackedLayout(n_theta, self.n_kappa, ncas, self.derivatives)
+        self.out_size = L.size
+        self._pieces = (L.nvec, L.dE, L.gvec, L.c1, L.c2, L.energy_and_gradient)
         self._keep = (gates_dev, g_ao, h_ao, kap_row, kap_col)
         self._pre = (n_theta, ctypes.c_void_p(gates_dev.data_ptr()), n_gates, n_qubits,
                      ctypes.c_uint32(init_index), dptr(g_ao), dptr(h_ao))
@@ -511,15 +545,11 @@ class OoEvalPlan:
         return out
 
     def unpack(self, out):
-        nk, a = self.n_kappa, self.ncas
-        o = 2 + self.n_t
-        gvec = out[o:o + self.nvec * nk].view(self.nvec, nk)
-        o += self.nvec * nk
-        c1 = out[o:o + a * a].view(a, a)
-        c2 = out[o + a * a:o + a * a + a ** 4].view((a,) * 4)
-        packed = out[1:2 + (self.nvec - 1) + nk] if self.nvec > 1 else None
-        return dict(c0=out[0:1], E=out[1:2], dE=out[2:2 + self.nvec - 1], gvec=gvec, c1=c1, c2=c2,
-                    packed=packed, fock=None, gmat=None, Gm=None, hmo=None)
+        nvec, dE, gvec, c1, c2, packed = self._pieces
+        a, der = self.ncas, self.derivatives
+        return dict(c0=out[0:1], E=out[1:2], dE=out[dE] if der else out[:0], gvec=out[gvec].view(nvec, self.n_kappa),
+                    c1=out[c1].view(a, a), c2=out[c2].view((a,) * 4), packed=out[packed] if der else None,
+                    fock=None, gmat=None, Gm=None, hmo=None)
 
 
 def orbital_hessian(g_ao, h_ao, C, gamma, Gamma, fock, n_occ, ncas, kap_row, kap_col,

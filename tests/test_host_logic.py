@@ -387,3 +387,36 @@ def test_points_host():
         with pytest.raises(ValueError) as err:
             gto.points_host(pts, 2)
         assert str(err.value) == "the points must be finite"
+
+
+# ---- the packed output row of an evaluation (auto_oo_amd/ops.py PackedLayout, include/oovqe.h) -----------------------------
+def test_packed_layout_follows_the_header():
+    """[c0 | E | dE/dtheta (n_theta slots, or 1 when derivatives == 0) | gvec (nvec x n_kappa) | c1 (a^2) | c2 (a^4)],
+    nvec = derivatives ? 1 + n_theta : 1: the size is the library's, the pieces tile the row in that order, and the rows
+    of ``oovqe_cas_eval_batch`` are those of ``oovqe_oo_eval_out_size(nrdm - 1, n_kappa, ncas, nrdm > 1)``."""
+    import itertools
+    from auto_oo_amd.ops import PackedLayout
+    lib = _lib.load()
+    for nt, nk, a, der in itertools.product(range(4), range(1, 5), (2, 3), (0, 1)):
+        L = PackedLayout(nt, nk, a, der)
+        assert L.size == lib.oovqe_oo_eval_out_size(nt, nk, a, der), (nt, nk, a, der)
+        assert L.nvec == (1 + nt if der else 1)
+        pieces = [slice(L.c0, L.c0 + 1), slice(L.E, L.E + 1), L.dE, L.gvec, L.c1, L.c2]
+        assert pieces[0].start == 0 and pieces[-1].stop == L.size
+        assert all(p.stop == q.start for p, q in zip(pieces, pieces[1:])), (nt, nk, a, der)      # no gap, no overlap
+        assert [p.stop - p.start for p in pieces] == [1, 1, max(1, nt) if der else 1, L.nvec * nk, a ** 2, a ** 4]
+        assert L.c12 == slice(L.c1.start, L.c2.stop)
+        assert L.energy_and_gradient == slice(1, 2 + nt + nk) and L.gradient == slice(2, 2 + nt + nk)
+        row = torch.arange(2 * L.size, dtype=torch.float64).reshape(2, L.size)
+        gv = L.gvec_rows(row)
+        assert tuple(gv.shape) == (2, L.nvec, nk) and torch.equal(gv.reshape(2, -1), row[:, L.gvec])
+        assert gv.data_ptr() == row[:, L.gvec].data_ptr()                                         # a view of the rows
+        if der and nt:
+            assert torch.equal(row[:, L.energy_and_gradient],
+                               torch.cat((row[:, L.E:L.E + 1], row[:, L.dE], gv[:, 0]), dim=1))
+        with pytest.raises(AttributeError):
+            L.n_theta = 1                                                                         # immutable
+    for nrdm, nk, a in itertools.product(range(1, 5), range(1, 5), (2, 3)):
+        L = PackedLayout.for_rdm_sets(nrdm, nk, a)
+        assert L == PackedLayout(nrdm - 1, nk, a, nrdm > 1) and L.nvec == nrdm
+        assert L.size == lib.oovqe_oo_eval_out_size(nrdm - 1, nk, a, int(nrdm > 1))

@@ -897,3 +897,45 @@ def test_band_route_beside_a_kernel_that_holds_the_chip():
         else:
             assert bool(torch.isnan(dp[k]).all())
         assert abs(low2[k].item() - lr) < 1e-11 * n and (dp2[k].cpu() - dr).abs().max() <= tol
+
+
+def _step_driver(kind):
+    """(driver, the stack under it, start thetas) of the three drivers of a lockstep step: the dense stack at CAS(2,2),
+    G = 3, stepping through its single entry points; a circuit in the sector engine at CAS(4,4), G = 2 (built as
+    ``test_sector_circuits_in_the_geometry_batch_cas44`` builds it); the ensemble of two singlets on the dense stack."""
+    from tests import _ensemble as T, test_ensemble_gpu as TE
+    if kind == "sector":
+        from tests.test_full_size_gpu import _sector_batch
+        pqc, _, _, batch = _sector_batch(10, 4, 4, 8, 2, 7100, "kupccd", k=1)
+        assert pqc._sector.fits()
+        pqc._use_sector = True
+        thetas = torch.tensor(np.random.default_rng(71).normal(0, 0.3, (2, int(pqc.theta_shape))), device="cuda")
+        return batch, batch, thetas
+    name = "cas22_fabric1"
+    batch, _ = TE.synthetic_batch.__wrapped__(name, 3)          # (a stack of its own: the step moves its orbitals)
+    thetas = TE.to_dev(TE.synthetic_thetas(name, 3))
+    if kind == "dense":
+        batch.step_by_calls = True
+        return batch, batch, thetas
+    ens = aoo.StateEnsemble(TE.circuit(name), T.initial_states(name, "singlet2"), T.WEIGHTS["equal2"])
+    return aoo.SA_OO_pqc_batch(batch, ens), batch, thetas
+
+
+@pytest.mark.parametrize("kind", ["dense", "sector", "ensemble"])
+def test_accepted_trial_is_the_new_point_for_every_driver(kind):
+    """The contract of the step body the three drivers share: after a step whose search did not give up, the accepted
+    trial's buffers ARE the new orbitals and its energy IS the closing energy -- the returned energies are the driver's
+    energy at the new parameters and ``mo_coeff = S^-1/2 C_oao`` holds, bit for bit (the same kernels on the same
+    inputs)."""
+    driver, batch, thetas = _step_driver(kind)
+    opt = aoo.BatchedNewtonStep(verbose=0)
+    e_before = driver.energy(thetas)
+    new_thetas, energies, low = driver.damped_newton_step(thetas, opt)
+    assert not opt.last_search_gave_up
+    assert (energies < e_before).all()
+    e_again = driver.energy(new_thetas)
+    mo = ops.matmul_nn_batch(batch.oao_coeff, batch.oao_mo_coeff)
+    print(f"{kind}: |E(new thetas) - returned| {(e_again - energies).abs().max().item():.2e}, "
+          f"|mo_coeff - S^-1/2 C_oao| {(batch.mo_coeff - mo).abs().max().item():.2e}")
+    assert torch.equal(e_again, energies)
+    assert torch.equal(batch.mo_coeff, mo)
